@@ -16,7 +16,13 @@ Transfers and the noise generator overlap compute on side streams (restore.resto
 Weak scaling: every rank owns its own 30-frame clip (the chunk_for_devices split of a 30*N-frame clip,
 elvis.py:255-280).  value = frames restored by all ranks / max-over-ranks step time.
 
-Extra keys of the JSON line
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, dtype,
+config).  `--dump-outputs DIR` then also writes what the last timed step returned to the caller - the restored uint8
+frames, rank 0's whole sequence when N > 1 - as DIR/restored_frames.npy in float32: a fixed seeded sample of
+DUMP_SAMPLES elements of the flattened [frames, H, W, 3] array (the inputs are seeded too, so two builds can be
+compared output for output).
+
+Extra keys of the JSON line, measured only with `--full` (the --no-* options drop parts of it)
   hbm_resident - the same step with inputs and outputs resident in HBM (no PCIe, no noise generation): the
                  round-1 figure, kept for comparison; never `value`
   roofline     - the dominant kernel (implicit-GEMM conv on MFMA): algorithmic FLOPs / HIP-event time measured
@@ -47,6 +53,8 @@ sys.path.insert(0, ROOT)
 PEAK_TFLOPS = {"f16": 2500.0, "f32": 157.3}
 HBM_PEAK_GBS = 8000.0
 TRAFFIC_FILE = "profiles/r03_hbm_traffic.json"
+DUMP_SAMPLES = 8 << 20   # float32 elements of --dump-outputs: 32 MB, half the 64 MB cap
+DUMP_SEED = 20261016
 
 
 def parse(argv=None):
@@ -75,6 +83,11 @@ def parse(argv=None):
                          "rank 0's download of the gathered clip - exercises the N > 1 code path on a one-GPU box")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the in_tolerance / staged / slots blocks (the headline, roofline, cpu_baseline and parity stay)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else the line can hold (hbm_resident, roofline, "
+                         "cpu_baseline, parity, in_tolerance, staged_schedule, slots, dist; slot runs: kernel table and parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the restored frames of the last timed step (a fixed seeded sample, float32) to DIR/restored_frames.npy")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU check of the --gpus launcher: gloo ranks, one all-gather of synthetic frames, no kernels")
     return ap.parse_args(argv)
@@ -270,6 +283,18 @@ def _timed_steps(step, warmup, steps):
     return (time.perf_counter() - t0) / steps
 
 
+def dump_outputs(directory, frames_u8):
+    """--dump-outputs: the restored uint8 frames (a host tensor) as DIR/restored_frames.npy in float32 - whole when they hold
+    at most DUMP_SAMPLES elements, else the elements at DUMP_SAMPLES seeded positions of the flattened array (sorted, duplicates
+    dropped: the same positions in every run with the same arguments)."""
+    import numpy as np
+    a = frames_u8.numpy()
+    if a.size > DUMP_SAMPLES:
+        a = a.reshape(-1)[np.unique(np.random.default_rng(DUMP_SEED).integers(0, a.size, DUMP_SAMPLES))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "restored_frames.npy"), a.astype(np.float32))
+
+
 def slot_parity(kind, dev):
     """f16 (the slot's default) and fp32 against oracle/restorers_ref.py on a small clip of the FULL slot config."""
     import numpy as np
@@ -303,12 +328,13 @@ def slot_parity(kind, dev):
     return out
 
 
-def slot_run(kind, dev, mode, frames=30, steps=3, warmup=1, parity=True):
+def slot_run(kind, dev, mode, frames=30, steps=3, warmup=1, parity=True, kernel_table=True, dump=None):
     """BASELINE config 3 (DCT: LaplacianVCAR-style DCNv2 restorer) or 4 (Blur: SwinTormer-style deblur, one round) as
     BASELINE states them: a `frames`-frame 1080p clip, HOST TO HOST (pinned host frames + maps -> upload -> restore ->
     block-map recompose -> download; restore.restore_clip_slot_host), `steps` timed steps after `warmup`.  The kernel
-    table comes from one further, HBM-resident, profiled pass over the clip (HIP events on the launch stream): conv
-    kernels against the MFMA peak, window attention and the DCNv2 gather against the HBM peak (algorithmic bytes)."""
+    table (`kernel_table`) comes from one further, HBM-resident, profiled pass over the clip (HIP events on the launch stream): conv
+    kernels against the MFMA peak, window attention and the DCNv2 gather against the HBM peak (algorithmic bytes).
+    `dump`: the --dump-outputs directory for the last timed step's frames."""
     import numpy as np
     import torch
     from elvis_amd import ops, restore, synth
@@ -322,11 +348,15 @@ def slot_run(kind, dev, mode, frames=30, steps=3, warmup=1, parity=True):
     net = restore._get_restorer(kind, dev, mode == "f32")
     step = lambda: restore.restore_clip_slot_host(kind, net, frames_h, maps_h, B, out_h, batch_size=2, upload_chunk=6)
     sec = _timed_steps(step, warmup, steps)
-    conv_prof, other_prof = [], []
-    ops.CONV_PROFILER, ops.KERNEL_PROFILER = conv_prof, other_prof
-    el = _timed_steps(step, 0, 1)
-    ops.CONV_PROFILER = ops.KERNEL_PROFILER = None
-    table = _kernel_table(conv_prof, other_prof, el, mode)
+    if dump:
+        dump_outputs(dump, out_h)
+    table = []
+    if kernel_table:
+        conv_prof, other_prof = [], []
+        ops.CONV_PROFILER, ops.KERNEL_PROFILER = conv_prof, other_prof
+        el = _timed_steps(step, 0, 1)
+        ops.CONV_PROFILER = ops.KERNEL_PROFILER = None
+        table = _kernel_table(conv_prof, other_prof, el, mode)
     res = {"workload": f"{frames}-frame 1920x1080 clip, ELVIS v2 {'DCT (DCNv2 restorer)' if kind == 'dct' else 'Blur (Swin deblur, 1 round)'}, "
                        f"block {B}, host to host (pinned frames+maps -> H2D, restore, recompose, D2H)",
            "frames_per_s": frames / sec, "steps": steps, "warmup": warmup, "ms_per_step": sec * 1e3, "dtype": mode,
@@ -460,11 +490,13 @@ def main():
     if args.slot != "downsample":
         if rank == 0:
             s = slot_run(args.slot, dev, args.mode, frames=F, steps=max(1, args.steps), warmup=max(1, args.warmup),
-                         parity=not args.no_cpu_baseline)
-            print(json.dumps({"metric": f"restored 1080p frames/sec, ELVIS v2 {args.slot} path", "value": s["frames_per_s"],
-                              "unit": "frames/s", "n_gpus": 1, "steps": s["steps"], "warmup": s["warmup"], "ms_per_step": s["ms_per_step"],
-                              "higher_is_better": True, "dtype": args.mode, "data": "synthetic", "config": {"workload": s["workload"]},
-                              "roofline": s["dominant_kernel"], "other_kernels": s["other_kernels"], "parity": s["parity"]}))
+                         parity=args.full and not args.no_cpu_baseline, kernel_table=args.full, dump=args.dump_outputs)
+            line = {"metric": f"restored 1080p frames/sec, ELVIS v2 {args.slot} path", "value": s["frames_per_s"],
+                    "unit": "frames/s", "n_gpus": 1, "steps": s["steps"], "warmup": s["warmup"], "ms_per_step": s["ms_per_step"],
+                    "higher_is_better": True, "dtype": args.mode, "data": "synthetic", "config": {"workload": s["workload"]}}
+            if args.full:
+                line.update(roofline=s["dominant_kernel"], other_kernels=s["other_kernels"], parity=s["parity"])
+            print(json.dumps(line))
         return
     cfg = SinSRConfig()
     model = restore.get_sinsr_model(dev, cfg=cfg, fp32=(args.mode == "f32"), fuse_gn=args.fuse_gn)
@@ -515,6 +547,34 @@ def main():
         step_host()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered_h if use_dist else out_h)
+    if use_dist:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    total_frames = world * F * args.steps
+    line = {
+        "metric": "restored 1080p frames/sec, SinSR 4x path (ELVIS v2 Downsample)",
+        "value": total_frames / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.mode, "data": "synthetic",
+        "config": {"workload": f"{F}-frame {W}x{H} synthetic clip per GPU, ELVIS v2 Downsample (SinSR 4x), "
+                               f"block {B}, levels 0-3, weights seed 0 (random init), quantize=True",
+                   "timed_region": "host to host: pinned host frames+maps -> H2D, sampler noise (host cores), network, "
+                                   "recompose" + (", one RCCL all-gather, rank 0 D2H of the whole sequence" if world > 1 else ", D2H")
+                                   + " -> pinned host frames",
+                   "frames_per_gpu": F,
+                   "parallelism": (f"frame-sharded x{world}, 1 all-gather ({'RCCL' if args.backend == 'nccl' else 'gloo REHEARSAL on ' + str(ndev) + ' GPU(s) - not a scaling measurement'})"
+                                   if world > 1 else "single GPU"),
+                   "gn_fused_into_conv": bool(args.fuse_gn), "frames_per_invocation": args.batch},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if use_dist:
+            dist.destroy_process_group()
+        return
 
     # ---- secondary: HBM-resident (round-1 definition), with per-launch HIP events for the roofline
     frames_d, levels_d = frames_h.to(dev), levels_h.to(dev)
@@ -545,9 +605,9 @@ def main():
     if use_dist and rank == 0:   # the gathered sequence on the host: rank 0's own shard must sit at its global offset, bit for bit
         gather_ok = bool(torch.equal(gathered_h[first:first + F], out_h))
     if use_dist:
-        t = torch.tensor([elapsed, elapsed2], dtype=torch.float64, device=dev)
+        t = torch.tensor([elapsed2], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, elapsed2 = float(t[0].item()), float(t[1].item())
+        elapsed2 = float(t.item())
 
     # ---- roofline of the dominant kernel from the live HIP events
     roof = None
@@ -594,21 +654,7 @@ def main():
             staged["parity"] = staged_parity(dev)
         if not args.no_slots and world == 1 and not args.no_extras:
             slots = {k: slot_run(k, dev, args.mode, frames=F) for k in ("dct", "blur")}
-        total_frames = world * F * args.steps
-        line = {
-            "metric": "restored 1080p frames/sec, SinSR 4x path (ELVIS v2 Downsample)",
-            "value": total_frames / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.mode, "data": "synthetic",
-            "config": {"workload": f"{F}-frame {W}x{H} synthetic clip per GPU, ELVIS v2 Downsample (SinSR 4x), "
-                                   f"block {B}, levels 0-3, weights seed 0 (random init), quantize=True",
-                       "timed_region": "host to host: pinned host frames+maps -> H2D, sampler noise (host cores), network, "
-                                       "recompose" + (", one RCCL all-gather, rank 0 D2H of the whole sequence" if world > 1 else ", D2H")
-                                       + " -> pinned host frames",
-                       "frames_per_gpu": F,
-                       "parallelism": (f"frame-sharded x{world}, 1 all-gather ({'RCCL' if args.backend == 'nccl' else 'gloo REHEARSAL on ' + str(ndev) + ' GPU(s) - not a scaling measurement'})"
-                                       if world > 1 else "single GPU"),
-                       "gn_fused_into_conv": bool(args.fuse_gn), "frames_per_invocation": args.batch},
+        line.update({
             "hbm_resident": {"value": world * F * steps2 / elapsed2, "unit": "frames/s", "steps": steps2,
                              "ms_per_step": elapsed2 / steps2 * 1e3, "same_output_as_host_path": same,
                              "note": "inputs, noise and outputs resident in HBM (round-1 definition); never `value`"},
@@ -617,7 +663,7 @@ def main():
             "dist": ({"backend": ("RCCL (torch 'nccl')" if args.backend == "nccl" else "gloo"), "world": world, "forced_at_world_1": bool(args.force_dist and world == 1),
                       "collectives_per_step": "one all_gather_into_tensor of the restored uint8 clip",
                       "gathered_sequence_holds_rank0_shard_bit_for_bit": gather_ok} if use_dist else None),
-        }
+        })
         print(json.dumps(line))
     if use_dist:
         dist.destroy_process_group()

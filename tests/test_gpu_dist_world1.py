@@ -17,7 +17,7 @@ def test_bench_force_dist_nccl_world_one(gpu_device):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--gpus", "1", "--steps", "1", "--warmup", "1",
            "--frames", "3", "--height", "256", "--width", "384", "--batch", "3", "--no-extras", "--no-cpu-baseline",
-           "--no-kernel-timing"]
+           "--no-kernel-timing", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -20,7 +20,7 @@ v=[float(r["Counter_Value"]) for f in glob.glob(os.path.join(sys.argv[1],"**","*
 print("co_group",sys.argv[2],"dec512 res FETCH (x2) GB per launch:", [round(2*1024*x/1e9,2) for x in v])
 P
 done
-for r in 1 2; do for g in 0 2; do ELVIS_CO_GROUP=$g python bench.py --steps 3 --warmup 1 --no-extras --no-slots --no-cpu-baseline > $O/bench_g${g}_$r.json 2> $O/bench_g${g}_$r.err; done; done
+for r in 1 2; do for g in 0 2; do ELVIS_CO_GROUP=$g python bench.py --steps 3 --warmup 1 --full --no-extras --no-slots --no-cpu-baseline > $O/bench_g${g}_$r.json 2> $O/bench_g${g}_$r.err; done; done
 python - <<P
 import json,glob
 for f in sorted(glob.glob("$O/bench_*.json")):

@@ -13,8 +13,8 @@ for r in 1 2; do
   ELVIS_AMD_LIB=$V python tools/conv_bench.py --n 15 --prologue --stats --only dec > $O/var_nores_$r.txt 2>&1
 done
 for r in 1 2; do
-  python bench.py --steps 3 --warmup 1 --no-extras --no-slots --no-cpu-baseline > $O/bench_base_$r.json 2> $O/bench_base_$r.err
-  ELVIS_AMD_LIB=$V python bench.py --steps 3 --warmup 1 --no-extras --no-slots --no-cpu-baseline > $O/bench_var_$r.json 2> $O/bench_var_$r.err
+  python bench.py --steps 3 --warmup 1 --full --no-extras --no-slots --no-cpu-baseline > $O/bench_base_$r.json 2> $O/bench_base_$r.err
+  ELVIS_AMD_LIB=$V python bench.py --steps 3 --warmup 1 --full --no-extras --no-slots --no-cpu-baseline > $O/bench_var_$r.json 2> $O/bench_var_$r.err
 done
 grep -h "dec128\|dec256_\|dec512" $O/base_res_*.txt $O/var_res_*.txt $O/base_nores_*.txt $O/var_nores_*.txt
 python - <<P

@@ -4,7 +4,7 @@ python -m pytest tests/test_gpu_kernels.py -x -q -k "weight_stationary" 2>&1 | t
 ELVIS_WS_STAG=1 python -m pytest tests/test_gpu_kernels.py -x -q -k "weight_stationary" 2>&1 | tail -1
 python -m pytest tests/test_gpu_restorers.py tests/test_gpu_surfaces.py -x -q 2>&1 | tail -1
 run() {
-  python bench.py --slot dct --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --slot dct --steps 3 --warmup 1 --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys,os; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', round(d['value'],1));
 ks=[d['roofline']]+d.get('other_kernels',[])
 [print('    ',k['kernel'], round(k['frac'],3), 'ms', round(k['avg_launch_ms'],3), 'share', round(k['time_share'],3)) for k in ks]"

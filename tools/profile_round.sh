@@ -8,7 +8,7 @@ TAG=${1:-r03}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras"
+BENCH="python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras"
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE"
 echo "== kernel stats (default bench)"; rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -o p -- $BENCH > $OUT/bench_under_stats.json 2> $OUT/stats.log
 echo "== FETCH_SIZE";  rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $OUT/fetch -o p -- $BENCH > /dev/null 2> $OUT/fetch.log
@@ -20,7 +20,7 @@ for m in x3 dec_f16; do
   rocprofv3 --kernel-trace --pmc $SQ -f csv -d $OUT/mode_${m}_sq -o p -- python3 tools/mode_profile.py $m > /dev/null 2> $OUT/mode_${m}_sq.log
 done
 echo "== slots"
-rocprofv3 --kernel-trace --stats -f csv -d $OUT/dct -o p -- python3 bench.py --slot dct --frames 12 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/slot_dct.json 2> $OUT/dct.log
-rocprofv3 --kernel-trace --stats -f csv -d $OUT/blur -o p -- python3 bench.py --slot blur --frames 12 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/slot_blur.json 2> $OUT/blur.log
+rocprofv3 --kernel-trace --stats -f csv -d $OUT/dct -o p -- python3 bench.py --slot dct --frames 12 --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/slot_dct.json 2> $OUT/dct.log
+rocprofv3 --kernel-trace --stats -f csv -d $OUT/blur -o p -- python3 bench.py --slot blur --frames 12 --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/slot_blur.json 2> $OUT/blur.log
 find $OUT -name "*.csv" | head -60
 for f in stats fetch write sq dct blur; do tail -2 $OUT/$f.log; done
