@@ -91,16 +91,27 @@ extern "C" int elvis_conv_x3_eligible(const elvis_conv_desc* d) {
     return x3_eligible(d) ? 1 : 0;
 }
 
-extern "C" int elvis_conv_kernel_name(const elvis_conv_desc* d, char* buf, size_t n) {
+// The one rule that picks a conv's kernel family: elvis_conv2d dispatches by it and the name query reports it, so the two
+// cannot drift.  A call with a residual or a statistics buffer never runs on the weight-stationary kernel (it fuses
+// neither): such a call of a ws-eligible shape lands on the halo kernel.
+enum class ConvPath { WS, HALO, IGEMM };
+static ConvPath conv_path(const elvis_conv_desc* d, bool has_residual, bool has_stats) {
+    if (no_halo()) return ConvPath::IGEMM;
+    if (ws_shape_ok(d) && !has_residual && !has_stats) return ConvPath::WS;   // narrow layer, large image: persistent weight-stationary kernel
+    return halo_eligible(d) ? ConvPath::HALO : ConvPath::IGEMM;
+}
+
+extern "C" int elvis_conv_kernel_name_for_call(const elvis_conv_desc* d, int has_residual, int has_stats, char* buf, size_t n) {
     int rc = validate(d);
     if (rc) return rc;
     ELVIS_REQUIRE(buf && n > 0, "elvis_conv_kernel_name: null buffer");
     const char* t = d->dtype == ELVIS_F16 ? "half" : "float";
     TileCfg c = choose_tile(d->cout);
-    if (ws_shape_ok(d) && !no_halo()) {   // (a call with a residual or a statistics buffer falls back to the halo kernel below)
+    const ConvPath path = conv_path(d, has_residual != 0, has_stats != 0);
+    if (path == ConvPath::WS) {
         const int nkc = (d->cin + 31) / 32 + (d->cin2 > 0 ? (d->cin2 + 31) / 32 : 0);
         snprintf(buf, n, "conv3x3_ws_kernel<%d,%d,%s>", nkc, c.tco, ws_stagger(nkc, c.tco) ? "true" : "false");
-    } else if (halo_eligible(d) && !no_halo()) {
+    } else if (path == ConvPath::HALO) {
         const bool pro = d->ksize == 3 && d->prologue;
         if (x3_planar_run(d))
             snprintf(buf, n, "conv3x3_x3p_kernel<%d,%d,%d,%s,%s>", c.tco, halo_ty(d), d->ksize, pro ? "true" : "false", d->act ? "true" : "false");
@@ -115,6 +126,10 @@ extern "C" int elvis_conv_kernel_name(const elvis_conv_desc* d, char* buf, size_
         snprintf(buf, n, "conv_igemm_kernel<%s,%d,%d,%d,%d>", t, cfg[c.id][0], cfg[c.id][1], cfg[c.id][2], cfg[c.id][3]);
     }
     return ELVIS_OK;
+}
+
+extern "C" int elvis_conv_kernel_name(const elvis_conv_desc* d, char* buf, size_t n) {
+    return elvis_conv_kernel_name_for_call(d, 0, 0, buf, n);   // a call without residual and statistics
 }
 
 extern "C" int elvis_conv2d(const elvis_conv_desc* d, const void* x, const void* x2, const void* w_packed,
@@ -170,14 +185,15 @@ extern "C" int elvis_conv2d(const elvis_conv_desc* d, const void* x, const void*
     a.two = (halo_two(d) || halo_g1(d)) ? 1 : 0;
     a.tall = (halo_two(d) && halo_tall(d)) ? 1 : 0;
     a.tiles_y = ((subpix ? d->h : d->ho) + tyv - 1) / tyv;
-    if (ws_shape_ok(d) && !residual && !stats && !no_halo()) {   // narrow layer, large image: persistent weight-stationary kernel
+    const ConvPath path = conv_path(d, residual != nullptr, stats != nullptr);
+    if (path == ConvPath::WS) {
         ELVIS_REQUIRE((long long)d->n * d->h * d->w < 0x7fffffffLL, "conv: input too large for 32-bit pixel indices");
         ConvArgs b = a;
         b.tiles_x = (d->wo + 31) / 32;
         b.tiles_y = (d->ho + 7) / 8;
         return dispatch_ws(b, t.tco, (hipStream_t)stream);
     }
-    if (halo_eligible(d) && !no_halo()) {
+    if (path == ConvPath::HALO) {
         ELVIS_REQUIRE((long long)d->n * d->h * d->w < 0x7fffffffLL, "conv: input too large for 32-bit pixel indices");
         hipStream_t st = (hipStream_t)stream;
         if (d->dtype == ELVIS_F16) {

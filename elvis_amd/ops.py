@@ -286,7 +286,7 @@ class PackedConv:
         if prof is not None:
             e1.record()
             flops = 2.0 * self.ksize * self.ksize * (self.cin + self.cin2) * self.cout * x.n * ho * wo
-            name = conv_kernel_name(d)
+            name = conv_kernel_name(d, residual=residual is not None, stats=stats is not None)
             if name.startswith("conv3x3_ws_kernel") and residual is None and KERNEL_PROFILER is not None:
                 # the weight-stationary kernel serves narrow layers, which are HBM-bound (csrc/conv_ws.inc): priced against
                 # the bytes it has to move - every input channel read once, every output channel written once
@@ -326,11 +326,12 @@ class _Timed:
             KERNEL_PROFILER.append(self.rec + (self.e0, self.e1))
 
 
-def conv_kernel_name(d) -> str:
-    """Name of the kernel instantiation `elvis_conv2d` dispatches descriptor `d` to - the template
-    name rocprofv3's kernel trace shows (queried from the library: conv.hip choose_tile / halo_two)."""
+def conv_kernel_name(d, residual: bool = False, stats: bool = False) -> str:
+    """Name of the kernel instantiation `elvis_conv2d` dispatches descriptor `d` to, for a call with (or without) a
+    residual and a statistics buffer - the template name rocprofv3's kernel trace shows (queried from the library:
+    conv.hip conv_path, the rule elvis_conv2d dispatches by)."""
     buf = C.create_string_buffer(128)
-    check(lib().elvis_conv_kernel_name(C.byref(d), buf, len(buf)), None)
+    check(lib().elvis_conv_kernel_name_for_call(C.byref(d), int(bool(residual)), int(bool(stats)), buf, len(buf)), None)
     return buf.value.decode()
 
 
@@ -375,8 +376,8 @@ class PackedUpConv:
             d.cout, d.cout_pitch = conv.cout_k, out.pitch
             packed = conv.weights_for(d)
             tiles = lib().elvis_conv_stats_tiles(C.byref(d))
-            if want_stats and stats is None:
-                stats = torch.empty((4 * tiles, self.cout, 2), dtype=torch.float32, device=x.t.device)
+            if want_stats and stats is None:   # rows of cout_k channels: what the kernel writes (sliced to cout below)
+                stats = torch.empty((4 * tiles, conv.cout_k, 2), dtype=torch.float32, device=x.t.device)
             sp = stats[k * tiles:(k + 1) * tiles] if stats is not None else None
             prof = CONV_PROFILER
             if prof is not None:
@@ -386,14 +387,16 @@ class PackedUpConv:
                                      ptr(sp), _s(x.t)), x.t.device)
             if prof is not None:
                 e1.record()
-                prof.append((conv_kernel_name(d),
+                prof.append((conv_kernel_name(d, stats=sp is not None),
                              2.0 * 4 * self.cin * self.cout * n * h * w, e0, e1))
                 if CONV_SHAPES is not None:
                     CONV_SHAPES.append((n, h, w, self.cin, self.cout, 2, 1, False, False))
         if stats is not None:
             # per image the reduce expects that image's tiles contiguous: [parity][n*tiles] -> [n][4*tiles/n]
-            t_img = tiles // n
-            stats = stats.view(4, n, t_img, self.cout, 2).permute(1, 0, 2, 3, 4).reshape(4 * tiles, self.cout, 2).contiguous() if n > 1 else stats
+            t_img, ck = tiles // n, stats.shape[1]
+            stats = stats.view(4, n, t_img, ck, 2).permute(1, 0, 2, 3, 4).reshape(4 * tiles, ck, 2).contiguous() if n > 1 else stats
+            if ck != self.cout:   # padded count: the consumers read [tiles, cout, 2] rows
+                stats = stats[:, :self.cout].contiguous()
         out.stats = stats
         return out
 
@@ -467,7 +470,7 @@ class PackedDownConv:
                                  ptr(stats), _s(x.t)), x.t.device)
         if prof is not None:
             e1.record()
-            prof.append((conv_kernel_name(d), 2.0 * 9 * self.cin * self.cout * x.n * out.h * out.w, e0, e1))   # algorithmic FLOPs of the 3x3/s2 conv
+            prof.append((conv_kernel_name(d, stats=stats is not None), 2.0 * 9 * self.cin * self.cout * x.n * out.h * out.w, e0, e1))   # algorithmic FLOPs of the 3x3/s2 conv
             if CONV_SHAPES is not None:
                 CONV_SHAPES.append((x.n, x.h, x.w, self.cin, self.cout, 3, 2, False, False))
         out.stats = stats

@@ -185,6 +185,11 @@ int elvis_conv_stats_tiles(const elvis_conv_desc* d);
  * into buf (NUL-terminated, truncated to n).  For per-kernel profiling (bench.py roofline). */
 int elvis_conv_kernel_name(const elvis_conv_desc* d, char* buf, size_t n);
 
+/* The same for a call that passes a residual (has_residual != 0) and / or a statistics buffer (has_stats != 0): such
+ * a call never runs on the weight-stationary kernel, whatever its shape.  elvis_conv_kernel_name(d, ...) is
+ * elvis_conv_kernel_name_for_call(d, 0, 0, ...); both come from the selection rule elvis_conv2d dispatches by. */
+int elvis_conv_kernel_name_for_call(const elvis_conv_desc* d, int has_residual, int has_stats, char* buf, size_t n);
+
 /* Test / experiment switch: "no_halo" = 1 routes every conv to the generic implicit-GEMM kernel (what the environment
  * variable ELVIS_NO_HALO does for a whole process), 0 forces the halo kernels, -1 returns to the environment's choice. */
 int elvis_conv_debug_set(const char* key, int value);
