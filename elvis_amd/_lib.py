@@ -22,7 +22,7 @@ ROUND_CV2, ROUND_HALF_UP = 0, 1
 _lock = threading.Lock()
 _lib: Optional[C.CDLL] = None
 
-vp, i32, f32, i64 = C.c_void_p, C.c_int, C.c_float, C.c_longlong
+vp, i32, f32, i64, f64 = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_double
 
 
 class ConvDesc(C.Structure):
@@ -74,6 +74,9 @@ SIGNATURES = {
     "elvis_degrade_downsample_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_degrade_gaussian_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp],
     "elvis_degrade_dct_u8": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_classical_lanczos_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "elvis_classical_unsharp_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp],
+    "elvis_temporal_blend_u8": [vp, vp, i32, i64, f64, f64, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],

@@ -303,6 +303,37 @@ int elvis_degrade_gaussian_u8(const uint8_t* src, const int32_t* rounds, uint8_t
 int elvis_degrade_dct_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, const float* basis64, const float* gain,
                          int n_levels, int n, int h, int w, int c, int by, int bx, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ classical restorers
+ * The OpenCV baselines of ELVIS and Presley, per block of a uint8 NHWC frame; map[n, by, bx] int32 with
+ * by = H / block_size, bx = W / block_size (floor: pixels past the last whole block are not written).
+ * block_size is a power of two in [2, 32], 1 <= C <= 4.  OpenCV's 8-bit fixed-point rules are restated
+ * (parity with cv2 unpinned); the tap tables are device pointers built by elvis_amd/classical.py. */
+
+#define ELVIS_CLASSICAL_MAX_LEVEL 16
+
+/* restore_downsample_opencv_lanczos (elvis.py:2773-2820): a block of level L > 0 is INTER_AREA-downscaled to
+ * s = max(1, block_size >> L) and INTER_LANCZOS4-resized back; level 0 is copied.  Levels are clamped to
+ * [0, ELVIS_CLASSICAL_MAX_LEVEL] (the Python layer rejects larger ones).  taps = int16[5][32][8]: the 11-bit
+ * Lanczos taps of destination index d for the factor 2^(i+1). */
+int elvis_classical_lanczos_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, int n, int h, int w, int c,
+                               int block_size, int by, int bx, const int16_t* taps, elvis_stream_t stream);
+
+/* restore_blur_opencv_unsharp_mask (elvis.py:2822-2866) and restore_with_opencv_lanczos / _unsharp
+ * (utils.py:1253-1392): a block of level L > 0 gets GaussianBlur(sigma L, ksize 6L+1, BORDER_REFLECT_101) and
+ * addWeighted(tile, 1 + L/2, blurred, -L/2, 0) on its tile - the block grown by `halo` (0..32) pixels and
+ * clipped at the frame; only the block is written.  taps = int16 8-bit Gaussian taps of level L at
+ * taps[tap_offsets[L] ...], 6L+1 of them, for L in [1, max_level]; levels are clamped to [0, max_level]
+ * (max_level <= ELVIS_CLASSICAL_MAX_LEVEL; the Python layer rejects larger ones). */
+int elvis_classical_unsharp_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, int n, int h, int w, int c,
+                               int block_size, int by, int bx, int halo, const int16_t* taps, const int32_t* tap_offsets,
+                               int max_level, elvis_stream_t stream);
+
+/* temporal_blend of utils.py:1308-1312 over a clip of `nframes` frames of `pixels` u8 elements each:
+ * out[0] = cur[0]; out[f] = trunc(tb * out[f-1] + one_minus_tb * cur[f]) in float64, 0 <= tb, one_minus_tb <= 1.
+ * In-place (out == cur) allowed. */
+int elvis_temporal_blend_u8(const uint8_t* cur, uint8_t* out, int nframes, long long pixels, double tb,
+                            double one_minus_tb, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
