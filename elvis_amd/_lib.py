@@ -35,6 +35,7 @@ class ConvDesc(C.Structure):
 SIGNATURES = {
     "elvis_abi_version": [],
     "elvis_last_error": [],
+    "elvis_last_launch": [],
     "elvis_recompose_u8": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_area_downscale_u8": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_blend_u8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
@@ -107,6 +108,7 @@ def lib() -> C.CDLL:
             fn.argtypes = argtypes
             fn.restype = C.c_int
         handle.elvis_last_error.restype = C.c_char_p
+        handle.elvis_last_launch.restype = C.c_char_p
         handle.elvis_conv_packed_weight_bytes.restype = C.c_size_t
         handle.elvis_groupnorm_workspace_floats.restype = C.c_size_t
         handle.elvis_swin_packed_bytes.restype = C.c_size_t

@@ -432,28 +432,37 @@ extern "C" int elvis_window_attention(const void* qkv, void* out, int dtype, int
     ELVIS_REQUIRE(ws == WS && head_dim == HD, "elvis_window_attention: only window 8 / head_dim 32 are built (got %d/%d)", ws, head_dim);
     ELVIS_REQUIRE(n > 0 && h > 0 && w > 0 && heads > 0 && h % ws == 0 && w % ws == 0, "elvis_window_attention: H,W (%d,%d) must be multiples of the window %d", h, w, ws);
     ELVIS_REQUIRE(shift >= 0 && shift < ws, "elvis_window_attention: bad shift %d", shift);
-    ELVIS_REQUIRE(qkv_pitch >= 3 * heads * head_dim && out_pitch >= heads * head_dim, "elvis_window_attention: bad pitch");
+    ELVIS_REQUIRE(qkv_pitch >= 3 * heads * head_dim && out_pitch >= heads * head_dim && qkv_pitch % 8 == 0 && out_pitch % 8 == 0,
+                  "elvis_window_attention: bad pitch (qkv %d, out %d: at least 3E / E and multiples of 8)", qkv_pitch, out_pitch);
     long long blocks = (long long)n * (h / ws) * (w / ws) * heads;
     ELVIS_REQUIRE(blocks < 0x7fffffffLL, "elvis_window_attention: grid too large");
     static const bool attn_valu = getenv("ELVIS_ATTN_VALU") != nullptr;   // A/B switch, read once
+    // the f16 kernels move a token's head slices as 16-byte vectors
+    ELVIS_REQUIRE(dtype != ELVIS_F16 || ((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0),
+                  "elvis_window_attention: f16 tensors must be 16-byte aligned");
+    const char* name = nullptr;
     if (dtype == ELVIS_F16 && !attn_valu) {
         // MFMA path: one workgroup per window, waves loop over heads
         long long wblocks = (long long)n * (h / ws) * (w / ws);
         static const bool lds_form = getenv("ELVIS_ATTN_LDS") != nullptr;   // A/B switch: round 2's P / O through LDS
+        name = lds_form ? "window_attention_mfma_kernel" : "window_attention_tr_kernel";
         if (lds_form)
             hipLaunchKernelGGL(window_attention_mfma_kernel, dim3((unsigned)wblocks), dim3(64 * ATT_NW), 0, (hipStream_t)stream,
                                (const half_t*)qkv, (half_t*)out, h, w, heads, shift, qkv_pitch, out_pitch, bias_table, scale);
         else
             hipLaunchKernelGGL(window_attention_tr_kernel, dim3((unsigned)wblocks), dim3(64 * ATT_NW), 0, (hipStream_t)stream,
                                (const half_t*)qkv, (half_t*)out, h, w, heads, shift, qkv_pitch, out_pitch, bias_table, scale);
-    } else if (dtype == ELVIS_F16)
+    } else if (dtype == ELVIS_F16) {
+        name = "window_attention_kernel<half>";
         hipLaunchKernelGGL(window_attention_kernel<half_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                            (const half_t*)qkv, (half_t*)out, h, w, heads, shift, qkv_pitch, out_pitch, bias_table, scale);
-    else if (dtype == ELVIS_F32)
+    } else if (dtype == ELVIS_F32) {
+        name = "window_attention_kernel<float>";
         hipLaunchKernelGGL(window_attention_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                            (const float*)qkv, (float*)out, h, w, heads, shift, qkv_pitch, out_pitch, bias_table, scale);
-    else
+    } else
         ELVIS_REQUIRE(false, "elvis_window_attention: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_window_attention");
+    elvis_note_launch(name);
     return ELVIS_OK;
 }

@@ -11,6 +11,8 @@
 #define ELVIS_WAVE 64
 
 void elvis_set_error(const char* fmt, ...);
+// records the instantiation a launch reached (a string literal or other static storage), read back by elvis_last_launch
+void elvis_note_launch(const char* name);
 
 #define ELVIS_REQUIRE(cond, ...)                      \
     do {                                              \

@@ -387,6 +387,7 @@ extern "C" int elvis_dcnv2(const void* x, const void* offset_mask, const void* w
                                (const half_t*)x, (const half_t*)offset_mask, (const half_t*)weight, bias, (half_t*)out, n, h, w,
                                x_pitch, om_pitch, mask_sigmoid, cout, out_pitch, act, tiles_x, tiles_y);
         ELVIS_CHECK_LAUNCH("elvis_dcnv2(tile)");
+        elvis_note_launch(cin == 7 ? "dcnv2_tile_kernel<7>" : "dcnv2_tile_kernel<8>");
         return ELVIS_OK;
     }
     if (dtype == ELVIS_F16)
@@ -400,6 +401,7 @@ extern "C" int elvis_dcnv2(const void* x, const void* offset_mask, const void* w
     else
         ELVIS_REQUIRE(false, "elvis_dcnv2: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_dcnv2");
+    elvis_note_launch(dtype == ELVIS_F16 ? "dcnv2_kernel<half>" : "dcnv2_kernel<float>");
     return ELVIS_OK;
 }
 

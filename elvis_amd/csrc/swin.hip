@@ -433,6 +433,12 @@ template <int C, int PXT, int MODE, bool STAG> int launch_swin(const SwinArgs& a
     ELVIS_REQUIRE(blocks < 0x7fffffffLL, "elvis_swin: grid too large");
     hipLaunchKernelGGL((swin_fused_kernel<C, PXT, MODE, STAG>), dim3((unsigned)blocks), dim3(512), lds, stream, a);
     ELVIS_CHECK_LAUNCH("elvis_swin");
+    static const char* const name = [] {   // formatted once per instantiation, static storage (elvis_last_launch)
+        static char b[48];
+        snprintf(b, sizeof(b), "swin_fused_kernel<%d,%d,%d,%s>", C, PXT, MODE, STAG ? "true" : "false");
+        return (const char*)b;
+    }();
+    elvis_note_launch(name);
     return ELVIS_OK;
 }
 

@@ -251,9 +251,15 @@ int elvis_swin_proj_mlp(const void* attn, const void* y, void* out, const void* 
                         const float* b2, const float* gamma, const float* beta, long long tokens, int c, int hidden,
                         int attn_pitch, int y_pitch, int out_pitch, float eps, elvis_stream_t stream);
 
+/* Normalised instantiation name (e.g. "swin_fused_kernel<192,2,1,true>", "dcnv2_tile_kernel<7>") of the last kernel that
+ * elvis_window_attention, elvis_swin_* or elvis_dcnv2 launched on the calling thread; "" before the first.  Static storage:
+ * no allocation, no device synchronisation. */
+const char* elvis_last_launch(void);
+
 /* Swin (shifted-)window attention on a token image qkv[n,h,w,3*E] (q|k|v, head-major inside
  * each), window ws, `shift` cyclic shift (0 or ws/2) with the standard region mask, relative
- * position bias table [(2ws-1)^2, heads] f32.  out[n,h,w,E] in image order (un-shifted). */
+ * position bias table [(2ws-1)^2, heads] f32.  out[n,h,w,E] in image order (un-shifted).  Pitches are multiples of 8;
+ * f16 tensors are 16-byte aligned. */
 int elvis_window_attention(const void* qkv, void* out, int dtype, int n, int h, int w, int heads,
                            int head_dim, int ws, int shift, int qkv_pitch, int out_pitch,
                            const float* bias_table, float scale, elvis_stream_t stream);
