@@ -13,13 +13,18 @@ from .recompose import (combine_blocks_into_image, split_image_into_blocks,  # n
 from .tiler import (adaptive_restore, blended_restoration, resource_aware_restore,  # noqa: F401
                     _extract_tile_with_halo, extract_tile_with_halo)
 from .frameio import (clear_directory, decode_strength_maps_from_npz, encode_strength_maps_to_npz,  # noqa: F401
-                      get_frame_paths, load_block_masks, load_frame, load_strength_maps, save_block_masks, save_frame)
+                      get_frame_paths, load_block_masks, load_frame, load_strength_maps, save_block_masks, save_frame, save_mask)
 from .degrade import filter_frame_dct, filter_frame_downsample, filter_frame_gaussian  # noqa: F401
 from .classical import (lanczos_restore_device, restore_blur_opencv_unsharp_mask,  # noqa: F401
                         restore_downsample_opencv_lanczos, restore_with_opencv_lanczos, restore_with_opencv_unsharp,
                         temporal_blend_device, unsharp_restore_device)
 from .metrics import calculate_block_ssim, calculate_mse, calculate_psnr, masked_mse, masked_psnr  # noqa: F401
-from .drivers import restore_blur_adaptive, restore_dct_adaptive, restore_downsampled_with_sinsr  # noqa: F401
+from .shrink import (apply_selective_removal, block_gather_device, shrink_frame_position_map,  # noqa: F401
+                     shrink_frame_removal_indices, shrink_frame_row_only, shrink_passes_device, shrink_topk_device,
+                     shrink_video_frames, stretch_device, stretch_frame, stretch_frame_position_map,
+                     stretch_frame_removal_indices, stretch_frame_row_only, stretch_index_device, stretch_video_frames)
+from .drivers import (restore_blur_adaptive, restore_dct_adaptive, restore_downsampled_with_sinsr,  # noqa: F401
+                      stretch_shrunk_frames)
 from .restore import (get_sinsr_model, get_sinsr_upsample_fn, restore_frames_blur,  # noqa: F401
                       restore_frames_dct, restore_frames_rounds, restore_frames_sinsr,
                       restore_with_sinsr_naive)

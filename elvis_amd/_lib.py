@@ -78,6 +78,11 @@ SIGNATURES = {
     "elvis_classical_lanczos_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "elvis_classical_unsharp_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp],
     "elvis_temporal_blend_u8": [vp, vp, i32, i64, f64, f64, vp],
+    "elvis_block_gather_u8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_shrink_select_topk": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "elvis_shrink_passes_plan": [i32, i32, i32, i32, vp, vp, vp, i32],
+    "elvis_shrink_select_passes": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_stretch_index": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],

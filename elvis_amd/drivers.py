@@ -5,6 +5,7 @@
   restore_blur_adaptive            <- restore_with_instantir_adaptive      (elvis.py:3000-3160)
   restore_dct_adaptive             -  the DCT slot the reference never wrote, given the
                                       Blur driver's shape
+  stretch_shrunk_frames            <- the ELVIS v1 client-side stretch loop   (elvis.py:4534-4580)
 
 Same arguments, file naming and errors as the reference: a directory of PNG frames (BGR on read) and a
 `(frames, blocks_y, blocks_x)` map; the Downsample driver writes `output_dir/<same names>`, the Blur /
@@ -24,7 +25,7 @@ from typing import Callable, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from .frameio import clear_directory, get_frame_paths, load_frame, save_frame
+from .frameio import clear_directory, get_frame_paths, load_block_masks, load_frame, save_frame, save_mask
 from .sharding import ChunkSpec, chunk_for_devices, resolve_device_list
 
 DeviceSpec = Union[int, str, torch.device]
@@ -49,6 +50,22 @@ def _blur_shard(frames, maps, block_size, device, first_frame_index, **kw):
 def _dct_shard(frames, maps, block_size, device, first_frame_index, **kw):
     from .restore import restore_frames_dct
     return restore_frames_dct(frames, maps, block_size, device, **kw)
+
+
+def _stretch_shard(frames, maps, block_size, device, first_frame_index, fullres_masks_dir=None, **kw):
+    """Stretch a run of decoded shrunk frames in one launch pair; the inpainter's full-resolution masks come out of
+    the same gather and are written here under the global frame numbers."""
+    from .recompose import frames_to_device, frames_to_host
+    from .shrink import stretch_device
+    with torch.cuda.device(device):
+        fd = frames_to_device(frames, device)
+        md = torch.from_numpy(np.ascontiguousarray(np.asarray(maps) != 0).view(np.uint8)).to(device)
+        out, full = stretch_device(fd, md, block_size, "flat", fullres_mask=True)
+        if fullres_masks_dir is not None:
+            full_h = full.cpu().numpy()
+            for i in range(len(frames)):
+                save_mask(full_h[i], os.path.join(fullres_masks_dir, f"{first_frame_index + i + 1:05d}.png"))
+        return frames_to_host(out)
 
 
 def _shard_worker(shard_fn: ShardFn, in_dir: str, out_dir: str, names: Sequence[str], start: int, end: int,
@@ -226,3 +243,50 @@ def restore_dct_adaptive(
     kw = {} if _shard_fn is not None else dict(fp32=fp32)
     _restore_in_place(_shard_fn or _dct_shard, input_frames_dir, strength_maps, block_size, devices,
                       max(0, int(temporal_radius)), kw, "strength_maps", _shard_fn is not None)
+
+
+def stretch_shrunk_frames(
+    frames_dir: str,
+    masks_npz: str,
+    block_size: int,
+    out_dir: Optional[str] = None,
+    fullres_masks_dir: Optional[str] = None,
+    block_masks_dir: Optional[str] = None,
+    devices: Optional[Sequence[DeviceSpec]] = None,
+    *,
+    _shard_fn: Optional[ShardFn] = None,
+) -> np.ndarray:
+    """ELVIS v1 client side over a directory (elvis.py:4534-4580): unpack the removal masks of `masks_npz`
+    (`frameio.load_block_masks`), stretch the decoded shrunk frames `00001.png` ... (one per mask) - in place, or
+    into `out_dir` - and write the masks for the inpainter as PNGs under the same `{i+1:05d}.png` names: 0/255 at
+    block resolution into `block_masks_dir`, 0/255 at frame resolution into `fullres_masks_dir` (either may be None).
+    Frames are dealt to the devices by the `chunk_for_devices` rule.  Returns the unpacked masks.
+
+    Every frame must hold exactly as many blocks as its mask keeps (`stretch_frame`'s rule): ValueError otherwise,
+    before anything is written."""
+    masks = load_block_masks(masks_npz)
+    if masks.ndim != 3 or masks.shape[0] == 0:
+        raise ValueError(f"removal masks must be (frames, blocks_y, blocks_x); got {masks.shape}")
+    names = [f"{i + 1:05d}.png" for i in range(masks.shape[0])]
+    missing = [n for n in names if not os.path.isfile(os.path.join(frames_dir, n))]
+    if missing:
+        raise ValueError(f"No frame {missing[0]} in {frames_dir} ({len(missing)} of {len(names)} frames missing)")
+    from PIL import Image
+    for i, n in enumerate(names):
+        with Image.open(os.path.join(frames_dir, n)) as im:
+            w, h = im.size
+        kept = int(masks[i].size - np.count_nonzero(masks[i]))
+        if h % block_size or w % block_size or (h // block_size) * (w // block_size) != kept:
+            raise ValueError(f"{n}: a {h}x{w} frame does not hold the {kept} blocks of {block_size} its mask keeps")
+    for d in (out_dir, fullres_masks_dir, block_masks_dir):
+        if d is not None:
+            os.makedirs(d, exist_ok=True)
+    if block_masks_dir is not None:
+        for i, n in enumerate(names):
+            save_mask((masks[i] * 255).astype(np.uint8), os.path.join(block_masks_dir, n))
+    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
+    gpus = [d for d in devs if d.type == "cuda"]
+    workers = gpus or (devs if _shard_fn is not None else devs[:1])
+    _run_shards(_shard_fn or _stretch_shard, frames_dir, out_dir or frames_dir, names, chunk_for_devices(len(names), workers),
+                masks, block_size, 0, dict(fullres_masks_dir=fullres_masks_dir))
+    return masks

@@ -63,6 +63,20 @@ def save_frame(frame: np.ndarray, path: PathLike) -> None:
         raise IOError(f"Failed to save frame: {path}") from exc
 
 
+def save_mask(mask: np.ndarray, path: PathLike) -> None:
+    """Write a uint8 (H,W) mask as a single-channel image, creating the directory - what `cv2.imwrite` does with a
+    2-D array (elvis.py:4566-4579)."""
+    from PIL import Image
+    mask = np.asarray(mask)
+    if mask.dtype != np.uint8 or mask.ndim != 2:
+        raise IOError(f"Failed to save mask: {path} (expected uint8 HxW, got {mask.dtype} {mask.shape})")
+    os.makedirs(os.path.dirname(os.fspath(path)) or ".", exist_ok=True)
+    try:
+        Image.fromarray(np.ascontiguousarray(mask), "L").save(path)
+    except (OSError, ValueError) as exc:
+        raise IOError(f"Failed to save mask: {path}") from exc
+
+
 def load_frames(directory: PathLike) -> List[np.ndarray]:
     return [load_frame(p) for p in get_frame_paths(directory)]
 

@@ -340,6 +340,64 @@ int elvis_classical_unsharp_u8(const uint8_t* src, const int32_t* levels, uint8_
 int elvis_temporal_blend_u8(const uint8_t* cur, uint8_t* out, int nframes, long long pixels, double tb,
                             double one_minus_tb, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ ELVIS v1 block removal
+ * Shrink (the server removes the least important blocks of a frame) and stretch (the client puts the kept blocks
+ * back and gets the hole mask for the inpainter) on uint8 NHWC clips.  Every shrink and every stretch is one
+ * block gather driven by an int32 index map; the entry points below build the maps on the device.  Scores are
+ * float64 and FINITE (no NaN; the Python layer rejects them); they are only compared, never rounded. */
+
+#define ELVIS_SHRINK_ROWS 0        /* shrink_frame_row_only: row passes only */
+#define ELVIS_SHRINK_ROWS_COLS 1   /* shrink_frame_position_map / _removal_indices: row pass, column pass, ... */
+#define ELVIS_STRETCH_FLAT 0       /* stretch_frame, stretch_video_frames: rank over the whole frame, row-major */
+#define ELVIS_STRETCH_ROWS 1       /* stretch_frame_row_only: rank inside the block row */
+
+/* dst[n, y, x] = src block src_of[n, y, x] (a flat index into the sby x sbx source grid of the same frame), a zero
+ * block where src_of < 0 or beyond the source grid.  src u8 [n, hs, ws, c] with hs >= sby*block_size and
+ * ws >= sbx*block_size (rows and columns past the grid are never read: the crop of utils.py:707); dst u8
+ * [n, dby*block_size, dbx*block_size, c]; src_of int32 [n, dby, dbx].  mask_out (may be NULL): u8
+ * [n, dby*block_size, dbx*block_size], 255 on the pixels of a zero block, 0 elsewhere - the inpainter's mask of
+ * elvis.py:4560-4575 in the same launch.  Any block_size >= 1, c in {1, 3}; a sby x sbx = 0 source gives all holes. */
+int elvis_block_gather_u8(const uint8_t* src, const int32_t* src_of, uint8_t* dst, uint8_t* mask_out, int n, int hs,
+                          int ws, int c, int block_size, int sby, int sbx, int dby, int dbx, elvis_stream_t stream);
+
+/* apply_selective_removal (elvis.py:1387-1427), selection step: per block row, column i is removed iff fewer than k
+ * columns j have s_j > s_i, or s_j == s_i and j < i - the k highest scores.  TIE RULE: among equal scores the lower
+ * column goes first; the reference's np.argsort(-row) is not a stable sort, so its ties are not defined.
+ * scores f64 [n, by, bx]; mask int8 [n, by, bx] (1 = removed); src_of int32 [n, by, bx - k]: the kept columns of
+ * every row in order, as flat indices into the by x bx grid (the map of the shrink).  0 <= k <= bx; src_of may be
+ * NULL when k == bx. */
+int elvis_shrink_select_topk(const double* scores, int8_t* mask, int32_t* src_of, int n, int by, int bx, int k,
+                             elvis_stream_t stream);
+
+/* Host only (no device work): the shrunk grid *sby x *sbx of the pass rule below and the number of removals of each
+ * pass (the first min(max_passes, return value) entries of pass_counts; pass_counts may be NULL with max_passes 0).
+ * Returns the number of passes (>= 0) or ELVIS_E_INVALID.  A function of (by, bx, target, mode) alone. */
+int elvis_shrink_passes_plan(int by, int bx, int target, int mode, int* sby, int* sbx, int* pass_counts, int max_passes);
+
+/* shrink_frame_row_only (utils.py:692-736), shrink_frame_position_map (:763-836) and shrink_frame_removal_indices
+ * (:862-948), selection step.  Until `target` = int(by * bx * shrink_amount) blocks are gone: a row pass removes from
+ * every row (in order) its current argmin - first index on ties, as np.argmin - and shifts the row left; with
+ * ELVIS_SHRINK_ROWS_COLS a column pass follows (argmin of every column, shift up), then a row pass, ...
+ * PARTIAL PASSES: a pass that reaches the target midway stops there.  ELVIS_SHRINK_ROWS still drops the last column
+ * (rows the pass did not reach lose their last block without a mask entry) and never goes below one column;
+ * ELVIS_SHRINK_ROWS_COLS keeps the dimension, so the shrunk grid ends with stale duplicates of the shifted lines.
+ * scores f64 [n, by, bx]; mask u8 [n, by, bx] (1 = removed); src_of int32 [n, sby, sbx]: the position map of the
+ * shrunk grid as flat indices (y * bx + x) into the by x bx grid; removal_idx (may be NULL) int32 [n, target]: the
+ * argmins in removal order (split per pass with elvis_shrink_passes_plan); ws_scores f64 / ws_pos int32
+ * [n, by, bx]: scratch.  sby, sbx must be what elvis_shrink_passes_plan gives. */
+int elvis_shrink_select_passes(const double* scores, uint8_t* mask, int32_t* src_of, int32_t* removal_idx,
+                               double* ws_scores, int32_t* ws_pos, int n, int by, int bx, int target, int mode, int sby,
+                               int sbx, elvis_stream_t stream);
+
+/* The index map of a stretch whose side data is a mask (u8 [n, by, bx], non-zero = removed): src_of int32
+ * [n, by, bx] = the rank of a kept block among the kept blocks - of the frame in row-major order
+ * (ELVIS_STRETCH_FLAT: stretch_frame elvis.py:1436-1455, stretch_video_frames presley.py:787-827), or of its row,
+ * plus row * sbx (ELVIS_STRETCH_ROWS: stretch_frame_row_only utils.py:739-759) - and -1 for a removed block or a
+ * rank outside the sby x sbx shrunk grid (the bounds checks of the Presley and row-only forms).  stretch_frame
+ * itself raises when the kept count differs from sby * sbx: a precondition here, checked by the Python layer. */
+int elvis_stretch_index(const uint8_t* mask, int32_t* src_of, int n, int by, int bx, int sby, int sbx, int mode,
+                        elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
