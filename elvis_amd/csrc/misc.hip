@@ -268,6 +268,7 @@ extern "C" int elvis_u8_to_float(const uint8_t* src, void* dst, int dtype, int n
     else
         ELVIS_REQUIRE(false, "elvis_u8_to_float: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_u8_to_float");
+    elvis_note_launch(dtype == ELVIS_F16 ? "u8_to_float_kernel<half>" : "u8_to_float_kernel<float>");
     return ELVIS_OK;
 }
 
@@ -285,6 +286,7 @@ extern "C" int elvis_float_to_u8(const void* src, int dtype, uint8_t* dst, float
     else
         ELVIS_REQUIRE(false, "elvis_float_to_u8: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_float_to_u8");
+    elvis_note_launch(dtype == ELVIS_F16 ? "float_to_u8_kernel<half>" : "float_to_u8_kernel<float>");
     return ELVIS_OK;
 }
 
@@ -302,6 +304,7 @@ extern "C" int elvis_bicubic_upsample(const void* x, void* y, int dtype, int n, 
     else
         ELVIS_REQUIRE(false, "elvis_bicubic_upsample: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_bicubic_upsample");
+    elvis_note_launch(dtype == ELVIS_F16 ? "bicubic_kernel<half>" : "bicubic_kernel<float>");
     return ELVIS_OK;
 }
 
@@ -320,6 +323,7 @@ extern "C" int elvis_vq_nearest(const void* z, void* zq, int32_t* idx_out, int d
     else
         ELVIS_REQUIRE(false, "elvis_vq_nearest: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_vq_nearest");
+    elvis_note_launch(dtype == ELVIS_F16 ? "vq_nearest_kernel<half>" : "vq_nearest_kernel<float>");
     return ELVIS_OK;
 }
 
@@ -341,6 +345,7 @@ extern "C" int elvis_pad_reflect_axpy(const void* x, void* y, int dtype, int n, 
     else
         ELVIS_REQUIRE(false, "elvis_pad_reflect_axpy: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_pad_reflect_axpy");
+    elvis_note_launch(dtype == ELVIS_F16 ? "pad_reflect_axpy_kernel<half>" : "pad_reflect_axpy_kernel<float>");
     return ELVIS_OK;
 }
 
@@ -358,6 +363,7 @@ extern "C" int elvis_crop_copy(const void* x, void* y, int dtype, int n, int h_i
     else
         ELVIS_REQUIRE(false, "elvis_crop_copy: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_crop_copy");
+    elvis_note_launch(dtype == ELVIS_F16 ? "crop_copy_kernel<half>" : "crop_copy_kernel<float>");
     return ELVIS_OK;
 }
 
@@ -375,5 +381,6 @@ extern "C" int elvis_convert_act(const void* x, int src_dtype, void* y, int dst_
     else
         ELVIS_REQUIRE(false, "elvis_convert_act: unsupported conversion %d -> %d", src_dtype, dst_dtype);
     ELVIS_CHECK_LAUNCH("elvis_convert_act");
+    elvis_note_launch(src_dtype == ELVIS_F16 ? "convert_act_kernel<half,float>" : "convert_act_kernel<float,half>");
     return ELVIS_OK;
 }

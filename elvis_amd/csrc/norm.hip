@@ -160,7 +160,8 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ x
                                                          int pitch_in, int pitch_out, const float* __restrict__ pa,
                                                          const float* __restrict__ pb, int act, long long total_vec) {
     constexpr int VEC = DT<T>::VEC;
-    const int cv = (c + VEC - 1) / VEC;
+    // vectors per pixel: the whole 8-channel groups [0, pitch_for(c)), zeros on [c, pitch_for(c)) (f32: two vectors a group)
+    const int cv = (c + 7) / 8 * (8 / VEC);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total_vec;
          i += (long long)gridDim.x * blockDim.x) {
         long long px = i / cv;
@@ -189,7 +190,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x, T* __restrict__ y, long long tokens,
                                                         int c, int pitch_in, int pitch_out,
                                                         const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, float eps, int lpt) {
+                                                        const float* __restrict__ beta, float eps, int lpt,
+                                                        int zero_tail) {
     constexpr int VEC = DT<T>::VEC;
     const int tpw = 64 / lpt;                       // tokens per wave
     const int lane = threadIdx.x & 63;
@@ -224,6 +226,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
                 o.set(k, (v.get(k) - mean) * rstd * gamma[ch] + beta[ch]);
             }
             *reinterpret_cast<uint4*>(y + tok * pitch_out + l * VEC) = o.raw;
+            // f32 with c % 8 == 4: the second vector of the last 8-channel group, [c, pitch_for(c)), is zeroed
+            if (zero_tail && l == cv - 1) *reinterpret_cast<uint4*>(y + tok * pitch_out + c) = make_uint4(0, 0, 0, 0);
         }
     }
 }
@@ -255,6 +259,7 @@ extern "C" int elvis_groupnorm_sums(const void* x, int dtype, int n, int hw, int
     int cv = (c + vec - 1) / vec;
     ELVIS_REQUIRE(cv <= 256, "elvis_groupnorm_sums: too many channels (%d)", c);
     ELVIS_REQUIRE(sums_coff >= 0 && sums_coff + c <= sums_ctot, "elvis_groupnorm_sums: channel slice [%d,%d) outside %d", sums_coff, sums_coff + c, sums_ctot);
+    ELVIS_REQUIRE((uintptr_t)x % 16 == 0, "elvis_groupnorm_sums: x must be 16-byte aligned");
     int pl = 256 / cv;
     int px_per_block = 0;
     int gx = gn_blocks(dtype, hw, c, &px_per_block);
@@ -269,6 +274,7 @@ extern "C" int elvis_groupnorm_sums(const void* x, int dtype, int n, int hw, int
     else
         ELVIS_REQUIRE(false, "elvis_groupnorm_sums: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_groupnorm_sums");
+    elvis_note_launch(dtype == ELVIS_F16 ? "gn_channel_sums_kernel<half>" : "gn_channel_sums_kernel<float>");
     hipLaunchKernelGGL(gn_partials_reduce_kernel, dim3(c, n), dim3(256), 0, (hipStream_t)stream, workspace, gx, c, sums,
                        sums_ctot, sums_coff);
     ELVIS_CHECK_LAUNCH("elvis_groupnorm_sums(reduce)");
@@ -279,13 +285,15 @@ extern "C" int elvis_gn_partials_to_sums(const float* partials, int tiles_per_im
                                          int sums_ctot, int sums_coff, elvis_stream_t stream) {
     ELVIS_REQUIRE(partials && sums && tiles_per_image > 0 && n > 0 && c > 0, "elvis_gn_partials_to_sums: bad argument");
     ELVIS_REQUIRE(sums_coff >= 0 && sums_coff + c <= sums_ctot, "elvis_gn_partials_to_sums: channel slice outside buffer");
-    if (c % 4 == 0 && ((uintptr_t)partials & 15) == 0)
+    const bool four = c % 4 == 0 && ((uintptr_t)partials & 15) == 0;
+    if (four)
         hipLaunchKernelGGL(gn_partials_reduce4_kernel, dim3(c / 4, n), dim3(256), 0, (hipStream_t)stream, partials,
                            tiles_per_image, c, sums, sums_ctot, sums_coff);
     else
         hipLaunchKernelGGL(gn_partials_reduce_kernel, dim3(c, n), dim3(256), 0, (hipStream_t)stream, partials,
                            tiles_per_image, c, sums, sums_ctot, sums_coff);
     ELVIS_CHECK_LAUNCH("elvis_gn_partials_to_sums");
+    elvis_note_launch(four ? "gn_partials_reduce4_kernel" : "gn_partials_reduce_kernel");
     return ELVIS_OK;
 }
 
@@ -298,6 +306,7 @@ extern "C" int elvis_groupnorm_affine(const double* sums, const float* gamma, co
     hipLaunchKernelGGL(gn_affine_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, sums, gamma,
                        beta, scale, shift, pa, pb, n, hw, c, groups, eps);
     ELVIS_CHECK_LAUNCH("elvis_groupnorm_affine");
+    elvis_note_launch("gn_affine_kernel");
     return ELVIS_OK;
 }
 
@@ -307,8 +316,9 @@ extern "C" int elvis_affine_act(const void* x, void* y, int dtype, int n, int hw
     ELVIS_REQUIRE(n > 0 && hw > 0 && c > 0 && pitch_in >= c && pitch_out >= c && pitch_in % 8 == 0 && pitch_out % 8 == 0,
                   "elvis_affine_act: bad shape");
     ELVIS_REQUIRE(act == 0 || act == 2, "elvis_affine_act: act must be 0 or 2");
+    ELVIS_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0, "elvis_affine_act: x and y must be 16-byte aligned");
     int vec = dtype == ELVIS_F16 ? 8 : 4;
-    long long total_vec = (long long)n * hw * ((c + vec - 1) / vec);
+    long long total_vec = (long long)n * hw * ((c + 7) / 8 * (8 / vec));   // whole 8-channel groups: [c, pitch_for(c)) is zeroed
     int grid = (int)((total_vec + 255) / 256);
     if (grid > 256 * 32) grid = 256 * 32;
     if (dtype == ELVIS_F16)
@@ -320,6 +330,7 @@ extern "C" int elvis_affine_act(const void* x, void* y, int dtype, int n, int hw
     else
         ELVIS_REQUIRE(false, "elvis_affine_act: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_affine_act");
+    elvis_note_launch(dtype == ELVIS_F16 ? "affine_act_kernel<half,false>" : "affine_act_kernel<float,true>");
     return ELVIS_OK;
 }
 
@@ -330,6 +341,7 @@ extern "C" int elvis_layernorm(const void* x, void* y, int dtype, long long toke
     int vec = dtype == ELVIS_F16 ? 8 : 4;
     ELVIS_REQUIRE(tokens > 0 && c > 0 && c % vec == 0 && c / vec <= 64, "elvis_layernorm: c=%d unsupported", c);
     ELVIS_REQUIRE(pitch_in >= c && pitch_out >= c && pitch_in % 8 == 0 && pitch_out % 8 == 0, "elvis_layernorm: bad pitch");
+    ELVIS_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0, "elvis_layernorm: x and y must be 16-byte aligned");
     int lpt = 1;
     while (lpt < c / vec) lpt <<= 1;
     int tpw = 64 / lpt;
@@ -338,12 +350,13 @@ extern "C" int elvis_layernorm(const void* x, void* y, int dtype, long long toke
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (dtype == ELVIS_F16)
         hipLaunchKernelGGL(layernorm_kernel<half_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                           (const half_t*)x, (half_t*)y, tokens, c, pitch_in, pitch_out, gamma, beta, eps, lpt);
+                           (const half_t*)x, (half_t*)y, tokens, c, pitch_in, pitch_out, gamma, beta, eps, lpt, 0);
     else if (dtype == ELVIS_F32)
         hipLaunchKernelGGL(layernorm_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                           (const float*)x, (float*)y, tokens, c, pitch_in, pitch_out, gamma, beta, eps, lpt);
+                           (const float*)x, (float*)y, tokens, c, pitch_in, pitch_out, gamma, beta, eps, lpt, c % 8 != 0);
     else
         ELVIS_REQUIRE(false, "elvis_layernorm: bad dtype");
     ELVIS_CHECK_LAUNCH("elvis_layernorm");
+    elvis_note_launch(dtype == ELVIS_F16 ? "layernorm_kernel<half>" : "layernorm_kernel<float>");
     return ELVIS_OK;
 }

@@ -220,6 +220,16 @@ int elvis_groupnorm_affine(const double* sums, const float* gamma, const float* 
                            const float* shift, float* pa, float* pb, int n, int hw, int c, int groups,
                            float eps, elvis_stream_t stream);
 
+/* Pad channels.  pitch_for(c) = c rounded up to a multiple of 8 is the pitch a tensor of c channels needs; the convs
+ * read whole 8-channel groups, so what an op leaves in [c, pitch_out) is part of its contract:
+ *   elvis_affine_act, elvis_layernorm        zero [c, pitch_for(c)) (f16 and f32), leave [pitch_for(c), pitch_out) alone
+ *   elvis_u8_to_float (c = 3), elvis_bicubic_upsample, elvis_vq_nearest, elvis_crop_copy     zero [c, pitch_out)
+ *   elvis_pad_reflect_axpy                   writes [ch_offset_out, ch_offset_out + c) only
+ *   elvis_convert_act                        converts all `pitch` channels
+ * Pad channels of an INPUT are loaded with the vectors they share and ignored (they may hold anything, NaN included).
+ * elvis_groupnorm_sums, elvis_affine_act and elvis_layernorm move 16-byte vectors: x (and y) must be 16-byte aligned
+ * and the pitches multiples of 8, else ELVIS_E_INVALID before anything is launched. */
+
 /* y = act(x*pa[n,c] + pb[n,c]); act 0 none / 2 SiLU.  In-place allowed. */
 int elvis_affine_act(const void* x, void* y, int dtype, int n, int hw, int c, int pitch_in,
                      int pitch_out, const float* pa, const float* pb, int act, elvis_stream_t stream);
@@ -252,7 +262,9 @@ int elvis_swin_proj_mlp(const void* attn, const void* y, void* out, const void* 
                         int attn_pitch, int y_pitch, int out_pitch, float eps, elvis_stream_t stream);
 
 /* Normalised instantiation name (e.g. "swin_fused_kernel<192,2,1,true>", "dcnv2_tile_kernel<7>") of the last kernel that
- * elvis_window_attention, elvis_swin_* or elvis_dcnv2 launched on the calling thread; "" before the first.  Static storage:
+ * elvis_window_attention, elvis_swin_*, elvis_dcnv2, elvis_block_gather_u8, or an entry point of csrc/norm.hip / csrc/misc.hip
+ * (elvis_groupnorm_sums reports its gn_channel_sums_kernel, elvis_gn_partials_to_sums which of its two reductions it chose)
+ * launched on the calling thread; "" before the first.  Static storage:
  * no allocation, no device synchronisation. */
 const char* elvis_last_launch(void);
 
