@@ -1,10 +1,9 @@
 // Swin (shifted-)window attention on an NHWC token image: 64 tokens x head_dim 32 per (window,
 // head).  QK^T + relative-position bias + shift mask -> softmax -> PV.  f16 tensors run on the
-// matrix cores (window_attention_mfma_kernel below); the exact-parity f32 mode runs in fp32 VALU on
+// matrix cores (window_attention_tr_kernel below); the exact-parity f32 mode runs in fp32 VALU on
 // LDS-resident tiles; the cyclic shift / window partition / reverse are pure index math
 // (tokens never leave image order in HBM).
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -104,171 +103,9 @@ __global__ __launch_bounds__(256) void window_attention_kernel(const T* __restri
 
 
 // ------------------------------------------------------------------------------------------
-// MFMA form (f16 tensors): one wave per (window, head).
-//   S[i][j] = sum_d Q[i][d] K[j][d]      16 x v_mfma_f32_16x16x32_f16, Q/K fragments straight from
-//                                        global memory (a token's 32-d head slice is 64 contiguous bytes)
-//   P = softmax_j(S*scale + bias + mask) in registers: a row lives in 4 registers x 16 lanes,
-//                                        reduced with DPP/shuffle xor 1,2,4,8
-//   O[i][d] = sum_j P[i][j] V[j][d]      16 MFMAs; P goes through a per-wave LDS tile to become an A
-//                                        operand (row = token, k = key contiguous), V through a
-//                                        LDS tile stored transposed ([d][key]): one ds_read_b128 per fragment
-constexpr int P_PITCH = NTOK + 8;   // halfs; 144-byte rows keep ds_read_b128 16-byte aligned
-constexpr int V_PITCH = NTOK + 8;   // halfs; V is kept TRANSPOSED ([d][key], 144-byte rows) so a B fragment is one ds_read_b128
-
-#ifndef ELVIS_ATT_WAVES
-#define ELVIS_ATT_WAVES 2   /* waves per workgroup (= heads in flight per window): 2 -> 30 KB of LDS, five workgroups per CU (-26 % vs 4) */
-#endif
-constexpr int ATT_NW = ELVIS_ATT_WAVES;
-__global__ __launch_bounds__(64 * ATT_NW) void window_attention_mfma_kernel(const half_t* __restrict__ qkv,
-                                                                    half_t* __restrict__ out, int h, int w,
-                                                                    int heads, int shift, int qkv_pitch,
-                                                                    int out_pitch,
-                                                                    const float* __restrict__ bias_table,
-                                                                    float scale) {
-    __shared__ __attribute__((aligned(16))) half_t sP[ATT_NW][NTOK * P_PITCH];
-    __shared__ __attribute__((aligned(16))) half_t sV[ATT_NW][HD * V_PITCH];
-    __shared__ float sBias[ATT_NW][(2 * WS - 1) * (2 * WS - 1)];
-    __shared__ int s_pos[NTOK];
-    __shared__ int s_region[NTOK];
-    const int E = heads * HD;
-    const int nwx = w / WS, nwy = h / WS;
-    int bid = blockIdx.x;
-    const int wx = bid % nwx;
-    bid /= nwx;
-    const int wy = bid % nwy;
-    const int n = bid / nwy;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-    if (tid < NTOK) {
-        int ty = tid / WS, tx = tid % WS;
-        int yr = wy * WS + ty, xr = wx * WS + tx;
-        int y = yr + shift, x = xr + shift;
-        if (y >= h) y -= h;
-        if (x >= w) x -= w;
-        s_pos[tid] = (n * h + y) * w + x;
-        int rh = 0, rw = 0;
-        if (shift) {
-            rh = yr < h - WS ? 0 : (yr < h - shift ? 1 : 2);
-            rw = xr < w - WS ? 0 : (xr < w - shift ? 1 : 2);
-        }
-        s_region[tid] = rh * 3 + rw;
-    }
-    __syncthreads();
-
-    const int lr = lane & 15, lq = lane >> 4;
-    half_t* myP = sP[wave];
-    half_t* myV = sV[wave];
-    float* myB = sBias[wave];
-
-    for (int head = wave; head < heads; head += ATT_NW) {
-        // relative-position bias column of this head -> LDS
-        for (int t = lane; t < (2 * WS - 1) * (2 * WS - 1); t += 64) myB[t] = bias_table[t * heads + head];
-        // V tile (64 keys x 32 dims) -> LDS, one 16-byte chunk per lane-iteration
-        for (int t = lane; t < NTOK * 4; t += 64) {
-            int j = t >> 2, c = t & 3;
-            half8 v8 = *reinterpret_cast<const half8*>(qkv + (long long)s_pos[j] * qkv_pitch + 2 * E + head * HD + c * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) myV[(c * 8 + e) * V_PITCH + j] = v8[e];
-        }
-        // Q (A operand) and K (B operand) fragments straight from global memory
-        half8 fq[4], fk[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            int tok = t * 16 + lr;
-            fq[t] = *reinterpret_cast<const half8*>(qkv + (long long)s_pos[tok] * qkv_pitch + head * HD + lq * 8);
-            fk[t] = *reinterpret_cast<const half8*>(qkv + (long long)s_pos[tok] * qkv_pitch + E + head * HD + lq * 8);
-        }
-        float4v sacc[4][4];
-#pragma unroll
-        for (int it = 0; it < 4; ++it)
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) {
-                sacc[it][jt] = (float4v){0.f, 0.f, 0.f, 0.f};
-                sacc[it][jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fq[it], fk[jt], sacc[it][jt], 0, 0, 0);
-            }
-        // softmax over j for each row i = it*16 + lq*4 + r ; this lane holds columns j = jt*16 + lr
-#pragma unroll
-        for (int it = 0; it < 4; ++it)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = it * 16 + lq * 4 + r;
-                const int yi = i / WS, xi = i % WS;
-                const int reg_i = s_region[i];
-                float v[4];
-                float mx = -3.0e38f;
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt) {
-                    const int j = jt * 16 + lr;
-                    const int yj = j / WS, xj = j % WS;
-                    float a = sacc[it][jt][r] * scale + myB[(yi - yj + WS - 1) * (2 * WS - 1) + (xi - xj + WS - 1)];
-                    if (shift && s_region[j] != reg_i) a += -100.0f;
-                    v[jt] = a;
-                    mx = fmaxf(mx, a);
-                }
-                mx = row16_max(mx);   // the 16 lanes holding a row's columns are one DPP row
-                float sum = 0.f;
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt) {
-                    v[jt] = __expf(v[jt] - mx);
-                    sum += v[jt];
-                }
-                sum = row16_sum(sum);
-                const float inv = __builtin_amdgcn_rcpf(sum);
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt) myP[i * P_PITCH + jt * 16 + lr] = (half_t)(v[jt] * inv);
-            }
-        // (wave-local LDS tile: no workgroup barrier needed, only the LDS writes to land)
-        __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-        __builtin_amdgcn_wave_barrier();
-        // O = P V : A = P[i][j] (rows on lr, k contiguous), B[k=j][col=d] from the V tile
-        float4v oacc[4][2];
-#pragma unroll
-        for (int it = 0; it < 4; ++it)
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) oacc[it][dt] = (float4v){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            half8 fv[2];
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-                fv[dt] = *reinterpret_cast<const half8*>(myV + (dt * 16 + lr) * V_PITCH + ks * 32 + lq * 8);
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                half8 fp = *reinterpret_cast<const half8*>(myP + (it * 16 + lr) * P_PITCH + ks * 32 + lq * 8);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt)
-                    oacc[it][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fp, fv[dt], oacc[it][dt], 0, 0, 0);
-            }
-        }
-        // store: lane holds O[i = it*16 + lq*4 + r][d = dt*16 + lr].  Transpose through the (now idle) P
-        // tile so that every token's 64-byte head slice leaves as four 16-byte stores, not 32 2-byte ones.
-        __builtin_amdgcn_s_waitcnt(0xC07F);   // this wave's P reads are done
-        __builtin_amdgcn_wave_barrier();
-        constexpr int O_PITCH = HD + 8;       // halfs; 80-byte rows: 16-byte aligned chunks
-#pragma unroll
-        for (int it = 0; it < 4; ++it)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = it * 16 + lq * 4 + r;
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) myP[i * O_PITCH + dt * 16 + lr] = (half_t)oacc[it][dt][r];
-            }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int pc = lane + 64 * k, tok = pc >> 2, c8 = pc & 3;
-            *reinterpret_cast<half8*>(out + (long long)s_pos[tok] * out_pitch + head * HD + c8 * 8) =
-                *reinterpret_cast<const half8*>(myP + tok * O_PITCH + c8 * 8);
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_wave_barrier();   // the next head reuses this wave's LDS tiles
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Round 3: the same attention with P and O kept in REGISTERS (window_attention_mfma_kernel above moves P, V and the
-// output tile through LDS in 2-byte pieces: 0.32 of its LDS cycles are bank conflicts, 0.34 of the HBM peak).
+// MFMA form (f16 tensors): one workgroup per window, a wave per head in flight, P and O kept in REGISTERS (the earlier
+// form that moved P, V and the output tile through LDS in 2-byte pieces lost 0.32 of its LDS cycles to bank conflicts and
+// reached 0.34 of the HBM peak).
 //   S^T[key][token] = K Q^T        (A = K, B = Q, both straight from global memory): a lane holds, for its token column,
 //                                   16 keys in registers and the rest in the lanes 16 / 32 / 48 away - the softmax over
 //                                   keys is 16 in-lane values + two cross-lane steps, no DPP row reductions
@@ -280,6 +117,7 @@ __global__ __launch_bounds__(64 * ATT_NW) void window_attention_mfma_kernel(cons
 //                                   a token's 64-byte head slice leaves as four 16-byte stores straight from registers
 // The 8-byte halves of a V row's 16-byte chunks are swapped on rows with bit 2 set: the two 4-row blocks a 32-lane half
 // reads (keys 4 apart) then fall on disjoint banks.
+constexpr int ATT_NW = 2;   // waves per workgroup (= heads in flight per window): 2 -> 30 KB of LDS, five workgroups per CU (-26 % vs 4)
 typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 __global__ __launch_bounds__(64 * ATT_NW) void window_attention_tr_kernel(const half_t* __restrict__ qkv,
                                                                   half_t* __restrict__ out, int h, int w,
@@ -436,25 +274,15 @@ extern "C" int elvis_window_attention(const void* qkv, void* out, int dtype, int
                   "elvis_window_attention: bad pitch (qkv %d, out %d: at least 3E / E and multiples of 8)", qkv_pitch, out_pitch);
     long long blocks = (long long)n * (h / ws) * (w / ws) * heads;
     ELVIS_REQUIRE(blocks < 0x7fffffffLL, "elvis_window_attention: grid too large");
-    static const bool attn_valu = getenv("ELVIS_ATTN_VALU") != nullptr;   // A/B switch, read once
-    // the f16 kernels move a token's head slices as 16-byte vectors
+    // the f16 kernel moves a token's head slices as 16-byte vectors
     ELVIS_REQUIRE(dtype != ELVIS_F16 || ((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0),
                   "elvis_window_attention: f16 tensors must be 16-byte aligned");
     const char* name = nullptr;
-    if (dtype == ELVIS_F16 && !attn_valu) {
+    if (dtype == ELVIS_F16) {
         // MFMA path: one workgroup per window, waves loop over heads
         long long wblocks = (long long)n * (h / ws) * (w / ws);
-        static const bool lds_form = getenv("ELVIS_ATTN_LDS") != nullptr;   // A/B switch: round 2's P / O through LDS
-        name = lds_form ? "window_attention_mfma_kernel" : "window_attention_tr_kernel";
-        if (lds_form)
-            hipLaunchKernelGGL(window_attention_mfma_kernel, dim3((unsigned)wblocks), dim3(64 * ATT_NW), 0, (hipStream_t)stream,
-                               (const half_t*)qkv, (half_t*)out, h, w, heads, shift, qkv_pitch, out_pitch, bias_table, scale);
-        else
-            hipLaunchKernelGGL(window_attention_tr_kernel, dim3((unsigned)wblocks), dim3(64 * ATT_NW), 0, (hipStream_t)stream,
-                               (const half_t*)qkv, (half_t*)out, h, w, heads, shift, qkv_pitch, out_pitch, bias_table, scale);
-    } else if (dtype == ELVIS_F16) {
-        name = "window_attention_kernel<half>";
-        hipLaunchKernelGGL(window_attention_kernel<half_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+        name = "window_attention_tr_kernel";
+        hipLaunchKernelGGL(window_attention_tr_kernel, dim3((unsigned)wblocks), dim3(64 * ATT_NW), 0, (hipStream_t)stream,
                            (const half_t*)qkv, (half_t*)out, h, w, heads, shift, qkv_pitch, out_pitch, bias_table, scale);
     } else if (dtype == ELVIS_F32) {
         name = "window_attention_kernel<float>";

@@ -10,23 +10,15 @@ __attribute__((visibility("hidden"))) int elvis_conv_launch_f32_(const void* con
 __attribute__((visibility("hidden"))) int elvis_conv_pack_x3p_(const float* w_oihw, void* packed, int cout, int ctot, int nkc, int n_co_tiles,
                                                               int tco, int taps, hipStream_t stream);
 
-// A/B switches of the experiment tools: the environment is read ONCE per process, never on the per-call path;
-// elvis_conv_debug_set() flips the same switches at run time (tests compare the halo kernels with the generic one).
+// elvis_conv_debug_set("no_halo", 1) sends every conv to the generic implicit-GEMM kernel (tests compare the halo
+// kernels with it); 0 or -1 restores the default dispatch.
 #include <atomic>
-static std::atomic<int> g_no_halo{-1};
-static bool no_halo() {
-    static const bool env = getenv("ELVIS_NO_HALO") != nullptr;
-    const int v = g_no_halo.load(std::memory_order_relaxed);
-    return v < 0 ? env : v != 0;
-}
+static std::atomic<int> g_no_halo{0};
+static bool no_halo() { return g_no_halo.load(std::memory_order_relaxed) > 0; }
 extern "C" int elvis_conv_debug_set(const char* key, int value) {
     ELVIS_REQUIRE(key, "elvis_conv_debug_set: null key");
-    if (!strcmp(key, "no_halo")) { g_no_halo.store(value, std::memory_order_relaxed); return ELVIS_OK; }   // -1: back to the environment
+    if (!strcmp(key, "no_halo")) { g_no_halo.store(value, std::memory_order_relaxed); return ELVIS_OK; }
     ELVIS_REQUIRE(false, "elvis_conv_debug_set: unknown key '%s'", key);
-}
-static int strip_width() {
-    static const int v = getenv("ELVIS_STRIP") ? atoi(getenv("ELVIS_STRIP")) : 8;   // 0 = row-major tile walk
-    return v;
 }
 
 static void conv_geom(const elvis_conv_desc* d, int* nkc1, int* nkc, int* co_pad) {
@@ -175,11 +167,8 @@ extern "C" int elvis_conv2d(const elvis_conv_desc* d, const void* x, const void*
         a.w_in = d->wo;
     }
     a.tiles_x = ((subpix ? d->w : d->wo) + HALO_TX - 1) / HALO_TX;
-    {
-        a.strip = strip_width();
-        if (a.strip < 0 || a.strip >= a.tiles_x) a.strip = 0;
-        a.strip_full = a.strip > 0 ? a.tiles_x / a.strip : 0;
-    }
+    a.strip = HALO_STRIP < a.tiles_x ? HALO_STRIP : 0;
+    a.strip_full = a.strip > 0 ? a.tiles_x / a.strip : 0;
     const int tyv = halo_ty(d);
     a.x3 = d->dtype == ELVIS_F32X3 ? (x3_planar_run(d) ? 2 : 1) : 0;
     a.two = (halo_two(d) || halo_g1(d)) ? 1 : 0;

@@ -20,7 +20,6 @@
 //  translation units so that hipcc compiles the two halves of the instantiation set in parallel)
 #pragma once
 #include "common.h"
-#include <stdlib.h>
 #include <mutex>
 
 // Experiment hooks.  In the product build they are the identity / nothing.  Timing-only variants (no weight or
@@ -137,18 +136,7 @@ __device__ __forceinline__ int lds_row_off(int row, int q) {
     return row * 64 + ((q ^ (((row >> 2) & 1) << 1)) << 4);
 }
 
-#ifndef ELVIS_RES_FMAMIX
-#define ELVIS_RES_FMAMIX 1   /* residual + bias seed of the accumulators as one v_fma_mix_f32 per value; 0: conversion + add (A/B builds) */
-#endif
-#ifndef ELVIS_STATS_LDS
-#define ELVIS_STATS_LDS 1   /* GroupNorm partial sums reduced through LDS columns; 0: the DPP row reduction (A/B builds) */
-#endif
-#ifndef ELVIS_G1_NST128
-#define ELVIS_G1_NST128 3
-#endif
-#ifndef ELVIS_G1_NST64
-#define ELVIS_G1_NST64 2   /* ring stages of the 1x1 GEMM path with a 64-channel tile */
-#endif
+constexpr int G1_NST128 = 3, G1_NST64 = 2;   // ring stages of the 1x1 GEMM path with a 128- / 64-channel tile
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
@@ -540,21 +528,12 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& p) {
     // global -> LDS by LDS-DMA through a ring of G1_NST stages ([pixel tile | weight slice] per
     // 64-byte K chunk), G1_NST-1 chunks in flight, one barrier per chunk, counted vmcnt.  Needs
     // cin (and cin2) to be whole K chunks: the DMA cannot zero-fill channel padding.
-#ifndef ELVIS_COUNTED_W
-#define ELVIS_COUNTED_W 1
-#endif
-#ifndef ELVIS_TWO_WDMA
-#define ELVIS_TWO_WDMA 1
-#endif
-    // weights of the 256-thread kernels: LDS-DMA (no staging registers) or register staging
-    constexpr bool WDMA = TWO && ELVIS_TWO_WDMA;
+    // weights of the 256-thread kernels go global -> LDS by LDS-DMA (no staging registers)
+    constexpr bool WDMA = TWO;
     constexpr bool G1 = TWO && KS == 1;
     // prologue in the hand-written form (prologue_dword_f16): table entries pre-scaled by -log2(e)
-#ifndef ELVIS_ASM_PROLOGUE
-#define ELVIS_ASM_PROLOGUE 1
-#endif
-    constexpr bool PSC = TWO && PRO && sizeof(T) == 2 && ELVIS_ASM_PROLOGUE;
-    constexpr int G1_NST = TCO == 64 ? ELVIS_G1_NST64 : ELVIS_G1_NST128;
+    constexpr bool PSC = TWO && PRO && sizeof(T) == 2;
+    constexpr int G1_NST = TCO == 64 ? G1_NST64 : G1_NST128;
     constexpr int HCH = HP * 4;
     constexpr int H_PER = (HCH + NT - 1) / NT;
     constexpr int HALO_BYTES = HP * 64;
@@ -642,10 +621,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& p) {
         h_ok |= (ok ? 1u : 0u) << i;
     }
     // every halo pixel of this tile lies inside the image and every K chunk is whole: halo_store skips its zero-fill selects
-#ifndef ELVIS_HALO_INSIDE
-#define ELVIS_HALO_INSIDE 1   /* 0: A/B builds (tools/build_variant.py) */
-#endif
-    const bool halo_inside = ELVIS_HALO_INSIDE && oy0 - pad_y >= 0 && oy0 - pad_y + HY <= lh && ox0 - pad_x >= 0 && ox0 - pad_x + HX <= lw &&
+    const bool halo_inside = oy0 - pad_y >= 0 && oy0 - pad_y + HY <= lh && ox0 - pad_x >= 0 && ox0 - pad_x + HX <= lw &&
                              (p.cin % KC) == 0 && (p.cin2 % KC) == 0 && p.cin_pitch >= p.nkc1 * KC && !(KS == 2 && p.s2d);
     const int q4 = tid & 3;   // NT is a multiple of 4: every chunk of this thread has the same q
     const int nkc = p.nkc;
@@ -826,15 +802,6 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& p) {
     // (seeded below, once per path: an unconditional zero fill here cost the hot paths 128 moves plus the copies that merge
     //  the branches' definitions - vector instructions in the start-up compete with the partner workgroup's K loop)
     float4v acc[WCO][WPX];
-#ifndef ELVIS_ACC_SEED_ONCE
-#define ELVIS_ACC_SEED_ONCE 1   /* 0: zero fill up front (A/B builds) */
-#endif
-#if !ELVIS_ACC_SEED_ONCE
-#pragma unroll
-    for (int i = 0; i < WCO; ++i)
-#pragma unroll
-        for (int j = 0; j < WPX; ++j) acc[i][j] = (float4v){0.f, 0.f, 0.f, 0.f};
-#endif
     auto acc_zero = [&]() {
 #pragma unroll
         for (int i = 0; i < WCO; ++i)
@@ -983,15 +950,8 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& p) {
 #pragma unroll
                     for (int d = 0; d < 8; ++d) {
                         float f0, f1;
-#if ELVIS_RES_FMAMIX
                         asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(f0) : "v"(rw[d]), "v"(bv[d >> 1][(d & 1) * 2]));
                         asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(f1) : "v"(rw[d]), "v"(bv[d >> 1][(d & 1) * 2 + 1]));
-#else
-                        typedef _Float16 half2r __attribute__((ext_vector_type(2)));
-                        const half2r hp = __builtin_bit_cast(half2r, rw[d]);
-                        f0 = bv[d >> 1][(d & 1) * 2] + (float)hp[0];
-                        f1 = bv[d >> 1][(d & 1) * 2 + 1] + (float)hp[1];
-#endif
                         acc[d >> 1][j][(d & 1) * 2] = f0;
                         acc[d >> 1][j][(d & 1) * 2 + 1] = f1;
                     }
@@ -1194,7 +1154,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& p) {
         if constexpr (WDMA) {                                                                          \
             /* retire the weight DMAs only: the halo loads of this row were issued AFTER them (younger), \
                so a counted wait leaves those HBM loads in flight across the barrier */                \
-            constexpr int YOUNGER = ELVIS_COUNTED_W ? (DY == 0 ? (PRO ? H_PER : HA) : (DY == 1 && !PRO) ? H_PER - HA : 0) : 0; \
+            constexpr int YOUNGER = DY == 0 ? (PRO ? H_PER : HA) : (DY == 1 && !PRO) ? H_PER - HA : 0;           \
             ELVIS_STAGE_W(asm volatile("s_waitcnt vmcnt(%0)" :: "n"(YOUNGER) : "memory");)            \
         }                                                                                              \
         ELVIS_BARRIER();                                                                               \
@@ -1264,10 +1224,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& p) {
     // update per 4-channel group and sub-tile - ~600 scalar and ~250 select / move instructions per wave that an interior
     // tile does not need), and the GroupNorm partial sums of the STORED halfs through v_dot2_f32_f16 on (pixel j, pixel
     // j + 1) pairs of a channel: 2 v_perm + 4 dot2 per four values instead of 4 conversions + 4 adds + 4 FMAs.
-#ifndef ELVIS_LEAN_EPILOGUE
-#define ELVIS_LEAN_EPILOGUE 1
-#endif
-    constexpr bool LEAN = ELVIS_LEAN_EPILOGUE && TWO && WIDE16 && !ACT && !X3 && (WPX % 2 == 0);
+    constexpr bool LEAN = TWO && WIDE16 && !ACT && !X3 && (WPX % 2 == 0);
     bool lean_done = false;
     if constexpr (LEAN) {
         const bool interior = wide16 && co0 + TCO <= p.cout &&
@@ -1465,7 +1422,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& p) {
             }
         }
     }
-    constexpr bool LDSRED = ELVIS_STATS_LDS && TWO && WCO == 4 && sizeof(T) == 2;
+    constexpr bool LDSRED = TWO && WCO == 4 && sizeof(T) == 2;
     if constexpr (LDSRED) {
         if (p.stats) {
             // Every lane writes its 32 partial sums, one thread per (channel, statistic) adds the tile's NW_PX * 16 pixel-lane
@@ -1557,12 +1514,8 @@ inline bool halo_eligible(const elvis_conv_desc* d) {
 // 512-thread workgroups.  Without the fused prologue: 16 x 32 pixel tile, 64co x 128px per wave
 // (248 VGPRs).  With it: 8 x 32 tile, 64co x 64px per wave, leaving registers for the SiLU math.
 constexpr int HALO_TY = 16, HALO_TY_PRO = 8, HALO_TY_PRO128 = 12, HALO_TX = 32;
-#ifndef ELVIS_G1_TY128
-#define ELVIS_G1_TY128 8
-#endif
-#ifndef ELVIS_G1_TY64
-#define ELVIS_G1_TY64 8
-#endif
+constexpr int HALO_STRIP = 8;   // pixel tiles are walked in column strips of this many tiles (rows of <= 8 tiles: row-major)
+constexpr int G1_TY128 = 8, G1_TY64 = 8;   // tile rows of the 1x1 GEMM path (see "1x1 convs are HBM/latency-bound" below)
 // 256-thread variant, two or three workgroups per CU (f16; 3x3 and sub-pixel 2x2; 128- or 64-channel tile):
 // 6 x 32 pixels x 128 channels (96px x 64co per wave) or 8 x 32 x 64 (64px x 64co per wave)
 // 8 x 32 pixel tiles; the 64-channel tile with the fused prologue uses 16 rows on large images (128 px x
@@ -1581,8 +1534,7 @@ inline int kc_elems(int dtype) { return dtype == ELVIS_F16 ? 32 : 16; }
 // Planar form of the compensated conv (conv_x3p.inc): 3x3 layers with a 64- / 128-channel output tile.  The PACKING of an ELVIS_F32X3 layer depends on channels and kernel size only (x3_planar_fmt), never on the
 // geometry of a call; a call runs on the planar kernel when its geometry is the plain 3x3 / stride 1 / pad 1 one.
 inline bool x3_planar_fmt(const elvis_conv_desc* d) {
-    static const bool off = getenv("ELVIS_NO_X3P") != nullptr;   // A/B switch: keep the interleaved (4-MFMA) form
-    if (off || d->dtype != ELVIS_F32X3 || choose_tile(d->cout).tco < 64 || d->cout % 4) return false;
+    if (d->dtype != ELVIS_F32X3 || choose_tile(d->cout).tco < 64 || d->cout % 4) return false;
     if (d->ksize == 2) return d->subpixel != ELVIS_CONV_S2D || d->cin % 128 == 0;   // space-to-depth: whole 32-channel chunks per phase
     return d->ksize == 3 && (d->cin2 == 0 || d->cin % 32 == 0);
 }
@@ -1592,26 +1544,25 @@ inline bool x3_planar_run(const elvis_conv_desc* d) {
     return d->stride == 1 && d->pad_before == 1 && !d->upsample && d->ho == d->h && d->wo == d->w;
 }
 inline int kc_of(const elvis_conv_desc* d) { return x3_planar_fmt(d) ? 32 : kc_elems(d->dtype); }   // input channels per K chunk
-// two-workgroups-per-CU variant: f16, 3x3, 128-channel tile, LDS footprint <= 80 KB
+// two-workgroups-per-CU (256-thread) variant: f16, 3x3 or 2x2, 64- or 128-channel tile, LDS footprint <= 80 KB.  Without
+// the prologue the footprint is at most 70 912 bytes (128-channel 3x3 tile), so the rule always holds; only the
+// prologue's per-chunk table (256 bytes per K chunk) can push a 3x3 conv to the 512-thread kernels.
 inline bool halo_two(const elvis_conv_desc* d) {
-    static const int mode = getenv("ELVIS_HALO2") ? atoi(getenv("ELVIS_HALO2")) : 1;   // 0 disables (A/B runs)
     const int tco = choose_tile(d->cout).tco, ks = d->ksize;
-    if (!mode || (ks != 3 && ks != 2) || d->dtype != ELVIS_F16 || tco < 64) return false;
-    if (mode == 2 && (ks != 3 || tco != 128)) return false;
+    if ((ks != 3 && ks != 2) || d->dtype != ELVIS_F16 || tco < 64) return false;
     int nkc = (d->cin + 31) / 32 + (d->cin2 > 0 ? (d->cin2 + 31) / 32 : 0);
     size_t lds = (size_t)(halo_ty2(d) + ks - 1) * (HALO_TX + ks - 1) * 64 + 2 * ks * (size_t)tco * 64 + (d->prologue ? (size_t)nkc * 256 : 0);
     return lds <= 80 * 1024;
 }
 // 1x1 GEMM path with LDS-DMA staging: f16, whole 32-channel K chunks, 64/128-channel tile
 inline bool halo_g1(const elvis_conv_desc* d) {
-    static const int on = getenv("ELVIS_G1") ? atoi(getenv("ELVIS_G1")) : 1;   // 0 disables (A/B runs)
-    return on && d->ksize == 1 && d->dtype == ELVIS_F16 && choose_tile(d->cout).tco >= 64 && d->cin % 32 == 0 &&
+    return d->ksize == 1 && d->dtype == ELVIS_F16 && choose_tile(d->cout).tco >= 64 && d->cin % 32 == 0 &&
            d->cin2 % 32 == 0;
 }
 inline int halo_ty(const elvis_conv_desc* d) {
     if (x3_planar_run(d)) return choose_tile(d->cout).tco == 128 ? 12 : 16;   // conv_x3p.inc X3P_TY128 / X3P_TY64
     if (halo_two(d)) return halo_ty2(d);
-    if (halo_g1(d)) return choose_tile(d->cout).tco == 128 ? ELVIS_G1_TY128 : ELVIS_G1_TY64;
+    if (halo_g1(d)) return choose_tile(d->cout).tco == 128 ? G1_TY128 : G1_TY64;
     if (d->ksize == 3 && d->prologue && choose_tile(d->cout).tco == 128) return HALO_TY_PRO128;
     // narrow output tiles (cout <= 32: HBM-bound layers) use the 8-row tile too: 61 KB of LDS and few accumulator
     // registers, so two 512-thread workgroups share a CU and their load / store phases overlap
@@ -1674,8 +1625,8 @@ int launch_halo_p(const ConvArgs& a, hipStream_t stream) {
         if (a.x3) return launch_halo_p<T, TCO, PRO, KS, NT, ACT, TY2, true>(a, stream);
     }
     constexpr bool TWO = NT == 256;
-    constexpr int TY = (TWO && KS == 1) ? (TCO == 128 ? ELVIS_G1_TY128 : ELVIS_G1_TY64) : TWO ? TY2 : (KS == 3 && PRO && TCO == 128) ? HALO_TY_PRO128 : ((PRO || KS == 1 || TCO <= 32) ? HALO_TY_PRO : HALO_TY);
-    const size_t lds_fixed = (TWO && KS == 1) ? (TCO == 64 ? ELVIS_G1_NST64 : ELVIS_G1_NST128) * ((size_t)TY * HALO_TX * 64 + (size_t)TCO * 64)
+    constexpr int TY = (TWO && KS == 1) ? (TCO == 128 ? G1_TY128 : G1_TY64) : TWO ? TY2 : (KS == 3 && PRO && TCO == 128) ? HALO_TY_PRO128 : ((PRO || KS == 1 || TCO <= 32) ? HALO_TY_PRO : HALO_TY);
+    const size_t lds_fixed = (TWO && KS == 1) ? (TCO == 64 ? G1_NST64 : G1_NST128) * ((size_t)TY * HALO_TX * 64 + (size_t)TCO * 64)
                            : (TWO ? 1 : 2) * (size_t)((TY + KS - 1) * (HALO_TX + KS - 1) * 64) + ((TWO || KS == 2) ? 2 : 3) * KS * (size_t)TCO * 64;
     const size_t lds = lds_fixed + (PRO ? (size_t)a.nkc * 4 * 2 * DT<T>::VEC * sizeof(float) : 0);
     ELVIS_REQUIRE(lds <= 160 * 1024, "conv3x3_halo: %zu bytes of LDS needed (too many input channels)", lds);
@@ -1719,9 +1670,14 @@ template <typename T, int TCO> int launch_halo(const ConvArgs& a, hipStream_t st
                                   : launch_halo_p<T, TCO, false, 3, 256, false, HALO_TY2_TALL>(a, stream);
         }
         if (a.two) return a.prologue ? launch_halo_p<T, TCO, true, 3, 256>(a, stream) : launch_halo_p<T, TCO, false, 3, 256>(a, stream);
+        // halo_two() holds for every f16 2x2 / 3x3 conv without the prologue (its LDS formula gives at most 70 912 of the
+        // 81 920 bytes, for the 128-channel 3x3 tile): only the prologue's per-chunk table can push a conv past it
+        ELVIS_REQUIRE(a.ksize == 3 && a.prologue, "conv3x3_halo: a conv without the prologue must fit the 256-thread kernel");
+        return launch_halo_p<T, TCO, true, 3>(a, stream);
+    } else {
+        if (a.ksize == 2) return launch_halo_p<T, TCO, false, 2>(a, stream);
+        return a.prologue ? launch_halo_p<T, TCO, true, 3>(a, stream) : launch_halo_p<T, TCO, false, 3>(a, stream);
     }
-    if (a.ksize == 2) return launch_halo_p<T, TCO, false, 2>(a, stream);
-    return a.prologue ? launch_halo_p<T, TCO, true, 3>(a, stream) : launch_halo_p<T, TCO, false, 3>(a, stream);
 }
 
 template <typename T> int dispatch(const ConvArgs& a, int id, hipStream_t stream) {

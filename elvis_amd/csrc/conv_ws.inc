@@ -144,7 +144,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws_kernel(ConvArgs p, int ntil
     //   P0: [barrier] registers -> halo [barrier] request the next halo; first half of the (chunk, tap) steps
     //   P1: [barrier] [barrier] second half of the steps; epilogue
     // half 0 runs P0 on even steps, half 1 on odd steps; 2 * iterations + 1 steps in all.
-    // STAG = false: both halves in step (P1 then needs no barriers).  Measured per instantiation (tools/ab_ws.sh): the stagger
+    // STAG = false: both halves in step (P1 then needs no barriers).  Measured per instantiation (tools/experiments/README.md): the stagger
     // pays where the MFMA share is largest (two K chunks x 64 channels: 1.03 -> 0.86 ms on the 64 -> 64 convs) and costs
     // 10 - 20 % on the single-chunk and narrow tiles, whose phases are too short for four barriers per tile.
     constexpr int STEPS = 9 * NKC, S0 = (STEPS + 1) / 2;
@@ -248,8 +248,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws_kernel(ConvArgs p, int ntil
 
 // Which convs run here: narrow f16 3x3 layers on large images, nothing fused but bias and ReLU.
 inline bool ws_shape_ok(const elvis_conv_desc* d) {
-    static const bool off = getenv("ELVIS_NO_WS") != nullptr;   // A/B switch, read once
-    if (off || d->dtype != ELVIS_F16 || d->ksize != 3 || d->stride != 1 || d->pad_before != 1 || d->upsample || d->prologue) return false;
+    if (d->dtype != ELVIS_F16 || d->ksize != 3 || d->stride != 1 || d->pad_before != 1 || d->upsample || d->prologue) return false;
     if (d->ho != d->h || d->wo != d->w || (d->act != 0 && d->act != 3)) return false;
     if (choose_tile(d->cout).tco > 64) return false;
     const int nkc = (d->cin + 31) / 32 + (d->cin2 > 0 ? (d->cin2 + 31) / 32 : 0);
@@ -257,7 +256,11 @@ inline bool ws_shape_ok(const elvis_conv_desc* d) {
     return (long long)d->ho * d->wo >= 128 * 1024;   // per image (never per batch: the kernel choice must not depend on n)
 }
 
-template <int NKC, int TCO, bool STAG> int launch_ws(const ConvArgs& a, hipStream_t stream) {
+// the halves run half an iteration apart where measured faster: two K chunks x a 64-channel tile
+constexpr bool ws_stagger(int nkc, int tco) { return nkc == 2 && tco == 64; }
+
+template <int NKC, int TCO> int launch_ws(const ConvArgs& a, hipStream_t stream) {
+    constexpr bool STAG = ws_stagger(NKC, TCO);
     constexpr size_t lds = (size_t)NKC * 9 * TCO * 64 + 2 * (size_t)NKC * 340 * 64;
     static std::mutex mu;
     static bool attr_set[64] = {};
@@ -289,24 +292,15 @@ template <int NKC, int TCO, bool STAG> int launch_ws(const ConvArgs& a, hipStrea
     return ELVIS_OK;
 }
 
-// the halves run half an iteration apart where measured faster: two K chunks x a 64-channel tile (ELVIS_WS_STAG = 0 / 1: never / always)
-inline bool ws_stagger(int nkc, int tco) {
-    static const int v = getenv("ELVIS_WS_STAG") ? atoi(getenv("ELVIS_WS_STAG")) : -1;
-    return v < 0 ? (nkc == 2 && tco == 64) : v != 0;
-}
-template <int NKC, int TCO> int launch_ws2(const ConvArgs& a, hipStream_t stream) {
-    return ws_stagger(NKC, TCO) ? launch_ws<NKC, TCO, true>(a, stream) : launch_ws<NKC, TCO, false>(a, stream);
-}
-
 inline int dispatch_ws(const ConvArgs& a, int tco, hipStream_t stream) {
     if (a.nkc == 1) {
-        if (tco == 64) return launch_ws2<1, 64>(a, stream);
-        if (tco == 32) return launch_ws2<1, 32>(a, stream);
-        return launch_ws2<1, 16>(a, stream);
+        if (tco == 64) return launch_ws<1, 64>(a, stream);
+        if (tco == 32) return launch_ws<1, 32>(a, stream);
+        return launch_ws<1, 16>(a, stream);
     }
-    if (tco == 64) return launch_ws2<2, 64>(a, stream);
-    if (tco == 32) return launch_ws2<2, 32>(a, stream);
-    return launch_ws2<2, 16>(a, stream);
+    if (tco == 64) return launch_ws<2, 64>(a, stream);
+    if (tco == 32) return launch_ws<2, 32>(a, stream);
+    return launch_ws<2, 16>(a, stream);
 }
 
 }  // namespace

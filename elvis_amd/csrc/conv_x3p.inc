@@ -434,58 +434,29 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x3p_kernel(ConvArgs p) {
             }
         }
     }
-    if constexpr (ELVIS_STATS_LDS) {
-        if (p.stats) {
-            // (as conv3x3_halo_body: every lane writes its 32 partial sums, one thread per (channel, statistic) adds the
-            //  tile's NW_PX * 16 pixel-lane partials in a fixed order; rows padded to an odd length)
-            constexpr int PXP = NW_PX * 16 + 1;
-            static_assert(TCO * 2 * PXP * 4 <= HALO_BYTES + 2 * W_ROW, "statistics columns fit the kernel's LDS");
-            float* red = reinterpret_cast<float*>(smem);   // all LDS reads are done (last barrier of the loop)
-            const int pcol = w_px * 16 + lr;
-#pragma unroll
-            for (int i = 0; i < WCO; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int cl = w_co * 64 + lq * 16 + i * 4 + r;
-                    red[(cl * 2 + 0) * PXP + pcol] = st[i][r];
-                    red[(cl * 2 + 1) * PXP + pcol] = sq[i][r];
-                }
-            __syncthreads();
-            if (tid < TCO * 2 && co0 + (tid >> 1) < p.cout) {
-                const float* row = red + tid * PXP;
-                float a = 0.f;
-#pragma unroll
-                for (int q = 0; q < NW_PX * 16; ++q) a += row[q];
-                const long long tile = ((long long)nimg * p.tiles_y + ty) * p.tiles_x + tx;
-                p.stats[(tile * p.cout + co0) * 2 + tid] = a;
-            }
-        }
-    } else
     if (p.stats) {
-        float* red = reinterpret_cast<float*>(smem);   // [NW_PX][TCO][2]; all LDS reads are done (last barrier of the loop)
+        // (as conv3x3_halo_body: every lane writes its 32 partial sums, one thread per (channel, statistic) adds the
+        //  tile's NW_PX * 16 pixel-lane partials in a fixed order; rows padded to an odd length)
+        constexpr int PXP = NW_PX * 16 + 1;
+        static_assert(TCO * 2 * PXP * 4 <= HALO_BYTES + 2 * W_ROW, "statistics columns fit the kernel's LDS");
+        float* red = reinterpret_cast<float*>(smem);   // all LDS reads are done (last barrier of the loop)
+        const int pcol = w_px * 16 + lr;
 #pragma unroll
         for (int i = 0; i < WCO; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float a = row16_sum(st[i][r]), b = row16_sum(sq[i][r]);
-                if (lr == 0) {
-                    const int cl = w_co * 64 + lq * 16 + i * 4 + r;
-                    red[(w_px * TCO + cl) * 2 + 0] = a;
-                    red[(w_px * TCO + cl) * 2 + 1] = b;
-                }
+                const int cl = w_co * 64 + lq * 16 + i * 4 + r;
+                red[(cl * 2 + 0) * PXP + pcol] = st[i][r];
+                red[(cl * 2 + 1) * PXP + pcol] = sq[i][r];
             }
         __syncthreads();
-        if (tid < TCO && co0 + tid < p.cout) {
-            float a = 0.f, b = 0.f;
+        if (tid < TCO * 2 && co0 + (tid >> 1) < p.cout) {
+            const float* row = red + tid * PXP;
+            float a = 0.f;
 #pragma unroll
-            for (int w = 0; w < NW_PX; ++w) {
-                a += red[(w * TCO + tid) * 2 + 0];
-                b += red[(w * TCO + tid) * 2 + 1];
-            }
+            for (int q = 0; q < NW_PX * 16; ++q) a += row[q];
             const long long tile = ((long long)nimg * p.tiles_y + ty) * p.tiles_x + tx;
-            float* dst = p.stats + (tile * p.cout + co0 + tid) * 2;
-            dst[0] = a;
-            dst[1] = b;
+            p.stats[(tile * p.cout + co0) * 2 + tid] = a;
         }
     }
 }

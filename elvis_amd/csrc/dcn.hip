@@ -20,7 +20,6 @@
 //  * dcnv2_kernel (any dtype / grouping): the generic scalar form - the fp32 exact mode and odd shapes.
 #include "common.h"
 #include <type_traits>
-#include <stdlib.h>
 #include <mutex>
 
 namespace {
@@ -354,8 +353,7 @@ extern "C" int elvis_dcnv2(const void* x, const void* offset_mask, const void* w
     const unsigned grid = (unsigned)((total + DPX - 1) / DPX);
     const int mask_off = deformable_groups * 18;
     // the tiled gather + MFMA kernel: f16, one channel per deformable group, up to 8 channels, up to 64 outputs
-    static const bool no_tile = getenv("ELVIS_DCN_GENERIC") != nullptr;   // A/B switch
-    if (dtype == ELVIS_F16 && !no_tile && deformable_groups == cin && (cin == 7 || cin == 8) && x_pitch == 8 && cout <= 64 &&
+    if (dtype == ELVIS_F16 && deformable_groups == cin && (cin == 7 || cin == 8) && x_pitch == 8 && cout <= 64 &&
         om_pitch % 8 == 0 && om_pitch >= ((27 * cin * 2 + 15) / 16) * 8 && (((uintptr_t)x | (uintptr_t)offset_mask | (uintptr_t)out | (uintptr_t)weight) & 15) == 0) {
         const int ksteps = (K + 31) / 32;
         const int tiles_x = (w + TX_ - 1) / TX_, tiles_y = (h + TY_ - 1) / TY_;

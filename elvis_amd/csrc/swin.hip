@@ -23,7 +23,6 @@
 // half a chunk behind waves 0-3 so that one SIMD partner's GELU overlaps the other's matrix part.
 #include "common.h"
 #include <mutex>
-#include <stdlib.h>
 
 namespace {
 
@@ -446,23 +445,13 @@ template <int C, int PXT, int MODE, bool STAG> int launch_swin(const SwinArgs& a
 // (tools/swin_bench.py, us per launch, lockstep -> staggered): C = 192 MLP 1137 -> 1064 but projection + MLP 1315 -> 1477
 // (the combined kernel spills once the half-steps split its loop); C = 64 487 -> 548 and 559 -> 740; C = 128 369 -> 392 and
 // 434 -> 438; C = 256 314 -> 276 and 339 -> 328.  So: staggered for C = 256 and for the C = 192 MLP, lockstep otherwise.
-// ELVIS_SWIN_STAGGER=0/1 forces it off / on for A/B runs (read once).
-static int stagger_mode() {
-    static const int v = getenv("ELVIS_SWIN_STAGGER") ? atoi(getenv("ELVIS_SWIN_STAGGER")) : -1;
-    return v;
-}
-template <int C, int PXT, int MODE> int launch_swin_s(const SwinArgs& a, hipStream_t stream, bool default_stag) {
-    if constexpr (MODE == 0) return launch_swin<C, PXT, MODE, false>(a, stream);
-    const int m = stagger_mode();
-    const bool st = m < 0 ? default_stag : m != 0;
-    return st ? launch_swin<C, PXT, MODE, true>(a, stream) : launch_swin<C, PXT, MODE, false>(a, stream);
-}
+// The linear (MODE 0) has no half-steps to stagger.
 template <int MODE> int dispatch_swin(int c, const SwinArgs& a, hipStream_t stream) {
     switch (c) {
-        case 64: return launch_swin_s<64, 2, MODE>(a, stream, false);
-        case 128: return launch_swin_s<128, 2, MODE>(a, stream, false);
-        case 192: return launch_swin_s<192, 2, MODE>(a, stream, MODE == 1);
-        case 256: return launch_swin_s<256, 1, MODE>(a, stream, true);
+        case 64: return launch_swin<64, 2, MODE, false>(a, stream);
+        case 128: return launch_swin<128, 2, MODE, false>(a, stream);
+        case 192: return launch_swin<192, 2, MODE, MODE == 1>(a, stream);
+        case 256: return launch_swin<256, 1, MODE, MODE != 0>(a, stream);
         default: break;
     }
     elvis_set_error("elvis_swin: channels must be 64, 128, 192 or 256 (got %d)", c);

@@ -7,7 +7,6 @@ multiple of 8, pad channels are kept at zero) accompanied by the logical channel
 from __future__ import annotations
 
 import ctypes as C
-import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -15,9 +14,6 @@ import torch
 
 from . import _lib as L
 from ._lib import ConvDesc, check, lib, ptr
-
-
-_NO_S2D = bool(os.environ.get("ELVIS_NO_S2D"))   # A/B switch, read once at import
 
 
 def _s(t: torch.Tensor) -> int:
@@ -420,7 +416,7 @@ class PackedDownConv:
     @staticmethod
     def supported_pad1(dtype, cin: int, cout: int) -> bool:
         """`conv3x3(x, stride=2, padding=1)` (the Blur / DCT slots' down convs) in the same form: f16, 32 or more outputs."""
-        return dtype == torch.float16 and cin % 32 == 0 and cout >= 32 and not _NO_S2D
+        return dtype == torch.float16 and cin % 32 == 0 and cout >= 32
 
     def __init__(self, weight_oihw: torch.Tensor, bias: Optional[torch.Tensor], dtype, device, cin: int, pad1: bool = False):
         cout, ctot, kh, kw = weight_oihw.shape

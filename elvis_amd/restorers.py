@@ -102,8 +102,7 @@ class _SwinStage:
         self.cfg, self.ch, self.heads = cfg, ch, ch // cfg.head_dim
         f32 = dict(device=device, dtype=torch.float32)
         self.blocks = []
-        from .sinsr import _SWIN_FUSE
-        fuse = _SWIN_FUSE and ops.SwinFused.supported(dtype, ch, 3 * ch) and ops.SwinFused.supported(dtype, ch, cfg.mlp_ratio * ch)
+        fuse = ops.SwinFused.supported(dtype, ch, 3 * ch) and ops.SwinFused.supported(dtype, ch, cfg.mlp_ratio * ch)
         for i in range(nblocks):
             b = f"{prefix}.{i}"
             lin = lambda n: PackedConv(sd[n + ".weight"][:, :, None, None], sd[n + ".bias"], dtype, device,

@@ -21,10 +21,6 @@ from .ops import Act, PackedConv, PackedUpConv
 from .weights import SinSRConfig, frame_noise, make_sinsr_weights, timestep_embedding, unet_layout
 
 
-import os as _os_mod
-_SWIN_FUSE = not _os_mod.environ.get("ELVIS_NO_SWIN_FUSE")   # A/B switch, read once at import
-
-
 class _GN:
     def __init__(self, sd, p, device):
         self.gamma = sd[p + ".weight"].to(device=device, dtype=torch.float32).contiguous()
@@ -38,14 +34,13 @@ def _conv(sd, p, dtype, device, cin, cin2=0) -> PackedConv:
 class _DownConv:
     """The autoencoder's Downsample: pad (0,1,0,1) + 3x3 conv, stride 2.  f16 (whole 32-channel chunks) and
     compensated-fp32 sections (16-channel chunks) with even sizes: the space-to-depth form on the halo-tile
-    kernel (ops.PackedDownConv, with fused GroupNorm statistics); otherwise (exact fp32 mode, ELVIS_NO_S2D=1,
+    kernel (ops.PackedDownConv, with fused GroupNorm statistics); otherwise (exact fp32 mode,
     odd sizes) the generic strided kernel - same result to rounding."""
 
     def __init__(self, sd, p, dtype, device, cin):
-        import os
         self.direct = _conv(sd, p, dtype, device, cin)
         self.s2d = None
-        if ops.PackedDownConv.supported(dtype, cin, sd[p + ".weight"].shape[0], x3=ops._X3_DEFAULT) and not os.environ.get("ELVIS_NO_S2D"):
+        if ops.PackedDownConv.supported(dtype, cin, sd[p + ".weight"].shape[0], x3=ops._X3_DEFAULT):
             self.s2d = ops.PackedDownConv(sd[p + ".weight"], sd[p + ".bias"], dtype, device, cin)
 
     def __call__(self, x: Act, want_stats=False) -> Act:
@@ -54,18 +49,9 @@ class _DownConv:
         return self.direct(x, stride=2, pad=0, ho=x.h // 2, wo=x.w // 2)
 
 
-class _UpConv:
-    """nearest-2x upsample + 3x3 conv: sub-pixel 2x2 decomposition (2.25x fewer FLOPs) or the
-    fused-upsample 3x3 kernel (ELVIS_NO_SUBPIXEL=1 / subpixel=False), same results to rounding."""
-
-    def __init__(self, sd, p, dtype, device, cin, subpixel=True):
-        self.sub = PackedUpConv(sd[p + ".weight"], sd[p + ".bias"], dtype, device, cin) if subpixel else None
-        self.full = None if subpixel else _conv(sd, p, dtype, device, cin)
-
-    def __call__(self, x: Act, want_stats=False) -> Act:
-        if self.sub is not None:
-            return self.sub(x, want_stats=want_stats)
-        return self.full(x, upsample=True, want_stats=want_stats)
+def _upconv(sd, p, dtype, device, cin) -> PackedUpConv:
+    """nearest-2x upsample + 3x3 conv as the sub-pixel 2x2 decomposition (2.25x fewer FLOPs)."""
+    return PackedUpConv(sd[p + ".weight"], sd[p + ".bias"], dtype, device, cin)
 
 
 def _linear(sd, p, dtype, device) -> PackedConv:
@@ -89,33 +75,25 @@ class _ResBlock:
         if self.skip is None and cin2:
             raise ValueError("a concatenated input needs a skip projection")
 
-    # The fused prologue recomputes normalise+SiLU once per 128-channel output tile (and 1.33x for
-    # the halo); with >= 4 output tiles it is cheaper to materialise the activated tensor once
-    # (one extra read+write) and run the faster prologue-free 16x32-tile kernel.
-    import os as _os
-    FUSE_MAX_COUT = int(_os.environ.get("ELVIS_FUSE_MAX_COUT", str(1 << 30)))   # A/B switch, see DESIGN.md 5.2
-
     def __call__(self, x: Act, x2: Optional[Act] = None, fuse_gn=False) -> Act:
         xs = [x] if x2 is None else [x, x2]
         pa, pb = ops.groupnorm_affine(xs, self.norm1.gamma, self.norm1.beta, self.groups, self.eps)
-        fuse1 = fuse_gn and self.conv1.cout <= self.FUSE_MAX_COUT
-        fuse2 = fuse_gn and self.conv2.cout <= self.FUSE_MAX_COUT
-        if fuse1:
+        if fuse_gn:
             h = self.conv1(x, x2, prologue=(pa, pb), want_stats=True)
         else:
             a1 = ops.affine_act(x, pa[:, :x.c].contiguous(), pb[:, :x.c].contiguous(), act=2)
             a2 = None
             if x2 is not None:
                 a2 = ops.affine_act(x2, pa[:, x.c:].contiguous(), pb[:, x.c:].contiguous(), act=2)
-            h = self.conv1(a1, a2, want_stats=fuse_gn)
+            h = self.conv1(a1, a2)
             del a1, a2
         pa, pb = ops.groupnorm_affine([h], self.norm2.gamma, self.norm2.beta, self.groups, self.eps,
                                       scale=self.scale, shift=self.shift)
         res = x if self.skip is None else self.skip(x, x2)
-        if fuse2:
+        if fuse_gn:
             return self.conv2(h, prologue=(pa, pb), residual=res, want_stats=True)
         ops.affine_act(h, pa, pb, act=2, out=h)
-        return self.conv2(h, residual=res, want_stats=fuse_gn)
+        return self.conv2(h, residual=res)
 
 
 class _SwinLayer:
@@ -126,7 +104,7 @@ class _SwinLayer:
         self.embed = _conv(sd, p + ".patch_embed.proj", dtype, device, ch)
         self.embed_norm = (sd[p + ".patch_embed.norm.weight"].to(**f32), sd[p + ".patch_embed.norm.bias"].to(**f32))
         self.blocks = []
-        fuse = _SWIN_FUSE and ops.SwinFused.supported(dtype, E, 3 * E) and ops.SwinFused.supported(dtype, E, cfg.mlp_ratio * E)
+        fuse = ops.SwinFused.supported(dtype, E, 3 * E) and ops.SwinFused.supported(dtype, E, cfg.mlp_ratio * E)
         for d in range(cfg.swin_depth):
             b = f"{p}.blocks.{d}"
             w = lambda n: sd[b + n]
@@ -201,8 +179,6 @@ class SinSRModel:
             self.dtype = self.sec_dtype["unet"]
         elif precision not in (None, "f16", "f32"):
             raise ValueError(f"unknown precision '{precision}'")
-        import os
-        self.subpixel_up = not os.environ.get("ELVIS_NO_SUBPIXEL")
         sd = state_dict if state_dict is not None else make_sinsr_weights(cfg, weight_seed)
         dev = self.device
         with torch.cuda.device(dev), ops.x3_default(self.x3):
@@ -240,7 +216,7 @@ class SinSRModel:
             if kind == "swin":
                 return _SwinLayer(sd, p, meta[0], cfg, dt, dev)
             if kind == "up":
-                return _UpConv(sd, p, dt, dev, meta[0], self.subpixel_up)
+                return _upconv(sd, p, dt, dev, meta[0])
             if kind == "down":
                 return _conv(sd, p, dt, dev, meta[0])
             raise ValueError(kind)
@@ -304,7 +280,7 @@ class SinSRModel:
             for b in range(nrb + 1):
                 blocks.append(rb(f"ae.decoder.up.{lvl}.block.{b}", cin, ch * mults[lvl], dt))
                 cin = ch * mults[lvl]
-            us = _UpConv(sd, f"ae.decoder.up.{lvl}.upsample.conv", dt, dev, cin, self.subpixel_up) if lvl != 0 else None
+            us = _upconv(sd, f"ae.decoder.up.{lvl}.upsample.conv", dt, dev, cin) if lvl != 0 else None
             self.d_up.append((blocks, us, dt))
         self.d_norm_out = _GN(sd, "ae.decoder.norm_out", dev)
         self.d_conv_out = _conv(sd, "ae.decoder.conv_out", self.sec_dtype["dec0"], dev, cin)

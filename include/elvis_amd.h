@@ -190,8 +190,8 @@ int elvis_conv_kernel_name(const elvis_conv_desc* d, char* buf, size_t n);
  * elvis_conv_kernel_name_for_call(d, 0, 0, ...); both come from the selection rule elvis_conv2d dispatches by. */
 int elvis_conv_kernel_name_for_call(const elvis_conv_desc* d, int has_residual, int has_stats, char* buf, size_t n);
 
-/* Test / experiment switch: "no_halo" = 1 routes every conv to the generic implicit-GEMM kernel (what the environment
- * variable ELVIS_NO_HALO does for a whole process), 0 forces the halo kernels, -1 returns to the environment's choice. */
+/* Test switch: "no_halo" = 1 routes every conv to the generic implicit-GEMM kernel (tests compare the halo kernels with
+ * it); 0 and -1 return to the default dispatch. */
 int elvis_conv_debug_set(const char* key, int value);
 
 /* 1 when a descriptor with dtype ELVIS_F32X3 has a compensated-f16 kernel (3x3 stride 1 / sub-pixel 2x2 / 1x1 on the

@@ -554,12 +554,3 @@ def _build_cases():
 
 
 CASES = _build_cases()
-
-# A/B-only instantiations: built for the experiment tools' environment switches, reached by no production call.
-# name -> the switch (or the reason) that reaches it.
-AB_ONLY = {
-    **{_halo("half", tco, 512, 16, False, ks, act): "ELVIS_HALO2=0 (the 256-thread variant always fits these)"
-       for tco in (64, 128) for ks in (2, 3) for act in (False, True)},
-    **{f"conv3x3_ws_kernel<{nkc},{tco},{'false' if nkc == 2 and tco == 64 else 'true'}>":
-       f"ELVIS_WS_STAG={0 if nkc == 2 and tco == 64 else 1}" for nkc in (1, 2) for tco in (16, 32, 64)},
-}

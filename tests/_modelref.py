@@ -386,8 +386,6 @@ def model_kernel_symbols(path: str):
 
 
 # ============================================================================================ cases
-AB_SWITCHES = ("ELVIS_ATTN_VALU", "ELVIS_ATTN_LDS", "ELVIS_DCN_GENERIC", "ELVIS_SWIN_STAGGER")
-
 SWIN_PXT = {64: 2, 128: 2, 192: 2, 256: 1}
 SWIN_STAG = {(64, 1): False, (128, 1): False, (192, 1): True, (256, 1): True,
              (64, 2): False, (128, 2): False, (192, 2): False, (256, 2): True}
@@ -507,14 +505,6 @@ def _build_cases():
 
 
 CASES = _build_cases()
-
-# A/B-only instantiations: built for the experiment switches, reached by no default dispatch.  name -> the switch.
-AB_ONLY = {
-    "window_attention_mfma_kernel": "ELVIS_ATTN_LDS",
-    "window_attention_kernel<half>": "ELVIS_ATTN_VALU",
-    **{f"swin_fused_kernel<{c},{SWIN_PXT[c]},{mode},{'false' if SWIN_STAG[(c, mode)] else 'true'}>":
-       f"ELVIS_SWIN_STAGGER={0 if SWIN_STAG[(c, mode)] else 1}" for c in (64, 128, 192, 256) for mode in (1, 2)},
-}
 
 
 # ============================================================================================ inputs

@@ -1,5 +1,5 @@
 """CPU-side checks of the conv test matrix (tests/_convref.py, tests/test_gpu_conv_matrix.py): the dispatch
-ledger (every conv kernel instantiation in the built library is reached by a matrix case or listed as A/B-only),
+ledger (every conv kernel instantiation in the built library is reached by a matrix case),
 the name query against the dispatch rule, and a mutation self-test of the tier-1 / tier-2 / statistics checks."""
 import ctypes as C
 import math
@@ -29,7 +29,7 @@ def test_demangle():
 
 
 def test_dispatch_ledger(built_lib):
-    """The conv instantiations of the built library == the names the matrix's cases resolve to + the A/B-only list."""
+    """The conv instantiations of the built library == the names the matrix's cases resolve to."""
     syms = _syms(built_lib)
     assert len(syms) >= 100, f"only {len(syms)} conv kernel symbols decoded"
     reached = {}
@@ -37,12 +37,11 @@ def test_dispatch_ledger(built_lib):
         for name in R.resolve(c):
             assert name == c.expect, f"{c.id} resolves to {name}, expected {c.expect}"
             reached.setdefault(name, c.id)
-    missing = syms - set(reached) - set(R.AB_ONLY)
-    assert not missing, f"instantiations without a matrix case or an A/B-only entry: {sorted(missing)}"
-    stale = (set(reached) | set(R.AB_ONLY)) - syms
-    assert not stale, f"cases / exclusions naming instantiations the library does not build: {sorted(stale)}"
-    both = set(reached) & set(R.AB_ONLY)
-    assert not both, f"listed as A/B-only but reached by a case: {sorted(both)}"
+    missing = syms - set(reached)
+    assert not missing, f"instantiations without a matrix case: {sorted(missing)}"
+    stale = set(reached) - syms
+    assert not stale, f"cases naming instantiations the library does not build: {sorted(stale)}"
+    assert syms == set(reached)
     assert len(set(c.id for c in R.CASES)) == len(R.CASES)
 
 

@@ -152,7 +152,7 @@ def test_conv_halo_fused(gpu_device, dtype, cfg):
     gd = got.double()
     assert torch.allclose(s[:, :, 0], gd.sum((2, 3)), rtol=1e-5, atol=1e-2)
     assert torch.allclose(s[:, :, 1], (gd * gd).sum((2, 3)), rtol=1e-5, atol=1e-2)
-    # and the same conv on the generic implicit-GEMM kernel (the run-time form of ELVIS_NO_HALO=1)
+    # and the same conv on the generic implicit-GEMM kernel (elvis_conv_debug_set("no_halo", 1))
     d = ops.ConvDesc()
     d.dtype, d.n, d.h, d.w, d.ho, d.wo = ops.L.dtype_code(dtype), n, h, w, ho, wo
     d.cin, d.cin_pitch, d.cin2, d.cin2_pitch = c1, a1.pitch, c2, (a2.pitch if c2 else 0)
@@ -685,7 +685,7 @@ def test_conv_weight_stationary(gpu_device, cfg):
     assert got.shape == ref.shape
     assert (got - ref).abs().max().item() < TOL[dtype]
     assert y.t[..., cout:].abs().max().item() == 0 if y.t.shape[-1] > cout else True   # pad channels are written as zeros
-    # same result as the halo-tile kernels (ELVIS_NO_HALO also switches this kernel off: both fall back to the generic one)
+    # same result as the halo-tile kernels (the "no_halo" debug switch also turns this kernel off: both fall back to the generic one)
     from elvis_amd._lib import lib, check
     check(lib().elvis_conv_debug_set(b"no_halo", 1))
     try:

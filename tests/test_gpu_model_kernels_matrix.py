@@ -4,7 +4,6 @@ default dispatch, asserts through elvis_last_launch the one instantiation it rea
 buffer that is NaN on its logical elements and a sentinel on the pitch padding and on one guard row past the end: every
 logical element must be written and nothing else."""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -15,12 +14,6 @@ import _modelref as R
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 1234.0
-
-
-def _no_ab_switches():
-    bad = [v for v in R.AB_SWITCHES if v in os.environ]
-    assert not bad, (f"A/B switch(es) {bad} set in the environment: the matrix checks the default dispatch only - "
-                     "unset them and rerun")
 
 
 def _last_launch():
@@ -157,7 +150,6 @@ RUN = {"attn": _run_attn, "swin": _run_swin, "dcn": _run_dcn}
 
 @pytest.mark.parametrize("case", R.CASES, ids=[c.id for c in R.CASES])
 def test_model_kernel_matrix(gpu_device, case):
-    _no_ab_switches()
     name, y, b = RUN[case.op](case, gpu_device)
     assert name == case.expect, f"{case.id}: launched {name!r}, the case exists for {case.expect!r}"
     assert y.shape == b.ref.shape
@@ -178,7 +170,6 @@ def test_window_attention_rejects_bad_pitch_and_alignment(gpu_device):
     """The f16 kernels move 16-byte vectors: a pitch that is not a multiple of 8 or a pointer off 16 bytes is a
     ValueError before anything launches."""
     from elvis_amd._lib import lib, check, ptr, stream_handle, F16
-    _no_ab_switches()
     heads, E, h, w = 2, 64, 8, 8
     qkv = torch.zeros(h * w * (3 * E + 8) + 64, dtype=torch.float16, device=gpu_device)
     out = torch.zeros(h * w * (E + 8) + 64, dtype=torch.float16, device=gpu_device)

@@ -1,6 +1,6 @@
 """CPU-side checks of the attention / Swin / DCNv2 matrix (tests/_modelref.py, tests/test_gpu_model_kernels_matrix.py):
 the dispatch ledger (every window_attention_*, swin_fused_kernel and dcnv2_* instantiation in the built library is
-reached by a matrix case or listed as A/B-only) and a mutation self-test: each checker is fed CPU-made wrong outputs and
+reached by a matrix case) and a mutation self-test: each checker is fed CPU-made wrong outputs and
 must reject every one of them."""
 import math
 
@@ -24,23 +24,17 @@ def test_demangle():
 
 
 def test_dispatch_ledger(built_lib):
-    """The model-kernel instantiations of the built library == the ones the matrix's cases expect + the A/B-only list."""
+    """The model-kernel instantiations of the built library == the ones the matrix's cases expect."""
     syms = R.model_kernel_symbols(built_lib)
     reached = {}
     for c in R.CASES:
         reached.setdefault(c.expect, c.id)
-    ab = set(R.AB_ONLY)
-    assert ab == {"window_attention_mfma_kernel", "window_attention_kernel<half>"} | {
-        f"swin_fused_kernel<{c},{R.SWIN_PXT[c]},{m},{'false' if R.SWIN_STAG[(c, m)] else 'true'}>"
-        for c in (64, 128, 192, 256) for m in (1, 2)}
-    assert len(ab) == 10
-    missing = syms - set(reached) - ab
-    assert not missing, f"instantiations without a matrix case or an A/B-only entry: {sorted(missing)}"
-    stale = (set(reached) | ab) - syms
-    assert not stale, f"cases / exclusions naming instantiations the library does not build: {sorted(stale)}"
-    both = set(reached) & ab
-    assert not both, f"listed as A/B-only but expected by a case: {sorted(both)}"
-    # every default-reachable instantiation: attention tr + f32, the 12 (C, MODE) Swin pairs, DCNv2 tile<7>/<8> + generic
+    missing = syms - set(reached)
+    assert not missing, f"instantiations without a matrix case: {sorted(missing)}"
+    stale = set(reached) - syms
+    assert not stale, f"cases naming instantiations the library does not build: {sorted(stale)}"
+    assert syms == set(reached)
+    # every instantiation: attention tr + f32, the 12 (C, MODE) Swin pairs, DCNv2 tile<7>/<8> + generic
     assert len([s for s in reached if s.startswith("swin_fused_kernel")]) == 12
     assert {"window_attention_tr_kernel", "window_attention_kernel<float>", "dcnv2_tile_kernel<7>", "dcnv2_tile_kernel<8>",
             "dcnv2_kernel<half>", "dcnv2_kernel<float>"} <= set(reached)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the fused Swin kernels (csrc/swin.hip) on the shapes of the two models.
-    python tools/swin_bench.py            # ELVIS_SWIN_STAGGER=0/1 forces the stagger off / on"""
+    python tools/swin_bench.py"""
 import math, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -40,7 +40,7 @@ for name, c, hid, n, h, w in SHAPES:
         by = (3 if kind == "mlp" else 3 if kind == "proj_mlp" else 4) * c * 2.0 * tok
         print(f"{name:18s} {kind:9s} {t*1e3:8.1f} us  {fl/t/1e9:7.1f} TFLOP/s  {by/t/1e6:7.1f} GB/s algorithmic", flush=True)
 
-# window attention on the same token images (qkv = 3C channels): ELVIS_ATTN_LDS=1 selects round 2's kernel
+# window attention on the same token images (qkv = 3C channels)
 for name, c, hid, n, h, w in SHAPES:
     heads = c // 32
     qkv = ops.Act(torch.randn((n, h, w, 3 * c), device=dev, dtype=torch.float16), 3 * c)
