@@ -162,6 +162,7 @@ extern "C" int elvis_recompose_u8(const uint8_t* a, const uint8_t* b, const int3
         hipLaunchKernelGGL(recompose_rows_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, map, out, h,
                            (w * c) / 16, block * c, block, by, bx, thr, nvec);
         ELVIS_CHECK_LAUNCH("elvis_recompose_u8");
+        elvis_note_launch("recompose_rows_u8_kernel");
         if (map_out) {
             int count = n * by * bx;
             hipLaunchKernelGGL(clamp_map_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, map,
@@ -172,13 +173,15 @@ extern "C" int elvis_recompose_u8(const uint8_t* a, const uint8_t* b, const int3
     }
     int bshift = 0;
     while ((1 << bshift) < block) ++bshift;
-    if ((1 << bshift) == block)
+    const bool pow2 = (1 << bshift) == block;
+    if (pow2)
         hipLaunchKernelGGL(recompose_u8_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, map, out, n, h, w,
                            c, block, bshift, by, bx, thr, total);
     else
         hipLaunchKernelGGL(recompose_u8_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, map, out, n, h, w,
                            c, block, bshift, by, bx, thr, total);
     ELVIS_CHECK_LAUNCH("elvis_recompose_u8");
+    elvis_note_launch(pow2 ? "recompose_u8_kernel<true>" : "recompose_u8_kernel<false>");
     if (map_out) {
         int count = n * by * bx;
         hipLaunchKernelGGL(clamp_map_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, map,
@@ -264,7 +267,8 @@ extern "C" int elvis_area_downscale_u8(const uint8_t* src, uint8_t* dst, int n, 
     ELVIS_REQUIRE(h % factor == 0 && w % factor == 0, "elvis_area_downscale_u8: H,W (%d,%d) not divisible by factor %d", h, w, factor);
     ELVIS_REQUIRE(rounding == ELVIS_ROUND_CV2 || rounding == ELVIS_ROUND_HALF_UP, "elvis_area_downscale_u8: bad rounding");
     long long total_px = (long long)n * (h / factor) * (w / factor);
-    if (c == 3 && factor == 4 && (w * 3) % 4 == 0 && ((uintptr_t)src % 4) == 0) {
+    const bool fast = c == 3 && factor == 4 && (w * 3) % 4 == 0 && ((uintptr_t)src % 4) == 0;
+    if (fast) {
         int grid = (int)((total_px + 255) / 256);
         if (grid > 8192) grid = 8192;
         hipLaunchKernelGGL(area_downscale4_c3_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, n, h,
@@ -277,6 +281,7 @@ extern "C" int elvis_area_downscale_u8(const uint8_t* src, uint8_t* dst, int n, 
                            c, factor, rounding, total);
     }
     ELVIS_CHECK_LAUNCH("elvis_area_downscale_u8");
+    elvis_note_launch(fast ? "area_downscale4_c3_kernel" : "area_downscale_u8_kernel");
     return ELVIS_OK;
 }
 
@@ -332,6 +337,7 @@ extern "C" int elvis_blend_u8(const uint8_t* orig, const uint8_t* rest, const in
     hipLaunchKernelGGL(blend_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, orig, rest, map, out, n, h, w,
                        c, block, by, bx, alpha, total);
     ELVIS_CHECK_LAUNCH("elvis_blend_u8");
+    elvis_note_launch("blend_u8_kernel");
     return ELVIS_OK;
 }
 
@@ -386,6 +392,7 @@ extern "C" int elvis_select_levels_u8(const uint8_t* const* versions, const int3
     hipLaunchKernelGGL(select_levels_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, versions,
                        slot_of_level, n_levels, map, out, n, h, w, c, block, by, bx, total);
     ELVIS_CHECK_LAUNCH("elvis_select_levels_u8");
+    elvis_note_launch("select_levels_u8_kernel");
     return ELVIS_OK;
 }
 
@@ -425,6 +432,7 @@ extern "C" int elvis_tile_accumulate_f32(float* acc, float* wsum, const uint8_t*
     hipLaunchKernelGGL(tile_accumulate_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, acc,
                        wsum, tile, wy, wx, wx2, h, w, y0, x0, th, tw, c, temporal_weight);
     ELVIS_CHECK_LAUNCH("elvis_tile_accumulate_f32");
+    elvis_note_launch("tile_accumulate_kernel");
     return ELVIS_OK;
 }
 
@@ -451,6 +459,7 @@ extern "C" int elvis_tile_normalize_u8(const float* acc, const float* wsum, uint
     if (grid > 8192) grid = 8192;
     hipLaunchKernelGGL(tile_normalize_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, acc, wsum, out, pixels, c);
     ELVIS_CHECK_LAUNCH("elvis_tile_normalize_u8");
+    elvis_note_launch("tile_normalize_kernel");
     return ELVIS_OK;
 }
 
@@ -495,6 +504,7 @@ extern "C" int elvis_sse_u8(const uint8_t* a, const uint8_t* b, const uint8_t* m
     hipLaunchKernelGGL(sse_u8_kernel, dim3(gx, n), dim3(256), 0, (hipStream_t)stream, a, b, mask, sse_out, cnt_out,
                        per_frame, c);
     ELVIS_CHECK_LAUNCH("elvis_sse_u8");
+    elvis_note_launch("sse_u8_kernel");
     return ELVIS_OK;
 }
 
@@ -561,5 +571,6 @@ extern "C" int elvis_block_ssim_u8(const uint8_t* a, const uint8_t* b, float* ss
     hipLaunchKernelGGL(block_ssim_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a, b, ssim_out,
                        win11, n, h, w, c, block_size, by, bx, total);
     ELVIS_CHECK_LAUNCH("elvis_block_ssim_u8");
+    elvis_note_launch("block_ssim_kernel");
     return ELVIS_OK;
 }

@@ -172,10 +172,15 @@ def test_sse_psnr(gpu_device, golden_dir):
     sse, cnt = ops.sse_u8(_dev(a, gpu_device), _dev(b, gpu_device))
     mse = (sse.double() / cnt.double()).cpu().numpy()
     assert np.allclose(mse, g["mse_full"], rtol=1e-6)
+    sq = ((a.astype(np.int64) - b.astype(np.int64)) ** 2).reshape(len(a), -1)
+    assert np.array_equal(sse.cpu().numpy().astype(np.int64), sq.sum(1))            # integer-exact by construction
     sse, cnt = ops.sse_u8(_dev(a, gpu_device), _dev(b, gpu_device), _dev(m.astype(np.uint8), gpu_device))
     cntn = cnt.cpu().numpy()
     msem = np.where(cntn > 0, sse.cpu().numpy() / np.maximum(cntn, 1), 0.0)
     assert np.allclose(msem, g["mse_masked"], rtol=1e-6)
+    use = np.repeat(m.astype(bool).reshape(len(a), -1), a.shape[-1], axis=1)
+    assert np.array_equal(sse.cpu().numpy().astype(np.int64), (sq * use).sum(1))
+    assert np.array_equal(cntn.astype(np.int64), use.sum(1))
 
 
 def test_error_conventions(gpu_device):
