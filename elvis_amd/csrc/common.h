@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <mutex>
 #include "../../include/elvis_amd.h"
 
 #define ELVIS_WAVE 64
@@ -13,6 +14,16 @@
 void elvis_set_error(const char* fmt, ...);
 // records the instantiation a launch reached (a string literal or other static storage), read back by elvis_last_launch
 void elvis_note_launch(const char* name);
+// an instantiation's name, formatted once from the launcher's template parameters: `static const ElvisKernelName name(...)`
+struct __attribute__((visibility("hidden"))) ElvisKernelName {
+    char s[64];
+    __attribute__((format(printf, 2, 3))) ElvisKernelName(const char* fmt, ...) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(s, sizeof(s), fmt, ap);
+        va_end(ap);
+    }
+};
 
 #define ELVIS_REQUIRE(cond, ...)                      \
     do {                                              \
@@ -32,6 +43,36 @@ void elvis_note_launch(const char* name);
     } while (0)
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// The 160 KB dynamic-LDS opt-in is a per-device function attribute: a launcher sets it once per (instantiation, device),
+// under a lock - hosts call from pool threads, one per device.  A launcher keeps one static ElvisLdsOptIn per
+// instantiation; elvis_lds_opt_in returns ELVIS_OK, or ELVIS_E_RUNTIME with "<prefix>: <HIP's error string>" as the error
+// (the prefix is a printf format).
+static inline int elvis_device_slot() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    return dev;
+}
+struct ElvisLdsOptIn {
+    std::mutex mu;
+    bool attr_set[64] = {};
+};
+__attribute__((format(printf, 4, 5))) static inline int elvis_lds_opt_in(const void* fn, ElvisLdsOptIn& st, int dev, const char* prefix, ...) {
+    std::lock_guard<std::mutex> guard(st.mu);
+    if (st.attr_set[dev]) return ELVIS_OK;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) {
+        char what[160];
+        va_list ap;
+        va_start(ap, prefix);
+        vsnprintf(what, sizeof(what), prefix, ap);
+        va_end(ap);
+        elvis_set_error("%s: %s", what, hipGetErrorString(e));
+        return ELVIS_E_RUNTIME;
+    }
+    st.attr_set[dev] = true;
+    return ELVIS_OK;
+}
 
 typedef _Float16 half_t;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));

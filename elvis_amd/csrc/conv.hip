@@ -1,11 +1,17 @@
 // C ABI of the conv kernels (elvis_conv2d and friends) + the f16 instantiations; the fp32 / compensated-f16
-// instantiations live in conv_f32.hip.  Kernels, launch helpers and dispatch rules: conv_kernels.inc.
+// instantiations live in conv_f32.hip.  Kernels, leaf launchers and the descriptor predicates: conv_kernels.inc.
+//
+// One path from a call to its kernel: conv_path() picks the family from the descriptor and the call's two flags,
+// conv_plan() builds the kernels' argument block, conv_walk() goes down the launch tree to a leaf launcher.  elvis_conv2d
+// walks it to launch; the name query and elvis_conv_stats_tiles walk the same tree with a ConvPick, which the leaf answers
+// with its own name and tile height instead of launching.  Nothing here names a kernel or knows a tile height: to change
+// one edit halo_tile_rows() and the constants beside it (conv_kernels.inc).
 #include "conv_kernels.inc"
 #include "conv_ws.inc"
 #include <string.h>
 
-// conv_f32.hip: halo != 0 -> launch_halo<float, tco>, else dispatch<float>(id)
-__attribute__((visibility("hidden"))) int elvis_conv_launch_f32_(const void* conv_args, int halo, int tco, int id, hipStream_t stream);
+// conv_f32.hip: halo != 0 -> launch_x3p<tco> / launch_halo<float, tco>, else dispatch<float>(id); query: a ConvPick* or null
+__attribute__((visibility("hidden"))) int elvis_conv_launch_f32_(const void* conv_args, int halo, int tco, int id, hipStream_t stream, void* query);
 // conv_f32.hip: the planar compensated form's weight packing (conv_x3p.inc)
 __attribute__((visibility("hidden"))) int elvis_conv_pack_x3p_(const float* w_oihw, void* packed, int cout, int ctot, int nkc, int n_co_tiles,
                                                               int tco, int taps, hipStream_t stream);
@@ -64,13 +70,6 @@ extern "C" int elvis_conv_pack_weights(const elvis_conv_desc* d, const float* w_
     return ELVIS_OK;
 }
 
-extern "C" int elvis_conv_stats_tiles(const elvis_conv_desc* d) {
-    if (!d || !halo_eligible(d)) return 0;
-    int ty = halo_ty(d);
-    if (d->ksize == 2 && d->subpixel != ELVIS_CONV_S2D) return d->n * ((d->h + ty - 1) / ty) * ((d->w + HALO_TX - 1) / HALO_TX);   // per parity launch
-    return d->n * ((d->ho + ty - 1) / ty) * ((d->wo + HALO_TX - 1) / HALO_TX);
-}
-
 // Does a descriptor with dtype ELVIS_F32X3 run on a compensated-f16 kernel?  (Its weights are packed as (hi, lo)
 // half pairs, which only those kernels read: a host keeps the ELVIS_F32 packing for everything else.)
 static bool x3_eligible(const elvis_conv_desc* d) {
@@ -83,9 +82,8 @@ extern "C" int elvis_conv_x3_eligible(const elvis_conv_desc* d) {
     return x3_eligible(d) ? 1 : 0;
 }
 
-// The one rule that picks a conv's kernel family: elvis_conv2d dispatches by it and the name query reports it, so the two
-// cannot drift.  A call with a residual or a statistics buffer never runs on the weight-stationary kernel (it fuses
-// neither): such a call of a ws-eligible shape lands on the halo kernel.
+// The one rule that picks a conv's kernel family.  A call with a residual or a statistics buffer never runs on the
+// weight-stationary kernel (it fuses neither): such a call of a ws-eligible shape lands on the halo kernel.
 enum class ConvPath { WS, HALO, IGEMM };
 static ConvPath conv_path(const elvis_conv_desc* d, bool has_residual, bool has_stats) {
     if (no_halo()) return ConvPath::IGEMM;
@@ -93,30 +91,79 @@ static ConvPath conv_path(const elvis_conv_desc* d, bool has_residual, bool has_
     return halo_eligible(d) ? ConvPath::HALO : ConvPath::IGEMM;
 }
 
+// Down the launch tree to the leaf.  query == nullptr: the leaf launches on `stream`; else it fills *query, no HIP call.
+static int conv_walk(const elvis_conv_desc* d, ConvPath path, const ConvArgs& a, hipStream_t stream, ConvPick* query) {
+    const TileCfg t = choose_tile(d->cout);
+    const bool f16 = d->dtype == ELVIS_F16;
+    if (path == ConvPath::WS) return dispatch_ws(a, t.tco, stream, query);
+    if (path == ConvPath::IGEMM) return f16 ? dispatch<half_t>(a, t.id, stream, query) : elvis_conv_launch_f32_(&a, 0, t.tco, t.id, stream, query);
+    if (!f16) return elvis_conv_launch_f32_(&a, 1, t.tco, t.id, stream, query);
+    switch (t.tco) {
+        case 128: return launch_halo<half_t, 128>(a, stream, query);
+        case 64: return launch_halo<half_t, 64>(a, stream, query);
+        case 32: return launch_halo<half_t, 32>(a, stream, query);
+        default: return launch_halo<half_t, 16>(a, stream, query);
+    }
+}
+
+// The argument block as far as it follows from the descriptor and the path (the caller adds pointers and residual
+// pitch), and the leaf the call resolves to: the pixel-tile grid is sized from the tile height that leaf reports.
+static int conv_plan(const elvis_conv_desc* d, ConvPath path, ConvArgs& a, ConvPick& pick) {
+    a.n = d->n; a.h = d->h; a.w_in = d->w;
+    a.cin = d->cin; a.cin_pitch = d->cin_pitch; a.cin2 = d->cin2; a.cin2_pitch = d->cin2_pitch;
+    a.cout = d->cout; a.cout_pitch = d->cout_pitch;
+    a.ksize = d->ksize; a.stride = d->stride; a.pad = d->pad_before; a.upsample = d->upsample;
+    a.ho = d->ho; a.wo = d->wo; a.act = d->act; a.prologue = d->prologue;
+    conv_geom(d, &a.nkc1, &a.nkc, &a.co_pad);
+    TileCfg t = choose_tile(d->cout);
+    a.M = (long long)d->n * d->ho * d->wo;
+    a.n_co_tiles = a.co_pad / t.tco;
+    a.n_px_tiles = (a.M + t.tpx - 1) / t.tpx;
+    const bool s2d = d->ksize == 2 && d->subpixel == ELVIS_CONV_S2D;
+    const bool subpix = d->ksize == 2 && !s2d;
+    a.sub = d->ksize == 2;
+    a.par_a = subpix ? (d->subpixel - 1) >> 1 : 0;
+    a.par_b = subpix ? (d->subpixel - 1) & 1 : 0;
+    a.ostr = subpix ? 2 : 1;
+    a.pad2y = subpix ? 1 - a.par_a : (s2d ? d->pad_before : 0);   // space-to-depth: pad (0,1,0,1) form 0, pad 1 form 1
+    a.pad2x = subpix ? 1 - a.par_b : (s2d ? d->pad_before : 0);
+    a.s2d = s2d ? 1 : 0;
+    a.istr = s2d ? 2 : 1;
+    a.nkc_c = s2d ? d->cin / 4 / kc_of(d) : 0x3fffffff;
+    a.wfull = d->w;
+    if (s2d) {   // the kernel sees the phase image: ho x wo pixels of 4C channels
+        a.h = d->ho;
+        a.w_in = d->wo;
+    }
+    a.x3 = d->dtype == ELVIS_F32X3 ? (x3_planar_run(d) ? 2 : 1) : 0;
+    a.two = (halo_two(d) || halo_g1(d)) ? 1 : 0;
+    a.tall = (halo_two(d) && halo_tall(d)) ? 1 : 0;
+    int rc = conv_walk(d, path, a, nullptr, &pick);
+    if (rc) return rc;
+    a.tiles_x = ((subpix ? d->w : d->wo) + HALO_TX - 1) / HALO_TX;   // a sub-pixel parity launch covers the low-resolution grid
+    a.tiles_y = pick.ty > 0 ? ((subpix ? d->h : d->ho) + pick.ty - 1) / pick.ty : 0;
+    a.strip = HALO_STRIP < a.tiles_x ? HALO_STRIP : 0;
+    a.strip_full = a.strip > 0 ? a.tiles_x / a.strip : 0;
+    return ELVIS_OK;
+}
+
+extern "C" int elvis_conv_stats_tiles(const elvis_conv_desc* d) {
+    if (!d || !halo_eligible(d)) return 0;
+    ConvArgs a{};
+    ConvPick pick{};
+    if (conv_plan(d, ConvPath::HALO, a, pick)) return 0;   // statistics are fused by the halo family only
+    return d->n * a.tiles_y * a.tiles_x;   // per parity launch for the sub-pixel form
+}
+
 extern "C" int elvis_conv_kernel_name_for_call(const elvis_conv_desc* d, int has_residual, int has_stats, char* buf, size_t n) {
     int rc = validate(d);
     if (rc) return rc;
     ELVIS_REQUIRE(buf && n > 0, "elvis_conv_kernel_name: null buffer");
-    const char* t = d->dtype == ELVIS_F16 ? "half" : "float";
-    TileCfg c = choose_tile(d->cout);
-    const ConvPath path = conv_path(d, has_residual != 0, has_stats != 0);
-    if (path == ConvPath::WS) {
-        const int nkc = (d->cin + 31) / 32 + (d->cin2 > 0 ? (d->cin2 + 31) / 32 : 0);
-        snprintf(buf, n, "conv3x3_ws_kernel<%d,%d,%s>", nkc, c.tco, ws_stagger(nkc, c.tco) ? "true" : "false");
-    } else if (path == ConvPath::HALO) {
-        const bool pro = d->ksize == 3 && d->prologue;
-        if (x3_planar_run(d))
-            snprintf(buf, n, "conv3x3_x3p_kernel<%d,%d,%d,%s,%s>", c.tco, halo_ty(d), d->ksize, pro ? "true" : "false", d->act ? "true" : "false");
-        else if (d->dtype == ELVIS_F32X3 && c.tco >= 64)
-            snprintf(buf, n, "conv3x3_halo_x3_kernel<%d,%d,%s,%d,%s>", c.tco, halo_ty(d), pro ? "true" : "false", d->ksize,
-                     d->act ? "true" : "false");
-        else
-        snprintf(buf, n, "conv3x3_halo_kernel<%s,%d,%d,%d,%s,%d,%s>", t, c.tco, (halo_two(d) || halo_g1(d)) ? 256 : 512, halo_ty(d),
-                 pro ? "true" : "false", d->ksize, d->act ? "true" : "false");
-    } else {
-        static const int cfg[4][4] = {{4, 4, 2, 2}, {4, 2, 1, 4}, {2, 4, 1, 4}, {1, 4, 1, 4}};
-        snprintf(buf, n, "conv_igemm_kernel<%s,%d,%d,%d,%d>", t, cfg[c.id][0], cfg[c.id][1], cfg[c.id][2], cfg[c.id][3]);
-    }
+    ConvArgs a{};
+    ConvPick pick{};
+    rc = conv_plan(d, conv_path(d, has_residual != 0, has_stats != 0), a, pick);
+    if (rc) return rc;
+    snprintf(buf, n, "%s", pick.name);
     return ELVIS_OK;
 }
 
@@ -137,65 +184,14 @@ extern "C" int elvis_conv2d(const elvis_conv_desc* d, const void* x, const void*
     ELVIS_REQUIRE(!residual || residual_pitch >= d->cout, "elvis_conv2d: bad residual pitch");
     ELVIS_REQUIRE(((uintptr_t)x | (uintptr_t)(x2 ? x2 : x) | (uintptr_t)w_packed | (uintptr_t)out) % 16 == 0,
                   "elvis_conv2d: pointers must be 16-byte aligned");
-    ConvArgs a;
-    a.x = x; a.x2 = x2; a.w = w_packed; a.bias = bias; a.res = residual; a.pa = pa; a.pb = pb; a.out = out;
-    a.n = d->n; a.h = d->h; a.w_in = d->w;
-    a.cin = d->cin; a.cin_pitch = d->cin_pitch; a.cin2 = d->cin2; a.cin2_pitch = d->cin2_pitch;
-    a.cout = d->cout; a.cout_pitch = d->cout_pitch; a.res_pitch = residual_pitch;
-    a.ksize = d->ksize; a.stride = d->stride; a.pad = d->pad_before; a.upsample = d->upsample;
-    a.ho = d->ho; a.wo = d->wo; a.act = d->act; a.prologue = d->prologue;
-    conv_geom(d, &a.nkc1, &a.nkc, &a.co_pad);
-    TileCfg t = choose_tile(d->cout);
-    a.M = (long long)d->n * d->ho * d->wo;
-    a.n_co_tiles = a.co_pad / t.tco;
-    a.n_px_tiles = (a.M + t.tpx - 1) / t.tpx;
-    a.stats = stats;
-    const bool s2d = d->ksize == 2 && d->subpixel == ELVIS_CONV_S2D;
-    const bool subpix = d->ksize == 2 && !s2d;
-    a.sub = d->ksize == 2;
-    a.par_a = subpix ? (d->subpixel - 1) >> 1 : 0;
-    a.par_b = subpix ? (d->subpixel - 1) & 1 : 0;
-    a.ostr = subpix ? 2 : 1;
-    a.pad2y = subpix ? 1 - a.par_a : (s2d ? d->pad_before : 0);   // space-to-depth: pad (0,1,0,1) form 0, pad 1 form 1
-    a.pad2x = subpix ? 1 - a.par_b : (s2d ? d->pad_before : 0);
-    a.s2d = s2d ? 1 : 0;
-    a.istr = s2d ? 2 : 1;
-    a.nkc_c = s2d ? d->cin / 4 / kc_of(d) : 0x3fffffff;
-    a.wfull = d->w;
-    if (s2d) {   // the kernel sees the phase image: ho x wo pixels of 4C channels
-        a.h = d->ho;
-        a.w_in = d->wo;
-    }
-    a.tiles_x = ((subpix ? d->w : d->wo) + HALO_TX - 1) / HALO_TX;
-    a.strip = HALO_STRIP < a.tiles_x ? HALO_STRIP : 0;
-    a.strip_full = a.strip > 0 ? a.tiles_x / a.strip : 0;
-    const int tyv = halo_ty(d);
-    a.x3 = d->dtype == ELVIS_F32X3 ? (x3_planar_run(d) ? 2 : 1) : 0;
-    a.two = (halo_two(d) || halo_g1(d)) ? 1 : 0;
-    a.tall = (halo_two(d) && halo_tall(d)) ? 1 : 0;
-    a.tiles_y = ((subpix ? d->h : d->ho) + tyv - 1) / tyv;
     const ConvPath path = conv_path(d, residual != nullptr, stats != nullptr);
-    if (path == ConvPath::WS) {
-        ELVIS_REQUIRE((long long)d->n * d->h * d->w < 0x7fffffffLL, "conv: input too large for 32-bit pixel indices");
-        ConvArgs b = a;
-        b.tiles_x = (d->wo + 31) / 32;
-        b.tiles_y = (d->ho + 7) / 8;
-        return dispatch_ws(b, t.tco, (hipStream_t)stream);
-    }
-    if (path == ConvPath::HALO) {
-        ELVIS_REQUIRE((long long)d->n * d->h * d->w < 0x7fffffffLL, "conv: input too large for 32-bit pixel indices");
-        hipStream_t st = (hipStream_t)stream;
-        if (d->dtype == ELVIS_F16) {
-            switch (t.tco) {
-                case 128: return launch_halo<half_t, 128>(a, st);
-                case 64: return launch_halo<half_t, 64>(a, st);
-                case 32: return launch_halo<half_t, 32>(a, st);
-                default: return launch_halo<half_t, 16>(a, st);
-            }
-        }
-        return elvis_conv_launch_f32_(&a, 1, t.tco, t.id, st);
-    }
-    ELVIS_REQUIRE(!stats, "elvis_conv2d: fused statistics need a 3x3/stride-1 conv with cout >= 64 (query elvis_conv_stats_tiles)");
-    if (d->dtype == ELVIS_F16) return dispatch<half_t>(a, t.id, (hipStream_t)stream);
-    return elvis_conv_launch_f32_(&a, 0, t.tco, t.id, (hipStream_t)stream);
+    ELVIS_REQUIRE(path != ConvPath::IGEMM || !stats, "elvis_conv2d: fused statistics need a 3x3/stride-1 conv with cout >= 64 (query elvis_conv_stats_tiles)");
+    ELVIS_REQUIRE(path == ConvPath::IGEMM || (long long)d->n * d->h * d->w < 0x7fffffffLL, "conv: input too large for 32-bit pixel indices");
+    ConvArgs a{};
+    ConvPick pick{};
+    rc = conv_plan(d, path, a, pick);
+    if (rc) return rc;
+    a.x = x; a.x2 = x2; a.w = w_packed; a.bias = bias; a.res = residual; a.pa = pa; a.pb = pb; a.out = out;
+    a.res_pitch = residual_pitch; a.stats = stats;
+    return conv_walk(d, path, a, (hipStream_t)stream, nullptr);
 }

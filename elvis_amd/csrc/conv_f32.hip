@@ -3,18 +3,19 @@
 #include "conv_kernels.inc"
 #include "conv_x3p.inc"
 
-__attribute__((visibility("hidden"))) int elvis_conv_launch_f32_(const void* conv_args, int halo, int tco, int id, hipStream_t stream) {
-    const ConvArgs& a = *static_cast<const ConvArgs*>(conv_args);   // same definition in both translation units
-    if (halo && a.x3 == 2) return tco == 128 ? launch_x3p<128>(a, stream) : launch_x3p<64>(a, stream);
+__attribute__((visibility("hidden"))) int elvis_conv_launch_f32_(const void* conv_args, int halo, int tco, int id, hipStream_t stream, void* query) {
+    const ConvArgs& a = *static_cast<const ConvArgs*>(conv_args);   // same definitions in both translation units
+    ConvPick* const q = static_cast<ConvPick*>(query);
+    if (halo && a.x3 == 2) return tco == 128 ? launch_x3p<128>(a, stream, q) : launch_x3p<64>(a, stream, q);
     if (halo) {
         switch (tco) {
-            case 128: return launch_halo<float, 128>(a, stream);
-            case 64: return launch_halo<float, 64>(a, stream);
-            case 32: return launch_halo<float, 32>(a, stream);
-            default: return launch_halo<float, 16>(a, stream);
+            case 128: return launch_halo<float, 128>(a, stream, q);
+            case 64: return launch_halo<float, 64>(a, stream, q);
+            case 32: return launch_halo<float, 32>(a, stream, q);
+            default: return launch_halo<float, 16>(a, stream, q);
         }
     }
-    return dispatch<float>(a, id, stream);
+    return dispatch<float>(a, id, stream, q);
 }
 
 __attribute__((visibility("hidden"))) int elvis_conv_pack_x3p_(const float* w_oihw, void* packed, int cout, int ctot, int nkc, int n_co_tiles,

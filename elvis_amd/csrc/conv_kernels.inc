@@ -20,7 +20,6 @@
 //  translation units so that hipcc compiles the two halves of the instantiation set in parallel)
 #pragma once
 #include "common.h"
-#include <mutex>
 
 // Experiment hooks.  In the product build they are the identity / nothing.  Timing-only variants (no weight or
 // halo staging, no barriers, no stores - all of which produce WRONG results - and the in-kernel phase stamps)
@@ -63,6 +62,9 @@ struct ConvArgs {
     int n_co_tiles;
     long long n_px_tiles;
     // halo kernel only
+    // two, tall and x3 (below) steer the host's launch tree (launch_halo, launch_halo_p) and no kernel reads them.  They
+    // stay where they are: this struct is the kernels' argument block, and taking a field out would move every later
+    // kernarg offset and so change the device code - a change of its own, with a benchmark.
     int two, tall;        // 256-thread two-workgroups-per-CU variant; its 16-row form
     float* stats;         // [n*tiles_y*tiles_x][cout][2] partial (sum, sumsq) or null
     int tiles_x, tiles_y;
@@ -71,8 +73,17 @@ struct ConvArgs {
     int s2d, istr, nkc_c, wfull;   // s2d: K chunk kc = phase (kc / nkc_c) of the full-res input (row stride wfull), istr = 2
     int strip;            // > 0: pixel tiles are walked in column strips of this many tiles (L2 reuse of halo rows)
     int strip_full;       // tiles_x / strip: whole strips per image row of tiles
-    int x3;               // fp32 storage, error-compensated f16 MFMA (ELVIS_F32X3)
+    int x3;               // fp32 storage, error-compensated f16 MFMA (ELVIS_F32X3): 1, or 2 on the planar kernel
 };
+
+// What a leaf launcher answers when it is asked what it would launch (a non-null `query` argument) instead of launching:
+// the instantiation's name as profilers print it, in static storage, and the rows of its pixel tile (0: no pixel tile).
+struct ConvPick {
+    const char* name;
+    int ty;
+    int set(const char* name_, int ty_) { name = name_; ty = ty_; return ELVIS_OK; }
+};
+constexpr const char* tf(bool b) { return b ? "true" : "false"; }
 
 template <typename T> struct Frag;
 template <> struct Frag<half_t> { typedef half8 type; };
@@ -1515,22 +1526,44 @@ inline bool halo_eligible(const elvis_conv_desc* d) {
 // (248 VGPRs).  With it: 8 x 32 tile, 64co x 64px per wave, leaving registers for the SiLU math.
 constexpr int HALO_TY = 16, HALO_TY_PRO = 8, HALO_TY_PRO128 = 12, HALO_TX = 32;
 constexpr int HALO_STRIP = 8;   // pixel tiles are walked in column strips of this many tiles (rows of <= 8 tiles: row-major)
-constexpr int G1_TY128 = 8, G1_TY64 = 8;   // tile rows of the 1x1 GEMM path (see "1x1 convs are HBM/latency-bound" below)
+constexpr int G1_TY128 = 8, G1_TY64 = 8;   // 1x1 GEMM path: HBM/latency-bound, the 8-row tile halves LDS and registers so two workgroups fit a CU
 // 256-thread variant, two or three workgroups per CU (f16; 3x3 and sub-pixel 2x2; 128- or 64-channel tile):
 // 6 x 32 pixels x 128 channels (96px x 64co per wave) or 8 x 32 x 64 (64px x 64co per wave)
 // 8 x 32 pixel tiles; the 64-channel tile with the fused prologue uses 16 rows on large images (128 px x
 // 64 cout per wave: better fragment reuse), 8 rows where a taller tile would leave CUs without work
 constexpr int HALO_TY2 = 8, HALO_TY2_TALL = 16;
+constexpr int X3P_TY128 = 12, X3P_TY64 = 16;   // the planar compensated kernel (conv_x3p.inc)
+
+// The one tile-height rule: a tile height is edited here and nowhere else.  The leaf launchers evaluate it at compile time
+// for the kernel's TY, halo_two() at run time; tiles_y and the statistics rows follow from the height the leaf reports.
+//   the fused-prologue kernel with a 128-channel tile uses 12 rows (64co x 96px per wave, ~210 VGPRs)
+//   narrow output tiles (cout <= 32: HBM-bound layers) use the 8-row tile too: 61 KB of LDS and few accumulator
+//   registers, so two 512-thread workgroups share a CU and their load / store phases overlap
+constexpr int halo_tile_rows(int ks, bool pro, int tco, int nt, bool tall) {
+    if (nt == 256) return ks == 1 ? (tco == 128 ? G1_TY128 : G1_TY64) : tall ? HALO_TY2_TALL : HALO_TY2;
+    if (ks == 3 && pro && tco == 128) return HALO_TY_PRO128;
+    return (pro || ks == 1 || tco <= 32) ? HALO_TY_PRO : HALO_TY;
+}
+constexpr int x3p_tile_rows(int tco) { return tco == 128 ? X3P_TY128 : X3P_TY64; }
+
+// The one dynamic-LDS footprint of the halo kernels: what launch_halo_p reserves and what halo_two() holds against 80 KB.
+// pro_chunks: K chunks of the fused prologue's (a, b) table (0 without it), kc channels each.
+constexpr size_t halo_tile_bytes(int ty, int ks) { return (size_t)(ty + ks - 1) * (HALO_TX + ks - 1) * 64; }   // one input tile with its halo
+constexpr size_t halo_lds_bytes(int ks, int tco, int ty, int nt, int pro_chunks, int kc = 32) {
+    const bool two = nt == 256;
+    const size_t fixed = (two && ks == 1) ? (tco == 64 ? G1_NST64 : G1_NST128) * ((size_t)ty * HALO_TX * 64 + (size_t)tco * 64)   // 1x1: LDS-DMA ring
+                                          : (two ? 1 : 2) * halo_tile_bytes(ty, ks) + ((two || ks == 2) ? 2 : 3) * ks * (size_t)tco * 64;
+    return fixed + (size_t)pro_chunks * kc * 2 * sizeof(float);
+}
+
 inline bool halo_tall(const elvis_conv_desc* d) {
     // (round 3: also without the prologue for single-K-chunk layers - the DCT slot's 32 -> 189 offset / mask conv streams
     //  more weight bytes than output bytes through an 8-row tile; two-chunk layers measured slower with the tall tile)
     return d->ksize == 3 && choose_tile(d->cout).tco == 64 && (d->prologue || d->cin + d->cin2 <= 32) &&
            (long long)d->ho * d->wo >= 128 * 1024;   // per image, NOT per batch: the tile shape sets the statistics' summation order
 }
-inline int halo_ty2(const elvis_conv_desc* d) { return halo_tall(d) ? HALO_TY2_TALL : HALO_TY2; }
-// 1x1 convs are HBM/latency-bound: the 8-row tile halves LDS and registers so two workgroups fit a CU
-// the fused-prologue kernel with a 128-channel tile uses 12 rows (64co x 96px per wave, ~210 VGPRs)
 inline int kc_elems(int dtype) { return dtype == ELVIS_F16 ? 32 : 16; }
+inline int conv_nkc32(const elvis_conv_desc* d) { return (d->cin + 31) / 32 + (d->cin2 > 0 ? (d->cin2 + 31) / 32 : 0); }   // K chunks of 32 channels
 // Planar form of the compensated conv (conv_x3p.inc): 3x3 layers with a 64- / 128-channel output tile.  The PACKING of an ELVIS_F32X3 layer depends on channels and kernel size only (x3_planar_fmt), never on the
 // geometry of a call; a call runs on the planar kernel when its geometry is the plain 3x3 / stride 1 / pad 1 one.
 inline bool x3_planar_fmt(const elvis_conv_desc* d) {
@@ -1544,29 +1577,20 @@ inline bool x3_planar_run(const elvis_conv_desc* d) {
     return d->stride == 1 && d->pad_before == 1 && !d->upsample && d->ho == d->h && d->wo == d->w;
 }
 inline int kc_of(const elvis_conv_desc* d) { return x3_planar_fmt(d) ? 32 : kc_elems(d->dtype); }   // input channels per K chunk
-// two-workgroups-per-CU (256-thread) variant: f16, 3x3 or 2x2, 64- or 128-channel tile, LDS footprint <= 80 KB.  Without
-// the prologue the footprint is at most 70 912 bytes (128-channel 3x3 tile), so the rule always holds; only the
-// prologue's per-chunk table (256 bytes per K chunk) can push a 3x3 conv to the 512-thread kernels.
+// two-workgroups-per-CU (256-thread) variant: f16, 3x3 or 2x2, 64- or 128-channel tile, LDS footprint <= 80 KB.  Only the
+// prologue's per-chunk table (256 bytes per K chunk) can push a 3x3 conv to the 512-thread kernels (static_assert below).
 inline bool halo_two(const elvis_conv_desc* d) {
     const int tco = choose_tile(d->cout).tco, ks = d->ksize;
     if ((ks != 3 && ks != 2) || d->dtype != ELVIS_F16 || tco < 64) return false;
-    int nkc = (d->cin + 31) / 32 + (d->cin2 > 0 ? (d->cin2 + 31) / 32 : 0);
-    size_t lds = (size_t)(halo_ty2(d) + ks - 1) * (HALO_TX + ks - 1) * 64 + 2 * ks * (size_t)tco * 64 + (d->prologue ? (size_t)nkc * 256 : 0);
-    return lds <= 80 * 1024;
+    const int ty = halo_tile_rows(ks, d->prologue != 0, tco, 256, halo_tall(d));
+    return halo_lds_bytes(ks, tco, ty, 256, d->prologue ? conv_nkc32(d) : 0) <= 80 * 1024;
 }
+static_assert(halo_lds_bytes(3, 128, HALO_TY2, 256, 0) == 70912 && halo_lds_bytes(3, 64, HALO_TY2_TALL, 256, 0) <= 80 * 1024,
+              "a conv without the prologue must fit the 256-thread kernel: at most 70 912 bytes (launch_halo relies on it)");
 // 1x1 GEMM path with LDS-DMA staging: f16, whole 32-channel K chunks, 64/128-channel tile
 inline bool halo_g1(const elvis_conv_desc* d) {
     return d->ksize == 1 && d->dtype == ELVIS_F16 && choose_tile(d->cout).tco >= 64 && d->cin % 32 == 0 &&
            d->cin2 % 32 == 0;
-}
-inline int halo_ty(const elvis_conv_desc* d) {
-    if (x3_planar_run(d)) return choose_tile(d->cout).tco == 128 ? 12 : 16;   // conv_x3p.inc X3P_TY128 / X3P_TY64
-    if (halo_two(d)) return halo_ty2(d);
-    if (halo_g1(d)) return choose_tile(d->cout).tco == 128 ? G1_TY128 : G1_TY64;
-    if (d->ksize == 3 && d->prologue && choose_tile(d->cout).tco == 128) return HALO_TY_PRO128;
-    // narrow output tiles (cout <= 32: HBM-bound layers) use the 8-row tile too: 61 KB of LDS and few accumulator
-    // registers, so two 512-thread workgroups share a CU and their load / store phases overlap
-    return (d->prologue || d->ksize == 1 || choose_tile(d->cout).tco <= 32) ? HALO_TY_PRO : HALO_TY;
 }
 
 int validate(const elvis_conv_desc* d) {
@@ -1602,8 +1626,13 @@ int validate(const elvis_conv_desc* d) {
     return ELVIS_OK;
 }
 
+// ---- leaf launchers.  A leaf is the only code that names its instantiation (formatted once, from its own template
+// parameters).  Asked through `query` it reports that name and its tile height and returns before any HIP call (the name
+// query and elvis_conv_stats_tiles run on hosts without a GPU); otherwise it launches and records the name.
 template <typename T, int WCO, int WPX, int NW_CO, int NW_PX>
-int launch(const ConvArgs& a, hipStream_t stream) {
+int launch(const ConvArgs& a, hipStream_t stream, ConvPick* query) {
+    static const ElvisKernelName name("conv_igemm_kernel<%s,%d,%d,%d,%d>", sizeof(T) == 2 ? "half" : "float", WCO, WPX, NW_CO, NW_PX);
+    if (query) return query->set(name.s, 0);
     constexpr int TCO = 16 * WCO * NW_CO, TPX = 16 * WPX * NW_PX;
     size_t lds = 2 * (size_t)(TCO + TPX) * 64;
     long long nblk = (long long)a.n_co_tiles * a.n_px_tiles;
@@ -1611,81 +1640,68 @@ int launch(const ConvArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL((conv_igemm_kernel<T, WCO, WPX, NW_CO, NW_PX>), dim3((unsigned)nblk), dim3(64 * NW_CO * NW_PX),
                        lds, stream, a);
     ELVIS_CHECK_LAUNCH("elvis_conv2d");
+    elvis_note_launch(name.s);
     return ELVIS_OK;
 }
 
-template <typename T, int TCO, bool PRO, int KS, int NT = 512, bool ACT = false, int TY2 = HALO_TY2, bool X3 = false>
-int launch_halo_p(const ConvArgs& a, hipStream_t stream) {
+template <typename T, int TCO, bool PRO, int KS, int NT = 512, bool ACT = false, bool TALL = false, bool X3 = false>
+int launch_halo_p(const ConvArgs& a, hipStream_t stream, ConvPick* query) {
     if constexpr (!ACT) {
-        if (a.act != 0) return launch_halo_p<T, TCO, PRO, KS, NT, true, TY2, X3>(a, stream);
+        if (a.act != 0) return launch_halo_p<T, TCO, PRO, KS, NT, true, TALL, X3>(a, stream, query);
     }
     // fp32 storage with the compensated f16 MFMA: the 512-thread kernels with a 64- / 128-channel tile
     // (narrower layers stay on the exact fp32 MFMA)
     if constexpr (!X3 && sizeof(T) == 4 && NT == 512 && TCO >= 64) {
-        if (a.x3) return launch_halo_p<T, TCO, PRO, KS, NT, ACT, TY2, true>(a, stream);
+        if (a.x3) return launch_halo_p<T, TCO, PRO, KS, NT, ACT, TALL, true>(a, stream, query);
     }
-    constexpr bool TWO = NT == 256;
-    constexpr int TY = (TWO && KS == 1) ? (TCO == 128 ? G1_TY128 : G1_TY64) : TWO ? TY2 : (KS == 3 && PRO && TCO == 128) ? HALO_TY_PRO128 : ((PRO || KS == 1 || TCO <= 32) ? HALO_TY_PRO : HALO_TY);
-    const size_t lds_fixed = (TWO && KS == 1) ? (TCO == 64 ? G1_NST64 : G1_NST128) * ((size_t)TY * HALO_TX * 64 + (size_t)TCO * 64)
-                           : (TWO ? 1 : 2) * (size_t)((TY + KS - 1) * (HALO_TX + KS - 1) * 64) + ((TWO || KS == 2) ? 2 : 3) * KS * (size_t)TCO * 64;
-    const size_t lds = lds_fixed + (PRO ? (size_t)a.nkc * 4 * 2 * DT<T>::VEC * sizeof(float) : 0);
+    constexpr int TY = halo_tile_rows(KS, PRO, TCO, NT, TALL);
+    static const ElvisKernelName name = X3 ? ElvisKernelName("conv3x3_halo_x3_kernel<%d,%d,%s,%d,%s>", TCO, TY, tf(PRO), KS, tf(ACT))
+                                    : ElvisKernelName("conv3x3_halo_kernel<%s,%d,%d,%d,%s,%d,%s>", sizeof(T) == 2 ? "half" : "float", TCO, NT, TY, tf(PRO), KS, tf(ACT));
+    if (query) return query->set(name.s, TY);
+    const void* fn = nullptr;
+    if constexpr (X3) fn = (const void*)conv3x3_halo_x3_kernel<TCO, TY, PRO, KS, ACT>;
+    else fn = (const void*)conv3x3_halo_kernel<T, TCO, NT, TY, PRO, KS, ACT>;
+    const size_t lds = halo_lds_bytes(KS, TCO, TY, NT, PRO ? a.nkc : 0, 4 * DT<T>::VEC);
     ELVIS_REQUIRE(lds <= 160 * 1024, "conv3x3_halo: %zu bytes of LDS needed (too many input channels)", lds);
-    {   // the 160 KB opt-in is a per-device function attribute: set it once per (instantiation, device),
-        // under a lock - P2 calls this from pool threads, one per device (elvis.py:342-346)
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        std::lock_guard<std::mutex> guard(mu);
-        if (!attr_set[dev]) {
-            const void* fn = nullptr;
-            if constexpr (X3) fn = (const void*)conv3x3_halo_x3_kernel<TCO, TY, PRO, KS, ACT>;
-            else fn = (const void*)conv3x3_halo_kernel<T, TCO, NT, TY, PRO, KS, ACT>;
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) {
-                elvis_set_error("conv3x3_halo: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-                return ELVIS_E_RUNTIME;
-            }
-            attr_set[dev] = true;
-        }
-    }
+    static ElvisLdsOptIn opt_in;
+    if (int rc = elvis_lds_opt_in(fn, opt_in, elvis_device_slot(), "conv3x3_halo: cannot reserve %zu bytes of LDS", lds)) return rc;
     long long nblk = (long long)a.n_co_tiles * a.tiles_x * a.tiles_y * a.n;
     ELVIS_REQUIRE(nblk < 0x7fffffffLL, "conv: grid too large");
     if constexpr (X3) hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TCO, TY, PRO, KS, ACT>), dim3((unsigned)nblk), dim3(NT), lds, stream, a);
     else hipLaunchKernelGGL((conv3x3_halo_kernel<T, TCO, NT, TY, PRO, KS, ACT>), dim3((unsigned)nblk), dim3(NT), lds, stream, a);
     ELVIS_CHECK_LAUNCH("elvis_conv2d(halo)");
+    elvis_note_launch(name.s);
     return ELVIS_OK;
 }
 
-template <typename T, int TCO> int launch_halo(const ConvArgs& a, hipStream_t stream) {
+template <typename T, int TCO> int launch_halo(const ConvArgs& a, hipStream_t stream, ConvPick* query) {
     if constexpr (TCO >= 64 && sizeof(T) == 2) {
-        if (a.two && a.ksize == 1) return launch_halo_p<T, TCO, false, 1, 256>(a, stream);
+        if (a.two && a.ksize == 1) return launch_halo_p<T, TCO, false, 1, 256>(a, stream, query);
     }
-    if (a.ksize == 1) return launch_halo_p<T, TCO, false, 1>(a, stream);
+    if (a.ksize == 1) return launch_halo_p<T, TCO, false, 1>(a, stream, query);
     if constexpr (TCO >= 64 && sizeof(T) == 2) {
-        if (a.two && a.ksize == 2) return launch_halo_p<T, TCO, false, 2, 256>(a, stream);
+        if (a.two && a.ksize == 2) return launch_halo_p<T, TCO, false, 2, 256>(a, stream, query);
         if constexpr (TCO == 64) {
             if (a.two && a.tall && a.ksize == 3)
-                return a.prologue ? launch_halo_p<T, TCO, true, 3, 256, false, HALO_TY2_TALL>(a, stream)
-                                  : launch_halo_p<T, TCO, false, 3, 256, false, HALO_TY2_TALL>(a, stream);
+                return a.prologue ? launch_halo_p<T, TCO, true, 3, 256, false, true>(a, stream, query)
+                                  : launch_halo_p<T, TCO, false, 3, 256, false, true>(a, stream, query);
         }
-        if (a.two) return a.prologue ? launch_halo_p<T, TCO, true, 3, 256>(a, stream) : launch_halo_p<T, TCO, false, 3, 256>(a, stream);
-        // halo_two() holds for every f16 2x2 / 3x3 conv without the prologue (its LDS formula gives at most 70 912 of the
-        // 81 920 bytes, for the 128-channel 3x3 tile): only the prologue's per-chunk table can push a conv past it
+        if (a.two) return a.prologue ? launch_halo_p<T, TCO, true, 3, 256>(a, stream, query) : launch_halo_p<T, TCO, false, 3, 256>(a, stream, query);
+        // halo_two() holds for every f16 2x2 / 3x3 conv without the prologue (the static_assert beside it)
         ELVIS_REQUIRE(a.ksize == 3 && a.prologue, "conv3x3_halo: a conv without the prologue must fit the 256-thread kernel");
-        return launch_halo_p<T, TCO, true, 3>(a, stream);
+        return launch_halo_p<T, TCO, true, 3>(a, stream, query);
     } else {
-        if (a.ksize == 2) return launch_halo_p<T, TCO, false, 2>(a, stream);
-        return a.prologue ? launch_halo_p<T, TCO, true, 3>(a, stream) : launch_halo_p<T, TCO, false, 3>(a, stream);
+        if (a.ksize == 2) return launch_halo_p<T, TCO, false, 2>(a, stream, query);
+        return a.prologue ? launch_halo_p<T, TCO, true, 3>(a, stream, query) : launch_halo_p<T, TCO, false, 3>(a, stream, query);
     }
 }
 
-template <typename T> int dispatch(const ConvArgs& a, int id, hipStream_t stream) {
+template <typename T> int dispatch(const ConvArgs& a, int id, hipStream_t stream, ConvPick* query) {
     switch (id) {
-        case 0: return launch<T, 4, 4, 2, 2>(a, stream);
-        case 1: return launch<T, 4, 2, 1, 4>(a, stream);   // 64 cout per wave, like the halo kernels (shared weight permutation)
-        case 2: return launch<T, 2, 4, 1, 4>(a, stream);
-        default: return launch<T, 1, 4, 1, 4>(a, stream);
+        case 0: return launch<T, 4, 4, 2, 2>(a, stream, query);
+        case 1: return launch<T, 4, 2, 1, 4>(a, stream, query);   // 64 cout per wave, like the halo kernels (shared weight permutation)
+        case 2: return launch<T, 2, 4, 1, 4>(a, stream, query);
+        default: return launch<T, 1, 4, 1, 4>(a, stream, query);
     }
 }
 

@@ -19,6 +19,7 @@
 // Packed weights, fragment layouts, the row permutation that gives a lane contiguous output channels: conv_kernels.inc.
 #pragma once
 #include "conv_kernels.inc"
+#include <atomic>
 
 namespace {
 
@@ -251,56 +252,53 @@ inline bool ws_shape_ok(const elvis_conv_desc* d) {
     if (d->dtype != ELVIS_F16 || d->ksize != 3 || d->stride != 1 || d->pad_before != 1 || d->upsample || d->prologue) return false;
     if (d->ho != d->h || d->wo != d->w || (d->act != 0 && d->act != 3)) return false;
     if (choose_tile(d->cout).tco > 64) return false;
-    const int nkc = (d->cin + 31) / 32 + (d->cin2 > 0 ? (d->cin2 + 31) / 32 : 0);
-    if (nkc > 2 || (d->cin_pitch & 7) || (d->cin2 > 0 && (d->cin2_pitch & 7)) || (d->cout_pitch & 7)) return false;
+    if (conv_nkc32(d) > 2 || (d->cin_pitch & 7) || (d->cin2 > 0 && (d->cin2_pitch & 7)) || (d->cout_pitch & 7)) return false;
     return (long long)d->ho * d->wo >= 128 * 1024;   // per image (never per batch: the kernel choice must not depend on n)
 }
 
 // the halves run half an iteration apart where measured faster: two K chunks x a 64-channel tile
 constexpr bool ws_stagger(int nkc, int tco) { return nkc == 2 && tco == 64; }
+constexpr int WS_TY = 8;   // the host sizes the grid for 8 x HALO_TX pixel tiles, the TY x TX of the kernel
 
-template <int NKC, int TCO> int launch_ws(const ConvArgs& a, hipStream_t stream) {
+template <int NKC, int TCO> int launch_ws(const ConvArgs& a, hipStream_t stream, ConvPick* query) {
     constexpr bool STAG = ws_stagger(NKC, TCO);
+    static const ElvisKernelName name("conv3x3_ws_kernel<%d,%d,%s>", NKC, TCO, tf(STAG));
+    if (query) return query->set(name.s, WS_TY);
     constexpr size_t lds = (size_t)NKC * 9 * TCO * 64 + 2 * (size_t)NKC * 340 * 64;
-    static std::mutex mu;
-    static bool attr_set[64] = {};
-    static int ncu[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    {
-        std::lock_guard<std::mutex> guard(mu);
-        if (!attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)conv3x3_ws_kernel<NKC, TCO, STAG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            int n = 0;
-            if (e == hipSuccess) e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            if (e != hipSuccess || n <= 0) {
-                elvis_set_error("conv3x3_ws: device setup failed: %s", hipGetErrorString(e));
-                return ELVIS_E_RUNTIME;
-            }
-            ncu[dev] = n;
-            attr_set[dev] = true;
+    static ElvisLdsOptIn opt_in;
+    static std::atomic<int> ncu[64];   // compute units per device: every thread that asks first stores the same value
+    const int dev = elvis_device_slot();
+    if (int rc = elvis_lds_opt_in((const void*)conv3x3_ws_kernel<NKC, TCO, STAG>, opt_in, dev, "conv3x3_ws: device setup failed")) return rc;
+    int n_cu = ncu[dev].load(std::memory_order_relaxed);
+    if (n_cu == 0) {
+        hipError_t e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess || n_cu <= 0) {
+            elvis_set_error("conv3x3_ws: device setup failed: %s", hipGetErrorString(e));
+            return ELVIS_E_RUNTIME;
         }
+        ncu[dev].store(n_cu, std::memory_order_relaxed);
     }
     const long long ntiles = (long long)a.n * a.tiles_y * a.tiles_x;
     ELVIS_REQUIRE(ntiles < 0x3fffffffLL, "conv: grid too large");
-    int nworkers = ncu[dev] / a.n_co_tiles;
+    int nworkers = n_cu / a.n_co_tiles;
     const long long npairs = (ntiles + 1) / 2;
     if (nworkers > npairs) nworkers = (int)npairs;
     ELVIS_REQUIRE(nworkers >= 1, "conv3x3_ws: more cout tiles than compute units");
     hipLaunchKernelGGL((conv3x3_ws_kernel<NKC, TCO, STAG>), dim3((unsigned)(nworkers * a.n_co_tiles)), dim3(512), lds, stream, a, (int)ntiles, nworkers);
     ELVIS_CHECK_LAUNCH("elvis_conv2d(ws)");
+    elvis_note_launch(name.s);
     return ELVIS_OK;
 }
 
-inline int dispatch_ws(const ConvArgs& a, int tco, hipStream_t stream) {
+inline int dispatch_ws(const ConvArgs& a, int tco, hipStream_t stream, ConvPick* query) {
     if (a.nkc == 1) {
-        if (tco == 64) return launch_ws<1, 64>(a, stream);
-        if (tco == 32) return launch_ws<1, 32>(a, stream);
-        return launch_ws<1, 16>(a, stream);
+        if (tco == 64) return launch_ws<1, 64>(a, stream, query);
+        if (tco == 32) return launch_ws<1, 32>(a, stream, query);
+        return launch_ws<1, 16>(a, stream, query);
     }
-    if (tco == 64) return launch_ws<2, 64>(a, stream);
-    if (tco == 32) return launch_ws<2, 32>(a, stream);
-    return launch_ws<2, 16>(a, stream);
+    if (tco == 64) return launch_ws<2, 64>(a, stream, query);
+    if (tco == 32) return launch_ws<2, 32>(a, stream, query);
+    return launch_ws<2, 16>(a, stream, query);
 }
 
 }  // namespace

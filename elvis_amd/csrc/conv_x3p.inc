@@ -461,8 +461,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_x3p_kernel(ConvArgs p) {
     }
 }
 
-constexpr int X3P_TY128 = 12, X3P_TY64 = 16;
-
 // packed weights of the planar form: OIHW f32 -> [tap][kc][cout tile][plane][TCO][32] halfs, rows permuted inside each
 // wave's 64-channel group like every other packing (pack_weights_kernel): a lane owns 16 contiguous output channels
 __global__ void pack_weights_x3p_kernel(const float* __restrict__ w, half_t* __restrict__ out, int cout, int ctot, int nkc,
@@ -486,35 +484,26 @@ __global__ void pack_weights_x3p_kernel(const float* __restrict__ w, half_t* __r
     out[i] = plane ? (half_t)(v - (float)h) : h;
 }
 
-template <int TCO, int KS, bool PRO, bool ACT> int launch_x3p_a(const ConvArgs& a, hipStream_t stream) {
-    constexpr int TY = TCO == 128 ? X3P_TY128 : X3P_TY64;
-    const size_t lds = (size_t)2 * (TY + KS - 1) * (32 + KS - 1) * 64 + 2 * KS * 2 * (size_t)TCO * 64 + (PRO ? 256 : 0);
-    {
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        std::lock_guard<std::mutex> guard(mu);
-        if (!attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)conv3x3_x3p_kernel<TCO, TY, KS, PRO, ACT>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) {
-                elvis_set_error("conv3x3_x3p: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-                return ELVIS_E_RUNTIME;
-            }
-            attr_set[dev] = true;
-        }
-    }
+template <int TCO, int KS, bool PRO, bool ACT> int launch_x3p_a(const ConvArgs& a, hipStream_t stream, ConvPick* query) {
+    constexpr int TY = x3p_tile_rows(TCO);
+    static const ElvisKernelName name("conv3x3_x3p_kernel<%d,%d,%d,%s,%s>", TCO, TY, KS, tf(PRO), tf(ACT));
+    if (query) return query->set(name.s, TY);
+    constexpr size_t lds = 2 * halo_tile_bytes(TY, KS) + 2 * KS * 2 * (size_t)TCO * 64 + (PRO ? 256 : 0);
+    static ElvisLdsOptIn opt_in;
+    if (int rc = elvis_lds_opt_in((const void*)conv3x3_x3p_kernel<TCO, TY, KS, PRO, ACT>, opt_in, elvis_device_slot(),
+                                  "conv3x3_x3p: cannot reserve %zu bytes of LDS", lds))
+        return rc;
     const long long nblk = (long long)a.n_co_tiles * a.tiles_x * a.tiles_y * a.n;
     ELVIS_REQUIRE(nblk < 0x7fffffffLL, "conv: grid too large");
     hipLaunchKernelGGL((conv3x3_x3p_kernel<TCO, TY, KS, PRO, ACT>), dim3((unsigned)nblk), dim3(512), lds, stream, a);
     ELVIS_CHECK_LAUNCH("elvis_conv2d(x3p)");
+    elvis_note_launch(name.s);
     return ELVIS_OK;
 }
-template <int TCO> int launch_x3p(const ConvArgs& a, hipStream_t stream) {
-    if (a.ksize == 2) return a.act != 0 ? launch_x3p_a<TCO, 2, false, true>(a, stream) : launch_x3p_a<TCO, 2, false, false>(a, stream);
-    if (a.act != 0) return a.prologue ? launch_x3p_a<TCO, 3, true, true>(a, stream) : launch_x3p_a<TCO, 3, false, true>(a, stream);
-    return a.prologue ? launch_x3p_a<TCO, 3, true, false>(a, stream) : launch_x3p_a<TCO, 3, false, false>(a, stream);
+template <int TCO> int launch_x3p(const ConvArgs& a, hipStream_t stream, ConvPick* query) {
+    if (a.ksize == 2) return a.act != 0 ? launch_x3p_a<TCO, 2, false, true>(a, stream, query) : launch_x3p_a<TCO, 2, false, false>(a, stream, query);
+    if (a.act != 0) return a.prologue ? launch_x3p_a<TCO, 3, true, true>(a, stream, query) : launch_x3p_a<TCO, 3, false, true>(a, stream, query);
+    return a.prologue ? launch_x3p_a<TCO, 3, true, false>(a, stream, query) : launch_x3p_a<TCO, 3, false, false>(a, stream, query);
 }
 
 }  // namespace

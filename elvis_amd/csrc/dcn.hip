@@ -20,7 +20,6 @@
 //  * dcnv2_kernel (any dtype / grouping): the generic scalar form - the fp32 exact mode and odd shapes.
 #include "common.h"
 #include <type_traits>
-#include <mutex>
 
 namespace {
 
@@ -358,23 +357,10 @@ extern "C" int elvis_dcnv2(const void* x, const void* offset_mask, const void* w
         const int ksteps = (K + 31) / 32;
         const int tiles_x = (w + TX_ - 1) / TX_, tiles_y = (h + TY_ - 1) / TY_;
         const size_t lds2 = XIN_BYTES + (size_t)ksteps * IMG_BYTES * 5;
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        {
-            std::lock_guard<std::mutex> guard(mu);
-            if (!attr_set[dev]) {
-                hipError_t e = hipFuncSetAttribute((const void*)dcnv2_tile_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute((const void*)dcnv2_tile_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) {
-                    elvis_set_error("elvis_dcnv2: cannot reserve LDS: %s", hipGetErrorString(e));
-                    return ELVIS_E_RUNTIME;
-                }
-                attr_set[dev] = true;
-            }
-        }
+        static ElvisLdsOptIn opt_in[2];   // per instantiation: cin 7, cin 8
+        if (int rc = elvis_lds_opt_in(cin == 7 ? (const void*)dcnv2_tile_kernel<7> : (const void*)dcnv2_tile_kernel<8>, opt_in[cin - 7],
+                                      elvis_device_slot(), "elvis_dcnv2: cannot reserve LDS"))
+            return rc;
         ELVIS_REQUIRE((long long)n * tiles_x * tiles_y < 0x7fffffffLL, "elvis_dcnv2: grid too large");
         if (cin == 7)
             hipLaunchKernelGGL(dcnv2_tile_kernel<7>, dim3((unsigned)(n * tiles_x * tiles_y)), dim3(256), lds2, (hipStream_t)stream,

@@ -22,7 +22,6 @@
 // The MLP is paced by the GELU's VALU (16 instructions per hidden value) rather than by its MFMAs or by HBM; waves 4-7 run
 // half a chunk behind waves 0-3 so that one SIMD partner's GELU overlaps the other's matrix part.
 #include "common.h"
-#include <mutex>
 
 namespace {
 
@@ -412,32 +411,17 @@ __global__ __launch_bounds__(512, 2) void swin_fused_kernel(SwinArgs p) {
 template <int C, int PXT, int MODE, bool STAG> int launch_swin(const SwinArgs& a, hipStream_t stream) {
     constexpr int STAGE = (C / 32) * 4096 + (MODE >= 1 ? 2 * C * 64 : 0);
     const size_t lds = 2 * (size_t)STAGE;
-    {
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        std::lock_guard<std::mutex> guard(mu);
-        if (!attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)swin_fused_kernel<C, PXT, MODE, STAG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) {
-                elvis_set_error("elvis_swin: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-                return ELVIS_E_RUNTIME;
-            }
-            attr_set[dev] = true;
-        }
-    }
+    static ElvisLdsOptIn opt_in;
+    if (int rc = elvis_lds_opt_in((const void*)swin_fused_kernel<C, PXT, MODE, STAG>, opt_in, elvis_device_slot(),
+                                  "elvis_swin: cannot reserve %zu bytes of LDS", lds))
+        return rc;
     const long long per = 128LL * PXT;
     const long long blocks = (a.M + per - 1) / per;
     ELVIS_REQUIRE(blocks < 0x7fffffffLL, "elvis_swin: grid too large");
     hipLaunchKernelGGL((swin_fused_kernel<C, PXT, MODE, STAG>), dim3((unsigned)blocks), dim3(512), lds, stream, a);
     ELVIS_CHECK_LAUNCH("elvis_swin");
-    static const char* const name = [] {   // formatted once per instantiation, static storage (elvis_last_launch)
-        static char b[48];
-        snprintf(b, sizeof(b), "swin_fused_kernel<%d,%d,%d,%s>", C, PXT, MODE, STAG ? "true" : "false");
-        return (const char*)b;
-    }();
-    elvis_note_launch(name);
+    static const ElvisKernelName name("swin_fused_kernel<%d,%d,%d,%s>", C, PXT, MODE, STAG ? "true" : "false");
+    elvis_note_launch(name.s);
     return ELVIS_OK;
 }
 

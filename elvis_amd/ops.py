@@ -325,7 +325,7 @@ class _Timed:
 def conv_kernel_name(d, residual: bool = False, stats: bool = False) -> str:
     """Name of the kernel instantiation `elvis_conv2d` dispatches descriptor `d` to, for a call with (or without) a
     residual and a statistics buffer - the template name rocprofv3's kernel trace shows (queried from the library:
-    conv.hip conv_path, the rule elvis_conv2d dispatches by)."""
+    the walk down elvis_conv2d's own launch tree, answered by the leaf launcher that would run)."""
     buf = C.create_string_buffer(128)
     check(lib().elvis_conv_kernel_name_for_call(C.byref(d), int(bool(residual)), int(bool(stats)), buf, len(buf)), None)
     return buf.value.decode()

@@ -1,6 +1,7 @@
 """CPU-side checks of the conv test matrix (tests/_convref.py, tests/test_gpu_conv_matrix.py): the dispatch
 ledger (every conv kernel instantiation in the built library is reached by a matrix case),
-the name query against the dispatch rule, and a mutation self-test of the tier-1 / tier-2 / statistics checks."""
+the name query against the dispatch rule, the statistics grid against the tile height in the resolved kernel's name,
+and a mutation self-test of the tier-1 / tier-2 / statistics checks."""
 import ctypes as C
 import math
 
@@ -72,6 +73,23 @@ def test_name_query_follows_call_flags(built_lib):
               R.Case(id="d", expect="", cin=32, cout=32, h=8, w=8, kind="up")):
         for d, _, _ in R.descs(c):
             assert _name(d, 1, 1) == _name(d, 0, 0) == ops.conv_kernel_name(d)
+
+
+def test_stats_grid_follows_the_named_kernels_tile_height(built_lib):
+    """elvis_conv_stats_tiles sizes the statistics grid with the tile height in the launched kernel's own name."""
+    from elvis_amd._lib import lib
+    halo = ("conv3x3_halo_kernel", "conv3x3_halo_x3_kernel", "conv3x3_x3p_kernel")
+    checked = 0
+    for c in R.CASES:
+        for (d, _, _), name in zip(R.descs(c), R.resolve(c)):
+            if not name.startswith(tuple(h + "<" for h in halo)):
+                continue
+            parity = d.ksize == 2 and d.subpixel != 5   # the sub-pixel parity form: one launch per parity, low-res grid
+            rows, cols = (d.h, d.w) if parity else (d.ho, d.wo)
+            want = d.n * math.ceil(rows / R.kernel_ty(name)) * math.ceil(cols / 32)
+            assert lib().elvis_conv_stats_tiles(C.byref(d)) == want, f"{c.id}: {name}"
+            checked += 1
+    assert checked >= 50
 
 
 # ------------------------------------------------------------------------------------------ mutation self-test

@@ -2,7 +2,9 @@
 tests/_convref.py: tier 1 on every element, tier 2 on >= 99.8 % of each f16 case, the per-tile fused
 GroupNorm partials, and the [cout, pitch) pad channels of an output pre-filled with NaN.  Each case
 asserts, before it runs, the instantiation it must reach (the library's name query for the call's real
-residual / statistics flags) and, after, that ops reported the same name for the launch."""
+residual / statistics flags) and, after, that ops reported the same name for the launch and that the leaf launcher
+which really ran recorded it too (elvis_last_launch: the name query walks the launch tree without launching, this is
+the launch itself)."""
 import math
 
 import pytest
@@ -31,8 +33,10 @@ def _nan_new_act(orig):
 
 
 def _run(case, dev):
-    """Runs the case on the GPU; returns (y_stored NCHW float64, pads, stats or None, Ref, kernel names ops reported)."""
+    """Runs the case on the GPU; returns (y_stored NCHW float64, pads, stats or None, Ref, kernel names ops reported,
+    the kernel the last conv call launched)."""
     from elvis_amd import ops
+    from elvis_amd._lib import lib
     c = case
     g = torch.Generator().manual_seed(1000 + c.seed)
     dtype = torch.float16 if c.dt == "f16" else torch.float32
@@ -100,6 +104,7 @@ def _run(case, dev):
                 y = down(xa, want_stats=c.stats, act=c.act)
             finally:
                 ops.new_act = orig
+        last = lib().elvis_last_launch().decode()   # read once after the op: an up-conv's four calls reach one instantiation
         torch.cuda.synchronize()
         names = [e[0] for e in names_ev]
     finally:
@@ -108,7 +113,7 @@ def _run(case, dev):
     yn = t[..., :c.cout].permute(0, 3, 1, 2).contiguous()
     pads = t[..., c.cout:]
     st = y.stats.cpu() if y.stats is not None else None
-    return yn, pads, st, r, names
+    return yn, pads, st, r, names, last
 
 
 @pytest.mark.parametrize("case", R.CASES, ids=[c.id for c in R.CASES])
@@ -116,8 +121,9 @@ def test_conv_matrix(gpu_device, case):
     # the instantiation the case exists for, asserted before anything runs
     got_names = R.resolve(case)
     assert set(got_names) == {case.expect}, f"{case.id}: resolves to {got_names}, expected {case.expect}"
-    y, pads, st, r, launched = _run(case, gpu_device)
+    y, pads, st, r, launched, last = _run(case, gpu_device)
     assert launched and set(launched) == {case.expect}, f"ops reported {launched}"
+    assert last == case.expect, f"{case.id}: launched {last}"
     assert y.shape == r.z.shape
     ok1, worst, at = R.tier1(y, r)
     line = f"{case.id}: {case.expect} tier1 worst {worst:.3f}"
