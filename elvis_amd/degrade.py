@@ -47,11 +47,21 @@ def _maps(levels_d: torch.Tensor, n: int) -> torch.Tensor:
     return levels_d.contiguous()
 
 
+def _out_for(frames_d: torch.Tensor, out) -> torch.Tensor:
+    """`out` goes to the kernel as a bare pointer: it must be the frames' twin (shape, uint8, device, contiguous)."""
+    if out is None:
+        return torch.empty_like(frames_d)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != frames_d.device \
+            or out.shape != frames_d.shape:
+        raise ValueError("degrade: out must be a contiguous uint8 tensor of the frames' shape on the frames' device")
+    return out
+
+
 def degrade_downsample_device(frames_d: torch.Tensor, levels_d: torch.Tensor, block_size: int, out=None) -> torch.Tensor:
     _chk_u8(frames_d)
     n, h, w, c = frames_d.shape
     m = _maps(levels_d, n)
-    out = torch.empty_like(frames_d) if out is None else out
+    out = _out_for(frames_d, out)
     check(lib().elvis_degrade_downsample_u8(ptr(frames_d), ptr(m), ptr(out), n, h, w, c, block_size, m.shape[1], m.shape[2],
                                             _s(frames_d)), frames_d.device)
     return out
@@ -61,7 +71,7 @@ def degrade_gaussian_device(frames_d: torch.Tensor, rounds_d: torch.Tensor, bloc
     _chk_u8(frames_d)
     n, h, w, c = frames_d.shape
     m = _maps(rounds_d, n)
-    out = torch.empty_like(frames_d) if out is None else out
+    out = _out_for(frames_d, out)
     k0, k1, k2 = gaussian_taps()
     check(lib().elvis_degrade_gaussian_u8(ptr(frames_d), ptr(m), ptr(out), n, h, w, c, block_size, m.shape[1], m.shape[2],
                                           k0, k1, k2, _s(frames_d)), frames_d.device)
@@ -73,7 +83,7 @@ def degrade_dct_device(frames_d: torch.Tensor, levels_d: torch.Tensor, out=None)
     n, h, w, c = frames_d.shape
     m = _maps(levels_d, n)
     basis, gain = _dct_tables(frames_d.device)
-    out = torch.empty_like(frames_d) if out is None else out
+    out = _out_for(frames_d, out)
     check(lib().elvis_degrade_dct_u8(ptr(frames_d), ptr(m), ptr(out), ptr(basis), ptr(gain), DCT_LEVELS, n, h, w, c,
                                      m.shape[1], m.shape[2], _s(frames_d)), frames_d.device)
     return out

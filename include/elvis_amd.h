@@ -305,25 +305,31 @@ int elvis_convert_act(const void* x, int src_dtype, void* y, int dst_dtype, long
  * blocks); map[n, by, bx] int32 with by = H / block_size, bx = W / block_size (H, W divisible by block_size). */
 
 /* filter_frame_downsample (elvis.py:2141-2169): per block, INTER_AREA downscale by 2**level then INTER_LINEAR
- * back to block_size (OpenCV's u8 fixed-point rules restated; block_size a power of two <= 16). */
+ * back to block_size (OpenCV's u8 fixed-point rules restated; block_size a power of two <= 16).  Levels are clamped
+ * to [0, 4] (a negative level copies the block; the factor is at most 16); a factor above block_size averages the
+ * whole block (s = max(1, block_size >> level)). */
 int elvis_degrade_downsample_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, int n, int h, int w, int c,
                                 int block_size, int by, int bx, elvis_stream_t stream);
 
 /* filter_frame_gaussian (elvis.py:2171-2196): per block, `rounds` passes of a separable 5-tap Gaussian with the
  * symmetric taps (tap0, tap1, tap2, tap1, tap0), BORDER_REFLECT_101 at the block's own edges, float32
- * arithmetic, round-half-even to uint8 after every pass pair (block_size <= 16). */
+ * arithmetic, round-half-even to uint8 after every pass pair (any block_size in [1, 16]).  `rounds` is clamped to
+ * [0, 32] (a negative count copies the block). */
 int elvis_degrade_gaussian_u8(const uint8_t* src, const int32_t* rounds, uint8_t* dst, int n, int h, int w, int c,
                               int block_size, int by, int bx, float tap0, float tap1, float tap2, elvis_stream_t stream);
 
 /* DCT-coefficient dampening (the build's definition of ELVIS v2 DCT's degrade; README.md:44 names it, the reference
  * holds no code): 8x8 blocks; basis64 = f32[8][8] DCT-II basis, gain = f32[n_levels][8][8] per-level coefficient
- * gains (both device pointers), level clamped to [0, n_levels). */
+ * gains (both device pointers), level clamped to [0, n_levels) (a negative level copies the block, a level of
+ * n_levels or more takes the gains of n_levels - 1). */
 int elvis_degrade_dct_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, const float* basis64, const float* gain,
                          int n_levels, int n, int h, int w, int c, int by, int bx, elvis_stream_t stream);
 
 /* ------------------------------------------------------------------ classical restorers
  * The OpenCV baselines of ELVIS and Presley, per block of a uint8 NHWC frame; map[n, by, bx] int32 with
- * by = H / block_size, bx = W / block_size (floor: pixels past the last whole block are not written).
+ * by = H / block_size, bx = W / block_size (floor).  PIXELS OUTSIDE THE BLOCK GRID (the rows and columns past the last
+ * whole block) are never written: dst keeps there what the caller put (the Python layer starts from a copy of src);
+ * they are read, as halo, by the unsharp mask of a neighbouring block.
  * block_size is a power of two in [2, 32], 1 <= C <= 4.  OpenCV's 8-bit fixed-point rules are restated
  * (parity with cv2 unpinned); the tap tables are device pointers built by elvis_amd/classical.py. */
 
@@ -331,7 +337,8 @@ int elvis_degrade_dct_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst
 
 /* restore_downsample_opencv_lanczos (elvis.py:2773-2820): a block of level L > 0 is INTER_AREA-downscaled to
  * s = max(1, block_size >> L) and INTER_LANCZOS4-resized back; level 0 is copied.  Levels are clamped to
- * [0, ELVIS_CLASSICAL_MAX_LEVEL] (the Python layer rejects larger ones).  taps = int16[5][32][8]: the 11-bit
+ * [0, ELVIS_CLASSICAL_MAX_LEVEL] (a negative level copies the block; the Python layer rejects larger ones; every
+ * level above log2(block_size) gives s = 1, so the upper clamp changes no output).  taps = int16[5][32][8]: the 11-bit
  * Lanczos taps of destination index d for the factor 2^(i+1). */
 int elvis_classical_lanczos_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, int n, int h, int w, int c,
                                int block_size, int by, int bx, const int16_t* taps, elvis_stream_t stream);
@@ -341,7 +348,8 @@ int elvis_classical_lanczos_u8(const uint8_t* src, const int32_t* levels, uint8_
  * addWeighted(tile, 1 + L/2, blurred, -L/2, 0) on its tile - the block grown by `halo` (0..32) pixels and
  * clipped at the frame; only the block is written.  taps = int16 8-bit Gaussian taps of level L at
  * taps[tap_offsets[L] ...], 6L+1 of them, for L in [1, max_level]; levels are clamped to [0, max_level]
- * (max_level <= ELVIS_CLASSICAL_MAX_LEVEL; the Python layer rejects larger ones). */
+ * (a negative level copies the block, a larger one is sharpened as max_level; max_level <=
+ * ELVIS_CLASSICAL_MAX_LEVEL; the Python layer rejects larger ones). */
 int elvis_classical_unsharp_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, int n, int h, int w, int c,
                                int block_size, int by, int bx, int halo, const int16_t* taps, const int32_t* tap_offsets,
                                int max_level, elvis_stream_t stream);

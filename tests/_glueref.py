@@ -433,16 +433,17 @@ def ssim_pair(content: str, n, h, w, c, seed: int):
 
 
 # ============================================================================================ kernel names
-def glue_kernel_stems(source_path: str):
-    """The __global__ functions of glue.hip, from its text."""
+def kernel_stems(source_path: str):
+    """The __global__ functions of a .hip source file, from its text."""
     text = open(source_path).read()
     return set(re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", text))
 
 
-def demangle_glue(sym: str, stems) -> Optional[str]:
+def demangle_kernel(sym: str, stems) -> Optional[str]:
     """`_Z19recompose_u8_kernelILb1EEvPKh...` -> `recompose_u8_kernel<true>`, `_Z15blend_u8_kernelPKh...` ->
-    `blend_u8_kernel`; None for everything that is not a kernel of glue.hip (the host stubs included)."""
-    t = re.match(r"_Z(\d+)", sym)
+    `blend_u8_kernel`, `_ZN12_GLOBAL__N_120stretch_index_kernelEPKhPiiiiii` (a kernel of an unnamed namespace) ->
+    `stretch_index_kernel`; None for everything that is not one of `stems` (the host stubs included)."""
+    t = re.match(r"_Z(?:N12_GLOBAL__N_1)?(\d+)", sym)
     if not t:
         return None
     ln, pos = int(t.group(1)), t.end()
@@ -453,9 +454,13 @@ def demangle_glue(sym: str, stems) -> Optional[str]:
     return f"{name}<{'true' if b.group(1) == '1' else 'false'}>" if b else name
 
 
-def glue_kernel_symbols(lib_path: str, source_path: str):
-    stems = glue_kernel_stems(source_path)
-    return {nm for nm in (demangle_glue(s, stems) for s in elf_symbols(lib_path)) if nm is not None}
+def kernel_symbols(lib_path: str, source_path: str):
+    """The kernels of one source file that the built library holds."""
+    stems = kernel_stems(source_path)
+    return {nm for nm in (demangle_kernel(s, stems) for s in elf_symbols(lib_path)) if nm is not None}
+
+
+glue_kernel_stems, demangle_glue, glue_kernel_symbols = kernel_stems, demangle_kernel, kernel_symbols
 
 
 # ============================================================================================ cases
