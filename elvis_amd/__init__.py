@@ -14,7 +14,9 @@ from .tiler import (adaptive_restore, blended_restoration, resource_aware_restor
                     _extract_tile_with_halo, extract_tile_with_halo)
 from .frameio import (clear_directory, decode_strength_maps_from_npz, encode_strength_maps_to_npz,  # noqa: F401
                       get_frame_paths, load_block_masks, load_frame, load_strength_maps, save_block_masks, save_frame, save_mask)
-from .degrade import filter_frame_dct, filter_frame_downsample, filter_frame_gaussian  # noqa: F401
+from .degrade import (blur_block, degrade_adaptive_blur, degrade_adaptive_downsample, degrade_frame,  # noqa: F401
+                      degrade_gaussian_fx_device, degrade_scale_device, degrade_video_adaptive, downscale_block,
+                      filter_frame_dct, filter_frame_downsample, filter_frame_gaussian, generate_degradation_map)
 from .classical import (lanczos_restore_device, restore_blur_opencv_unsharp_mask,  # noqa: F401
                         restore_downsample_opencv_lanczos, restore_with_opencv_lanczos, restore_with_opencv_unsharp,
                         temporal_blend_device, unsharp_restore_device)

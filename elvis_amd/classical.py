@@ -73,11 +73,14 @@ def lanczos_tap_table() -> np.ndarray:
     return np.stack([lanczos_taps(f, LANCZOS_PHASES)[1] for f in LANCZOS_FACTORS])
 
 
-def gaussian_taps_u8(level: int) -> np.ndarray:
-    """cv::GaussianBlur's CV_8U taps for sigma = level (ksize = cvRound(6 sigma + 1) | 1 = 6L + 1):
-    getGaussianKernelBitExact, then error diffusion to 8 fractional bits; int16, symmetric, sum 256."""
-    n = 6 * level + 1
-    scale2 = -0.125 / (float(level) * float(level))
+def gaussian_taps_u8(sigma: float, ksize: int = 0) -> np.ndarray:
+    """cv::GaussianBlur's CV_8U taps for `sigma` and an odd `ksize` (0: cvRound(6 sigma + 1) | 1, which is 6L + 1 for
+    the unsharp mask's sigma = L): getGaussianKernelBitExact, then error diffusion to 8 fractional bits; int16,
+    symmetric, sum 256.  (5, sigma 1), the kernel of both degraders, gives 14 62 104 62 14."""
+    n = int(ksize) if ksize else int(np.rint(6 * float(sigma) + 1)) | 1
+    if n < 1 or n % 2 == 0 or not sigma > 0:
+        raise ValueError("gaussian_taps_u8: ksize must be odd and sigma positive")
+    scale2 = -0.125 / (float(sigma) * float(sigma))
     vals = [math.exp(float((2 * i + 1 - n) ** 2) * scale2) for i in range(n // 2)]
     mul = 1.0 / (sum(vals) * 2.0 + 1.0)
     taps = np.zeros(n, np.int16)

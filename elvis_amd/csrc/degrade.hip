@@ -12,21 +12,9 @@
 // documented fixed-point arithmetic ("parity unpinned"); what is pinned is bit-exactness against
 // oracle/degrade_ref.py, which restates the same rules in numpy.  Evaluation order of every float expression
 // is fixed (explicit round-to-nearest intrinsics; the library is built with -ffp-contract=off).
-#include "common.h"
+#include "block_u8.h"
 
 namespace {
-
-// cv2.resize(INTER_LINEAR) source index and 11-bit weights of destination index d (s source samples, b results)
-__device__ __forceinline__ void linear_coef(int d, int s, int b, int& i0, int& a0, int& a1) {
-    float f = (float)(((double)d + 0.5) * ((double)s / (double)b) - 0.5);   // double arithmetic, one rounding to float
-    int i = (int)floorf(f);
-    f = __fsub_rn(f, (float)i);
-    if (i < 0) { i = 0; f = 0.f; }
-    if (i >= s - 1) { i = s - 1; f = 0.f; }
-    i0 = i;
-    a0 = __float2int_rn(__fmul_rn(__fsub_rn(1.0f, f), 2048.0f));
-    a1 = __float2int_rn(__fmul_rn(f, 2048.0f));
-}
 
 // one thread per (block, channel): the block is at most 16 x 16 (b <= 16)
 __global__ __launch_bounds__(64) void degrade_downsample_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ levels,
@@ -61,7 +49,7 @@ __global__ __launch_bounds__(64) void degrade_downsample_kernel(const uint8_t* _
             uint32_t v = fac == 2 ? (sum + 2) >> 2 : (uint32_t)__float2int_rn(__fmul_rn((float)sum, inv));   // INTER_AREA u8 rules
             small[y][x] = (uint8_t)(v > 255 ? 255 : v);
         }
-    // INTER_LINEAR back to b x b: horizontal pass in 11-bit fixed point, vertical pass (b0*(S0>>4)>>16 + b1*(S1>>4)>>16 + 2)>>2
+    // INTER_LINEAR back to b x b (block_u8.h: linear_coef, linear_mix)
     for (int y = 0; y < b; ++y) {
         int y0, b0, b1;
         linear_coef(y, s, b, y0, b0, b1);
@@ -70,19 +58,10 @@ __global__ __launch_bounds__(64) void degrade_downsample_kernel(const uint8_t* _
             int x0, a0, a1;
             linear_coef(x, s, b, x0, a0, a1);
             const int x1 = x0 + 1 < s ? x0 + 1 : x0;
-            const int r0 = small[y0][x0] * a0 + small[y0][x1] * a1;
-            const int r1 = small[y1][x0] * a0 + small[y1][x1] * a1;
-            int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-            v = v < 0 ? 0 : (v > 255 ? 255 : v);
-            dst[base + y * rs + (long long)x * c] = (uint8_t)v;
+            dst[base + y * rs + (long long)x * c] =
+                (uint8_t)linear_mix(small[y0][x0], small[y0][x1], small[y1][x0], small[y1][x1], a0, a1, b0, b1);
         }
     }
-}
-
-__device__ __forceinline__ int reflect101(int i, int n) {   // BORDER_REFLECT_101: -1 -> 1, n -> n-2 (n == 1: 0)
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
-    return i;
 }
 
 // one thread per (block, channel); b <= 16.  Per round: float32 horizontal pass, float32 vertical pass,

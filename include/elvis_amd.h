@@ -325,6 +325,33 @@ int elvis_degrade_gaussian_u8(const uint8_t* src, const int32_t* rounds, uint8_t
 int elvis_degrade_dct_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, const float* basis64, const float* gain,
                          int n_levels, int n, int h, int w, int c, int by, int bx, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ Presley's adaptive degraders
+ * utils.py:1101-1217 and presley.py:968-1039 in OpenCV's 8-bit arithmetic (restated, parity with cv2 unpinned).
+ * One wave per block; map[n, by, bx] int32 with by = H / block_size, bx = W / block_size (floor).  PIXELS OUTSIDE
+ * THE BLOCK GRID are never written: dst keeps there what the caller put (the Python layer starts from a copy of src).
+ * Any block_size in [2, 32], 1 <= C <= 4. */
+
+#define ELVIS_DEGRADE_MAX_ROUNDS 64
+
+/* downscale_block (presley.py:978-983) and the block loop of degrade_adaptive_downsample (utils.py:1153-1161): a block
+ * of scale >= 2 is INTER_AREA-resized to d = max(1, block_size / scale) and INTER_LINEAR-resized back; scale <= 1
+ * copies the block.  block_size % d == 0 takes the integer-ratio rule of elvis_degrade_downsample_u8; any other d
+ * takes cv::ResizeArea_<uchar, float> with the computeResizeAreaTab table of block_size -> d, built by
+ * elvis_amd/degrade.py for every d in [1, block_size / 2] (device pointers): the entries of destination index i are
+ * tab_src / tab_w[tab_starts[d * (block_size / 2 + 2) + i] .. tab_starts[d * (block_size / 2 + 2) + i + 1]), all
+ * below tab_len; a d has at most 2 * block_size entries. */
+int elvis_degrade_scale_u8(const uint8_t* src, const int32_t* scales, uint8_t* dst, int n, int h, int w, int c,
+                           int block_size, int by, int bx, const int32_t* tab_starts, const int32_t* tab_src,
+                           const float* tab_w, int tab_len, elvis_stream_t stream);
+
+/* blur_block (presley.py:986-990) and the block loop of degrade_adaptive_blur (utils.py:1203-1210): `rounds` passes of
+ * cv2.GaussianBlur(block, (5, 5), 1.0) on CV_8U: 8.8 fixed-point taps (tap0, tap1, tap2, tap1, tap0) that sum to 256
+ * (14, 62, 104 from the host), u8 x tap summed in u16, u16 x tap summed in u32, one rounding (acc + 0x8000) >> 16,
+ * BORDER_REFLECT_101 at the block's own edges.  `rounds` is clamped to [0, ELVIS_DEGRADE_MAX_ROUNDS] (a negative
+ * count copies the block; the Python layer rejects larger ones). */
+int elvis_degrade_gaussian_fx_u8(const uint8_t* src, const int32_t* rounds, uint8_t* dst, int n, int h, int w, int c,
+                                 int block_size, int by, int bx, int tap0, int tap1, int tap2, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ classical restorers
  * The OpenCV baselines of ELVIS and Presley, per block of a uint8 NHWC frame; map[n, by, bx] int32 with
  * by = H / block_size, bx = W / block_size (floor).  PIXELS OUTSIDE THE BLOCK GRID (the rows and columns past the last
