@@ -21,6 +21,8 @@ from .classical import (lanczos_restore_device, restore_blur_opencv_unsharp_mask
                         restore_downsample_opencv_lanczos, restore_with_opencv_lanczos, restore_with_opencv_unsharp,
                         temporal_blend_device, unsharp_restore_device)
 from .metrics import calculate_block_ssim, calculate_mse, calculate_psnr, masked_mse, masked_psnr  # noqa: F401
+from .metrics import (apply_binary_mask, calculate_foreground_metric, calculate_ssim, compute_fg_bg_ssim,  # noqa: F401
+                      compute_mask_union_bbox, evaluate_fg_bg_metrics, masked_ssim, masked_ssim_device)
 from .shrink import (apply_selective_removal, block_gather_device, shrink_frame_position_map,  # noqa: F401
                      shrink_frame_removal_indices, shrink_frame_row_only, shrink_passes_device, shrink_topk_device,
                      shrink_video_frames, stretch_device, stretch_frame, stretch_frame_position_map,

@@ -18,6 +18,9 @@ LIBPATH = os.environ.get("ELVIS_AMD_LIB") or os.path.join(HERE, "lib", "libelvis
 
 F32, F16 = 0, 1
 ROUND_CV2, ROUND_HALF_UP = 0, 1
+SSIM_LUMA, SSIM_CHANNELS = 0, 1
+SSIM_REFLECT, SSIM_VALID = 0, 1
+SSIM_PAD_AUTO = -1
 
 _lock = threading.Lock()
 _lib: Optional[C.CDLL] = None
@@ -44,6 +47,10 @@ SIGNATURES = {
     "elvis_tile_normalize_u8": [vp, vp, vp, i32, i32, i32, vp],
     "elvis_sse_u8": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "elvis_block_ssim_u8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "elvis_mask_bbox_u8": [vp, vp, i32, i32, i32, vp],
+    "elvis_apply_mask_u8": [vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "elvis_ssim_workspace_bytes": [i32, i32, i32, i32],
+    "elvis_ssim_mean_f64": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, i32, f64, vp],
     "elvis_u8_to_float": [vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, i32, vp],
     "elvis_float_to_u8": [vp, i32, vp, vp, i32, i32, i32, i32, f32, f32, i32, i32, vp],
     "elvis_conv_packed_weight_bytes": [C.POINTER(ConvDesc)],
@@ -119,6 +126,7 @@ def lib() -> C.CDLL:
         handle.elvis_conv_packed_weight_bytes.restype = C.c_size_t
         handle.elvis_groupnorm_workspace_floats.restype = C.c_size_t
         handle.elvis_swin_packed_bytes.restype = C.c_size_t
+        handle.elvis_ssim_workspace_bytes.restype = C.c_size_t
         if handle.elvis_abi_version() != 1:
             raise RuntimeError("libelvis_amd.so ABI version mismatch")
         _lib = handle

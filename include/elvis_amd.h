@@ -113,6 +113,46 @@ int elvis_sse_u8(const uint8_t* a, const uint8_t* b, const uint8_t* mask, unsign
 int elvis_block_ssim_u8(const uint8_t* a, const uint8_t* b, float* ssim_out, const float* win11, int n, int h, int w, int c,
                         int block_size, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ quality report (quality.hip) */
+
+/* Per-frame bounding box of a [n,h,w] u8 mask (non-zero = set), the crop of elvis.py:688-690 and presley.py:431-436:
+ * bbox_out int32 [n,4] = y0, y1, x0, x1 with exclusive ends, 0,0,0,0 for an empty mask.  Integer min/max only. */
+int elvis_mask_bbox_u8(const uint8_t* mask, int32_t* bbox_out, int n, int h, int w, elvis_stream_t stream);
+
+/* out = ((mask != 0) != invert) ? frames : 0 per pixel (_apply_binary_mask, elvis.py:615-624).  frames, out: [n,h,w,c] u8;
+ * mask: [n,h,w] u8.  16-byte vectors for c = 1, 3, 4 on 16-byte aligned tensors. */
+int elvis_apply_mask_u8(const uint8_t* frames, const uint8_t* mask, uint8_t* out, int n, int h, int w, int c, int invert,
+                        elvis_stream_t stream);
+
+#define ELVIS_SSIM_LUMA 0      /* source: Y = (1868 B + 9617 G + 4899 R + 8192) >> 14 of a BGR pixel, one output per frame */
+#define ELVIS_SSIM_CHANNELS 1  /* source: every channel on its own, value / scale */
+#define ELVIS_SSIM_REFLECT 0   /* border: scipy.ndimage `reflect` at the work area's edge, repeated as often as needed */
+#define ELVIS_SSIM_VALID 1     /* border: none, the map is 10 shorter; a dimension under 11 is not smoothed */
+#define ELVIS_SSIM_PAD_AUTO (-1)
+
+/* Bytes of the partial-sum workspace elvis_ssim_mean_f64 needs for [n,h,w,c] frames (host query, 0 for a bad shape). */
+size_t elvis_ssim_workspace_bytes(int n, int h, int w, int c);
+
+/* Mean of the windowed SSIM map, float64 throughout (no fused contraction), for both evaluators of the reference:
+ *   _masked_ssim (elvis.py:674-721: skimage structural_similarity, gaussian_weights, on masked luma):
+ *       LUMA, REFLECT, C1 = 6.5025, C2 = 58.5225, scale unused, pad = ELVIS_SSIM_PAD_AUTO
+ *   calculate_ssim (presley.py:248-259: pytorch_msssim.ssim): CHANNELS, VALID, scale = 255, C1 = 1e-4, C2 = 9e-4,
+ *       cov_norm = 1, pad = 0
+ * a, b: [n,h,w,c] u8 (c <= 4; LUMA needs c = 3).  mask: [n,h,w] u8 or NULL, samples are zeroed where it is 0
+ * (elvis.py:696-697).  rects: int32 [n,4] = y0, y1, x0, x1 per frame (exclusive ends, clipped to the frame) or NULL for
+ * whole frames: the work area the window reflects in and the map is taken over.  win11: device f64[11].
+ * With moments ux, uy, uxx, uyy, uxy: vx = cov_norm (uxx - ux^2), likewise vy, vxy;
+ * S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)); out f64 [n, C] (C = 1 for LUMA) is the mean of S
+ * over the map shrunk by pad on every side.  pad = ELVIS_SSIM_PAD_AUTO takes pad and cov_norm per frame from the work
+ * area by elvis.py:702-711 (win = 7, or the largest odd number <= a smallest side of 3..6; pad = (win-1)/2,
+ * cov_norm = win^2/(win^2-1)), so a batch of unequal crops is one call.  A frame with nothing to average (empty
+ * rectangle, smallest side < 3 under the automatic rule, pad >= half a side) gives 1.0 (elvis.py:685-686, 704-706).
+ * One workgroup per 16x32 map tile writes one partial sum to workspace (elvis_ssim_workspace_bytes); a second launch
+ * adds a frame's partials in a fixed order: no float atomics, and a frame's result does not depend on n. */
+int elvis_ssim_mean_f64(const uint8_t* a, const uint8_t* b, const uint8_t* mask, const int32_t* rects, const double* win11,
+                        double* workspace, double* out, int n, int h, int w, int c, int source, int border, double C1,
+                        double C2, double cov_norm, int pad, double scale, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ u8 <-> float */
 
 /* dst[n,h,w,pitch] = (div255 ? src_u8/255 : src_u8) * scale + bias for the first 3 channels
