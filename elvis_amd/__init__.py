@@ -17,6 +17,8 @@ from .frameio import (clear_directory, decode_strength_maps_from_npz, encode_str
 from .degrade import (blur_block, degrade_adaptive_blur, degrade_adaptive_downsample, degrade_frame,  # noqa: F401
                       degrade_gaussian_fx_device, degrade_scale_device, degrade_video_adaptive, downscale_block,
                       filter_frame_dct, filter_frame_downsample, filter_frame_gaussian, generate_degradation_map)
+from .handoff import (calculate_importance_scores, convert_frames_to_yuv420p, create_kvazaar_roi_file,  # noqa: F401
+                      create_svtav1_roi_file, kvazaar_delta_qp, rgb_to_i420_device, svtav1_delta_qp, write_y4m)
 from .classical import (lanczos_restore_device, restore_blur_opencv_unsharp_mask,  # noqa: F401
                         restore_downsample_opencv_lanczos, restore_with_opencv_lanczos, restore_with_opencv_unsharp,
                         temporal_blend_device, unsharp_restore_device)

@@ -392,6 +392,20 @@ int elvis_degrade_scale_u8(const uint8_t* src, const int32_t* scales, uint8_t* d
 int elvis_degrade_gaussian_fx_u8(const uint8_t* src, const int32_t* rounds, uint8_t* dst, int n, int h, int w, int c,
                                  int block_size, int by, int bx, int tap0, int tap1, int tap2, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ encoder hand-off (handoff.hip) */
+
+/* cv2.cvtColor(frame, COLOR_RGB2YUV_I420) per frame (write_y4m, utils.py:453-462 and presley.py:590-599;
+ * convert_frames_to_yuv420p, presley.py:217-223); bgr != 0 reads B,G,R (COLOR_BGR2YUV_I420).  src: [n,h,w,3] u8;
+ * dst: [n, h*3/2, w] u8 - per frame the Y plane h x w, then U h/2 x w/2, then V h/2 x w/2, each dense.  OpenCV 4.x
+ * RGB8toYUV420pInvoker restated (parity with cv2 unpinned), int32, 20-bit fixed point:
+ *   Y = ( 269484 R + 528482 G + 102760 B + (1 << 19) +  (16 << 20)) >> 20   for every pixel,
+ *   U = (-155188 R - 305135 G + 460324 B + (1 << 19) + (128 << 20)) >> 20
+ *   V = ( 460324 R - 385875 G -  74448 B + (1 << 19) + (128 << 20)) >> 20   of the pixel at the even row and even column
+ * of each 2x2 quad (not the quad's average).  Every output lies in [16, 240].  An odd h or w, a negative dimension or a
+ * null pointer with work to do is ELVIS_E_INVALID before anything is launched; n == 0 does nothing and succeeds.  Rows
+ * go out as dwords when w % 4 == 0 and both pointers are 4-byte aligned, byte by byte otherwise. */
+int elvis_rgb_to_i420_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int bgr, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ classical restorers
  * The OpenCV baselines of ELVIS and Presley, per block of a uint8 NHWC frame; map[n, by, bx] int32 with
  * by = H / block_size, bx = W / block_size (floor).  PIXELS OUTSIDE THE BLOCK GRID (the rows and columns past the last
