@@ -165,6 +165,14 @@ def require_gpu(device) -> None:
         raise RuntimeError("no ROCm GPU visible to torch; elvis_amd cannot run")
 
 
+def resolve_device(device):
+    """The torch.device of a `device=` argument ("cuda" is "cuda:0"), checked by `require_gpu`."""
+    import torch
+    dev = torch.device("cuda:0" if str(device) == "cuda" else device)
+    require_gpu(dev)
+    return dev
+
+
 def dtype_code(torch_dtype) -> int:
     import torch
     if torch_dtype == torch.float32:

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib as L
 from ._lib import check, lib, ptr
-from .ops import _chk_u8, _s
+from .ops import _block_maps, _block_out, _check_image_grid, _chk_u8, _one_image, _s
 from .recompose import frames_to_device, frames_to_host
 from .tiler import _nearest_rows
 
@@ -112,21 +112,7 @@ def _tables(device) -> tuple:
 
 
 # ----------------------------------------------------------------------------- device-resident forms
-def _maps(levels_d: torch.Tensor, n: int) -> torch.Tensor:
-    if levels_d.dtype != torch.int32 or levels_d.dim() != 3 or levels_d.shape[0] != n or not levels_d.is_cuda:
-        raise ValueError("classical restorers: the map must be a CUDA int32 tensor [n, by, bx]")
-    return levels_d.contiguous()
-
-
-def _out_for(frames_d: torch.Tensor, block_size: int, out):
-    if out is not None:
-        _chk_u8(out)
-        if out.shape != frames_d.shape:
-            raise ValueError("out must have the frames' shape")
-        return out
-    h, w = frames_d.shape[1:3]
-    # pixels past the last whole block are not written by the kernels: start from a copy when there are any
-    return torch.empty_like(frames_d) if h % block_size == 0 and w % block_size == 0 else frames_d.clone()
+_WHO = "classical restorers"
 
 
 def lanczos_restore_device(frames_d: torch.Tensor, levels_d: torch.Tensor, block_size: int, out=None) -> torch.Tensor:
@@ -134,9 +120,9 @@ def lanczos_restore_device(frames_d: torch.Tensor, levels_d: torch.Tensor, block
     block_size (levels clamped to [0, 16] on the device).  frames [n,H,W,C] u8, levels [n,H//b,W//b] int32."""
     _chk_u8(frames_d)
     n, h, w, c = frames_d.shape
-    m = _maps(levels_d, n)
+    m = _block_maps(levels_d, n, _WHO)
     taps, _, _ = _tables(frames_d.device)
-    out = _out_for(frames_d, block_size, out)
+    out = _block_out(frames_d, block_size, out, _WHO)
     check(lib().elvis_classical_lanczos_u8(ptr(frames_d), ptr(m), ptr(out), n, h, w, c, block_size, m.shape[1], m.shape[2],
                                            ptr(taps), _s(frames_d)), frames_d.device)
     return out
@@ -148,9 +134,9 @@ def unsharp_restore_device(frames_d: torch.Tensor, levels_d: torch.Tensor, block
     clipped at the frame (levels clamped to [0, 16] on the device).  frames [n,H,W,C] u8, levels [n,H//b,W//b]."""
     _chk_u8(frames_d)
     n, h, w, c = frames_d.shape
-    m = _maps(levels_d, n)
+    m = _block_maps(levels_d, n, _WHO)
     _, g_taps, g_offs = _tables(frames_d.device)
-    out = _out_for(frames_d, block_size, out)
+    out = _block_out(frames_d, block_size, out, _WHO)
     check(lib().elvis_classical_unsharp_u8(ptr(frames_d), ptr(m), ptr(out), n, h, w, c, block_size, m.shape[1], m.shape[2],
                                            int(halo), ptr(g_taps), ptr(g_offs), MAX_LEVEL, _s(frames_d)), frames_d.device)
     return out
@@ -174,33 +160,13 @@ def temporal_blend_device(frames_d: torch.Tensor, temporal_blend: float, out=Non
 
 
 # ----------------------------------------------------------------------------- the reference's call surface
-def _device(device) -> torch.device:
-    dev = torch.device("cuda:0" if str(device) == "cuda" else device)
-    L.require_gpu(dev)
-    return dev
-
-
 def _check_image(image: np.ndarray, maps: np.ndarray, block_size: int):
-    if image.dtype != np.uint8 or image.ndim != 3:
-        raise ValueError("the classical restorers take uint8 (H,W,C) images")
-    h, w = image.shape[:2]
-    if h % block_size or w % block_size:
-        raise ValueError("Image dimensions must be divisible by block_size.")   # split_image_into_blocks, elvis.py:1376
-    if maps.shape != (h // block_size, w // block_size):
-        raise ValueError(f"map {maps.shape} does not match the block grid {(h // block_size, w // block_size)}")
+    _check_image_grid(image, maps, block_size, "the classical restorers", "map {} does")
 
 
 def _check_level_range(levels: np.ndarray):
     if levels.size and levels.max() > MAX_LEVEL:
         raise ValueError(f"levels above {MAX_LEVEL} are not supported")
-
-
-def _one_image(image: np.ndarray, levels: np.ndarray, device, fn, *args) -> np.ndarray:
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        img_d = torch.from_numpy(np.ascontiguousarray(image)[None]).to(dev)
-        map_d = torch.from_numpy(np.ascontiguousarray(levels.astype(np.int32))[None]).to(dev)
-        return fn(img_d, map_d, *args)[0].cpu().numpy()
 
 
 def restore_downsample_opencv_lanczos(downsampled_image: np.ndarray, downscale_maps: np.ndarray, block_size: int,
@@ -270,7 +236,7 @@ def _restore_clip(frames: List[np.ndarray], degradation_maps, block_size: int, h
     if not 2 <= block_size <= MAX_BLOCK or block_size & (block_size - 1):
         raise ValueError(f"block_size must be a power of two in [2, {MAX_BLOCK}]")
     levels = _clip_levels(frames, degradation_maps, block_size)
-    dev = _device(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         fd = frames_to_device(frames, dev)
         if levels.shape[1] and levels.shape[2]:

@@ -11,32 +11,12 @@
 // OpenCV is absent from the build and GPU environments, so its 8-bit fixed-point rules are restated (DESIGN.md 7,
 // "parity unpinned"); what is pinned is bit-exactness against the numpy restatement in tests/_classical_ref.py.
 // The tap tables are built once on the host (elvis_amd/classical.py) so that the kernels are pure integer work.
-#include "common.h"
+#include "block_u8.h"
 
 namespace {
 
-constexpr int kMaxBlock = 32;
 constexpr int kMaxHalo = 32;
-constexpr int kMaxChannels = 4;
 constexpr int kLanczosPhases = 32;   // taps[(log2(f) - 1)][d][8] for d < kLanczosPhases
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ int reflect101(int i, int n) {   // cv::borderInterpolate(BORDER_REFLECT_101): reflects until inside
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
-    return i;
-}
-
-__device__ __forceinline__ void copy_block(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long base,
-                                           long long rs, int b, int c) {
-    const int rowlen = b * c;
-    for (int e = threadIdx.x; e < b * rowlen; e += ELVIS_WAVE) {
-        const int y = e / rowlen;
-        const long long o = base + y * rs + (e - y * rowlen);
-        dst[o] = src[o];
-    }
-}
 
 // One wave per block (the level is uniform per workgroup).  LDS: the block (u8), the INTER_AREA result (int), the
 // horizontal Lanczos pass (int), this factor's taps (int).  Every loop strides the lanes over (pixel, channel).
@@ -44,13 +24,9 @@ __global__ __launch_bounds__(64) void classical_lanczos_kernel(const uint8_t* __
                                                                uint8_t* __restrict__ dst, int h, int w, int c, int b, int lb,
                                                                int by, int bx, const int16_t* __restrict__ taps) {
     extern __shared__ int lds[];
-    const int blk = blockIdx.x;
-    const int bxi = blk % bx;
-    const int byi = (blk / bx) % by;
-    const int f = blk / (bx * by);
-    const long long rs = (long long)w * c;
-    const long long base = ((long long)f * h + (long long)byi * b) * rs + (long long)bxi * b * c;
-    const int lv = clampi(levels[blk], 0, 16);
+    const BlockAddr at(h, w, c, b, by, bx);
+    const long long rs = at.rs, base = at.base;
+    const int lv = clampi(levels[at.blk], 0, 16);
     if (lv == 0) {
         copy_block(src, dst, base, rs, b, c);
         return;
@@ -64,24 +40,15 @@ __global__ __launch_bounds__(64) void classical_lanczos_kernel(const uint8_t* __
     int* hp = small + s * s * c;                // [s][b][c]
     uint8_t* blkp = (uint8_t*)(hp + s * b * c); // [b][b][c]
     for (int e = threadIdx.x; e < b * 8; e += ELVIS_WAVE) tap[e] = taps[(lf - 1) * kLanczosPhases * 8 + e];
-    for (int e = threadIdx.x; e < b * rowlen; e += ELVIS_WAVE) {
-        const int y = e / rowlen;
-        blkp[e] = src[base + y * rs + (e - y * rowlen)];
-    }
+    stage_block(src, blkp, base, rs, b, rowlen);
     __syncthreads();
-    // INTER_AREA at the integer scale fac (cv::resizeAreaFast_ u8 rules, as degrade_downsample_kernel)
+    // INTER_AREA at the integer scale fac
     const float inv = 1.0f / (float)(fac * fac);
     for (int e = threadIdx.x; e < s * s * c; e += ELVIS_WAVE) {
         const int ch = e % c;
         const int sx = (e / c) % s;
         const int sy = e / (c * s);
-        uint32_t sum = 0;
-        for (int dy = 0; dy < fac; ++dy) {
-            const uint8_t* row = blkp + (sy * fac + dy) * rowlen + sx * fac * c + ch;
-            for (int dx = 0; dx < fac; ++dx) sum += row[dx * c];
-        }
-        const uint32_t v = fac == 2 ? (sum + 2) >> 2 : (uint32_t)__float2int_rn(__fmul_rn((float)sum, inv));
-        small[e] = (int)(v > 255 ? 255 : v);
+        small[e] = (int)area_box(blkp, rowlen, c, sy, sx, ch, fac, inv);
     }
     __syncthreads();
     // horizontal INTER_LANCZOS4 pass: s rows x b columns, source columns clamped (BORDER_REPLICATE).
@@ -123,14 +90,11 @@ __global__ __launch_bounds__(64) void classical_unsharp_kernel(const uint8_t* __
                                                                int bx, int halo, const int16_t* __restrict__ taps,
                                                                const int32_t* __restrict__ tap_offsets, int max_level) {
     extern __shared__ int lds[];
-    const int blk = blockIdx.x;
-    const int bxi = blk % bx;
-    const int byi = (blk / bx) % by;
-    const int f = blk / (bx * by);
-    const long long rs = (long long)w * c;
-    const long long fbase = (long long)f * h * rs;
-    const int y0 = byi * b, x0 = bxi * b;
-    const int lv = clampi(levels[blk], 0, max_level);
+    const BlockAddr at(h, w, c, b, by, bx);
+    const long long rs = at.rs;
+    const long long fbase = (long long)at.f * h * rs;
+    const int y0 = at.byi * b, x0 = at.bxi * b;
+    const int lv = clampi(levels[at.blk], 0, max_level);
     if (lv == 0) {
         copy_block(src, dst, fbase + (long long)y0 * rs + (long long)x0 * c, rs, b, c);
         return;
@@ -144,10 +108,7 @@ __global__ __launch_bounds__(64) void classical_unsharp_kernel(const uint8_t* __
     uint16_t* hp = (uint16_t*)lds;                  // [th][b][c]
     uint8_t* tile = (uint8_t*)(hp + ((th * hrow + 1) & ~1));
     const long long tbase = fbase + (long long)ty0 * rs + (long long)tx0 * c;
-    for (int e = threadIdx.x; e < th * trow; e += ELVIS_WAVE) {
-        const int r = e / trow;
-        tile[e] = src[tbase + r * rs + (e - r * trow)];
-    }
+    stage_block(src, tile, tbase, rs, th, trow);
     __syncthreads();
     const int n = 6 * lv + 1, rad = 3 * lv;
     const int16_t* k0 = taps + tap_offsets[lv];
@@ -193,24 +154,11 @@ __global__ __launch_bounds__(256) void temporal_blend_kernel(const uint8_t* cur,
     }
 }
 
-int check_blocks(const void* src, const void* levels, const void* dst, const void* taps, int n, int h, int w, int c,
-                 int block, int by, int bx, const char* what) {
-    ELVIS_REQUIRE(src && levels && dst && taps, "%s: null pointer", what);
-    ELVIS_REQUIRE(n > 0 && h > 0 && w > 0, "%s: bad shape", what);
-    ELVIS_REQUIRE(c >= 1 && c <= kMaxChannels, "%s: %d channels (1..%d supported)", what, c, kMaxChannels);
-    ELVIS_REQUIRE(block >= 2 && block <= kMaxBlock && (block & (block - 1)) == 0,
-                  "%s: block_size %d must be a power of two in [2, %d]", what, block, kMaxBlock);
-    ELVIS_REQUIRE(by > 0 && bx > 0 && by == h / block && bx == w / block,
-                  "%s: the map must be %dx%d for a %dx%d image and block_size %d", what, h / block, w / block, h, w, block);
-    ELVIS_REQUIRE((long long)n * by * bx < (1LL << 31), "%s: too many blocks", what);
-    return ELVIS_OK;
-}
-
 }  // namespace
 
 extern "C" int elvis_classical_lanczos_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, int n, int h, int w, int c,
                                           int block, int by, int bx, const int16_t* taps, elvis_stream_t stream) {
-    int rc = check_blocks(src, levels, dst, taps, n, h, w, c, block, by, bx, "elvis_classical_lanczos_u8");
+    int rc = check_block_maps(src && levels && dst && taps, n, h, w, c, block, by, bx, true, "elvis_classical_lanczos_u8");
     if (rc) return rc;
     const int lb = __builtin_ctz((unsigned)block);
     const int s_max = block / 2;
@@ -224,7 +172,7 @@ extern "C" int elvis_classical_lanczos_u8(const uint8_t* src, const int32_t* lev
 extern "C" int elvis_classical_unsharp_u8(const uint8_t* src, const int32_t* levels, uint8_t* dst, int n, int h, int w, int c,
                                           int block, int by, int bx, int halo, const int16_t* taps, const int32_t* tap_offsets,
                                           int max_level, elvis_stream_t stream) {
-    int rc = check_blocks(src, levels, dst, taps, n, h, w, c, block, by, bx, "elvis_classical_unsharp_u8");
+    int rc = check_block_maps(src && levels && dst && taps, n, h, w, c, block, by, bx, true, "elvis_classical_unsharp_u8");
     if (rc) return rc;
     ELVIS_REQUIRE(tap_offsets, "elvis_classical_unsharp_u8: null pointer");
     ELVIS_REQUIRE(halo >= 0 && halo <= kMaxHalo, "elvis_classical_unsharp_u8: halo %d outside [0, %d]", halo, kMaxHalo);

@@ -46,8 +46,7 @@ __global__ __launch_bounds__(64) void degrade_downsample_kernel(const uint8_t* _
             uint32_t sum = 0;
             for (int dy = 0; dy < fac; ++dy)
                 for (int dx = 0; dx < fac; ++dx) sum += src[base + (long long)(y * fac + dy) * rs + (long long)(x * fac + dx) * c];
-            uint32_t v = fac == 2 ? (sum + 2) >> 2 : (uint32_t)__float2int_rn(__fmul_rn((float)sum, inv));   // INTER_AREA u8 rules
-            small[y][x] = (uint8_t)(v > 255 ? 255 : v);
+            small[y][x] = (uint8_t)area_round(sum, fac, inv);
         }
     // INTER_LINEAR back to b x b (block_u8.h: linear_coef, linear_mix)
     for (int y = 0; y < b; ++y) {

@@ -13,19 +13,6 @@
 
 namespace {
 
-constexpr int kMaxBlock = 32;
-constexpr int kMaxChannels = 4;
-
-__device__ __forceinline__ void copy_block(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long base,
-                                           long long rs, int b, int c) {
-    const int rowlen = b * c;
-    for (int e = threadIdx.x; e < b * rowlen; e += ELVIS_WAVE) {
-        const int y = e / rowlen;
-        const long long o = base + y * rs + (e - y * rowlen);
-        dst[o] = src[o];
-    }
-}
-
 __device__ __forceinline__ int pixel_of(int xc, int c) {   // xc / c for xc < 2^15, c in 1..4 (uniform), no integer divide
     return c == 1 ? xc : (c == 2 ? xc >> 1 : (c == 4 ? xc >> 2 : (int)(((unsigned)xc * 43691u) >> 17)));
 }
@@ -48,7 +35,7 @@ struct ScaleLds {
 };
 
 // One wave per block (the scale is uniform per workgroup).  INTER_AREA from b to d = max(1, b / scale): at an integer
-// ratio the box sum of degrade_downsample_kernel; otherwise cv::ResizeArea_<uchar, float> - per source row
+// ratio block_u8.h's area_box; otherwise cv::ResizeArea_<uchar, float> - per source row
 // buf[dx] = sum_k float(S[sx_k]) * alpha_k, per destination row sum[dx] = sum_j beta_j * buf_j[dx], float32 from 0
 // in table order, every product rounded before it is added, then saturate_cast<uchar> (round-half-even).  Every output
 // is its own ordered sum; the lanes are strided over outputs and never split a sum.  Then INTER_LINEAR back to b.
@@ -58,13 +45,9 @@ __global__ __launch_bounds__(64) void degrade_scale_kernel(const uint8_t* __rest
                                                            const int32_t* __restrict__ tab_src,
                                                            const float* __restrict__ tab_w, int tab_len) {
     extern __shared__ int lds[];
-    const int blk = blockIdx.x;
-    const int bxi = blk % bx;
-    const int byi = (blk / bx) % by;
-    const int f = blk / (bx * by);
-    const long long rs = (long long)w * c;
-    const long long base = ((long long)f * h + (long long)byi * b) * rs + (long long)bxi * b * c;
-    const int sc = scales[blk];
+    const BlockAddr at(h, w, c, b, by, bx);
+    const long long rs = at.rs, base = at.base;
+    const int sc = scales[at.blk];
     if (sc <= 1) {                                  // 0 = keep; 1 resizes to the same size twice: the identity
         copy_block(src, dst, base, rs, b, c);
         return;
@@ -82,10 +65,7 @@ __global__ __launch_bounds__(64) void degrade_scale_kernel(const uint8_t* __rest
     uint8_t* small = (uint8_t*)(l8 + L.small);
     uint8_t* blkp = (uint8_t*)(l8 + L.blk);
     const bool whole = b % d == 0;
-    for (int e = threadIdx.x; e < b * rowlen; e += ELVIS_WAVE) {
-        const int y = e / rowlen;
-        blkp[e] = src[base + y * rs + (e - y * rowlen)];
-    }
+    stage_block(src, blkp, base, rs, b, rowlen);
     for (int e = threadIdx.x; e < b; e += ELVIS_WAVE) linear_coef(e, d, b, coef[3 * e], coef[3 * e + 1], coef[3 * e + 2]);
     if (!whole) {
         // this d's table, read with a wave-uniform base; every index is clamped so that a bad table cannot leave the LDS
@@ -108,13 +88,7 @@ __global__ __launch_bounds__(64) void degrade_scale_kernel(const uint8_t* __rest
             const int xc = e - sy * drow;
             const int sx = pixel_of(xc, c);
             const int ch = xc - sx * c;
-            uint32_t sum = 0;
-            for (int dy = 0; dy < fac; ++dy) {
-                const uint8_t* row = blkp + (sy * fac + dy) * rowlen + sx * fac * c + ch;
-                for (int dx = 0; dx < fac; ++dx) sum += row[dx * c];
-            }
-            const uint32_t v = fac == 2 ? (sum + 2) >> 2 : (uint32_t)__float2int_rn(__fmul_rn((float)sum, inv));   // INTER_AREA u8 rules
-            small[e] = (uint8_t)(v > 255 ? 255 : v);
+            small[e] = (uint8_t)area_box(blkp, rowlen, c, sy, sx, ch, fac, inv);
         }
     } else {
         for (int e = threadIdx.x; e < b * drow; e += ELVIS_WAVE) {
@@ -165,13 +139,9 @@ __global__ __launch_bounds__(64) void degrade_gaussian_fx_kernel(const uint8_t* 
                                                                  uint8_t* __restrict__ dst, int h, int w, int c, int b, int by,
                                                                  int bx, int t0, int t1, int t2) {
     extern __shared__ int lds[];
-    const int blk = blockIdx.x;
-    const int bxi = blk % bx;
-    const int byi = (blk / bx) % by;
-    const int f = blk / (bx * by);
-    const long long rs = (long long)w * c;
-    const long long base = ((long long)f * h + (long long)byi * b) * rs + (long long)bxi * b * c;
-    const int r = clampi(rounds[blk], 0, ELVIS_DEGRADE_MAX_ROUNDS);
+    const BlockAddr at(h, w, c, b, by, bx);
+    const long long rs = at.rs, base = at.base;
+    const int r = clampi(rounds[at.blk], 0, ELVIS_DEGRADE_MAX_ROUNDS);
     if (r == 0) {
         copy_block(src, dst, base, rs, b, c);
         return;
@@ -179,10 +149,7 @@ __global__ __launch_bounds__(64) void degrade_gaussian_fx_kernel(const uint8_t* 
     const int rowlen = b * c, count = b * rowlen;
     uint16_t* hp = (uint16_t*)lds;                          // [b][b][c]
     uint8_t* cur = (uint8_t*)(hp + ((count + 1) & ~1));     // [b][b][c]
-    for (int e = threadIdx.x; e < count; e += ELVIS_WAVE) {
-        const int y = e / rowlen;
-        cur[e] = src[base + y * rs + (e - y * rowlen)];
-    }
+    stage_block(src, cur, base, rs, b, rowlen);
     __syncthreads();
     const int y_first = threadIdx.x / rowlen, xc_first = threadIdx.x - y_first * rowlen;
     for (int it = 0; it < r; ++it) {
@@ -212,24 +179,12 @@ __global__ __launch_bounds__(64) void degrade_gaussian_fx_kernel(const uint8_t* 
     }
 }
 
-int check_presley(const void* src, const void* map, const void* dst, int n, int h, int w, int c, int b, int by, int bx,
-                  const char* what) {
-    ELVIS_REQUIRE(src && map && dst, "%s: null pointer", what);
-    ELVIS_REQUIRE(n > 0 && h > 0 && w > 0, "%s: bad shape", what);
-    ELVIS_REQUIRE(c >= 1 && c <= kMaxChannels, "%s: %d channels (1..%d supported)", what, c, kMaxChannels);
-    ELVIS_REQUIRE(b >= 2 && b <= kMaxBlock, "%s: block_size %d outside [2, %d]", what, b, kMaxBlock);
-    ELVIS_REQUIRE(by > 0 && bx > 0 && by == h / b && bx == w / b,
-                  "%s: the map must be %dx%d for a %dx%d image and block_size %d", what, h / b, w / b, h, w, b);
-    ELVIS_REQUIRE((long long)n * by * bx < (1LL << 31), "%s: too many blocks", what);
-    return ELVIS_OK;
-}
-
 }  // namespace
 
 extern "C" int elvis_degrade_scale_u8(const uint8_t* src, const int32_t* scales, uint8_t* dst, int n, int h, int w, int c,
                                       int block, int by, int bx, const int32_t* tab_starts, const int32_t* tab_src,
                                       const float* tab_w, int tab_len, elvis_stream_t stream) {
-    int rc = check_presley(src, scales, dst, n, h, w, c, block, by, bx, "elvis_degrade_scale_u8");
+    int rc = check_block_maps(src && scales && dst, n, h, w, c, block, by, bx, false, "elvis_degrade_scale_u8");
     if (rc) return rc;
     ELVIS_REQUIRE(tab_starts && tab_src && tab_w && tab_len > 0, "elvis_degrade_scale_u8: area tables missing");
     hipLaunchKernelGGL(degrade_scale_kernel, dim3((unsigned)(n * by * bx)), dim3(ELVIS_WAVE), (size_t)ScaleLds(block, c).bytes,
@@ -240,7 +195,7 @@ extern "C" int elvis_degrade_scale_u8(const uint8_t* src, const int32_t* scales,
 
 extern "C" int elvis_degrade_gaussian_fx_u8(const uint8_t* src, const int32_t* rounds, uint8_t* dst, int n, int h, int w, int c,
                                             int block, int by, int bx, int tap0, int tap1, int tap2, elvis_stream_t stream) {
-    int rc = check_presley(src, rounds, dst, n, h, w, c, block, by, bx, "elvis_degrade_gaussian_fx_u8");
+    int rc = check_block_maps(src && rounds && dst, n, h, w, c, block, by, bx, false, "elvis_degrade_gaussian_fx_u8");
     if (rc) return rc;
     // 8.8 fixed point: the taps sum to one, which is what keeps the horizontal pass inside u16
     ELVIS_REQUIRE(tap0 >= 0 && tap1 >= 0 && tap2 >= 0 && 2 * (tap0 + tap1) + tap2 == 256,

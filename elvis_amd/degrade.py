@@ -32,7 +32,7 @@ import torch
 from . import _lib as L
 from ._lib import check, lib, ptr
 from .classical import gaussian_taps_u8
-from .ops import _chk_u8, _s
+from .ops import _block_maps, _block_out, _check_image_grid, _chk_u8, _one_image, _s
 from .recompose import frames_to_device, frames_to_host
 
 DCT_LEVELS = 4
@@ -62,27 +62,11 @@ def _dct_tables(device) -> tuple:
     return _TABLES[key]
 
 
-def _maps(levels_d: torch.Tensor, n: int) -> torch.Tensor:
-    if levels_d.dtype != torch.int32 or levels_d.dim() != 3 or levels_d.shape[0] != n or not levels_d.is_cuda:
-        raise ValueError("degrade: the map must be a CUDA int32 tensor [n, by, bx]")
-    return levels_d.contiguous()
-
-
-def _out_for(frames_d: torch.Tensor, out) -> torch.Tensor:
-    """`out` goes to the kernel as a bare pointer: it must be the frames' twin (shape, uint8, device, contiguous)."""
-    if out is None:
-        return torch.empty_like(frames_d)
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != frames_d.device \
-            or out.shape != frames_d.shape:
-        raise ValueError("degrade: out must be a contiguous uint8 tensor of the frames' shape on the frames' device")
-    return out
-
-
 def degrade_downsample_device(frames_d: torch.Tensor, levels_d: torch.Tensor, block_size: int, out=None) -> torch.Tensor:
     _chk_u8(frames_d)
     n, h, w, c = frames_d.shape
-    m = _maps(levels_d, n)
-    out = _out_for(frames_d, out)
+    m = _block_maps(levels_d, n, "degrade")
+    out = _block_out(frames_d, block_size, out, "degrade")
     check(lib().elvis_degrade_downsample_u8(ptr(frames_d), ptr(m), ptr(out), n, h, w, c, block_size, m.shape[1], m.shape[2],
                                             _s(frames_d)), frames_d.device)
     return out
@@ -91,8 +75,8 @@ def degrade_downsample_device(frames_d: torch.Tensor, levels_d: torch.Tensor, bl
 def degrade_gaussian_device(frames_d: torch.Tensor, rounds_d: torch.Tensor, block_size: int, out=None) -> torch.Tensor:
     _chk_u8(frames_d)
     n, h, w, c = frames_d.shape
-    m = _maps(rounds_d, n)
-    out = _out_for(frames_d, out)
+    m = _block_maps(rounds_d, n, "degrade")
+    out = _block_out(frames_d, block_size, out, "degrade")
     k0, k1, k2 = gaussian_taps()
     check(lib().elvis_degrade_gaussian_u8(ptr(frames_d), ptr(m), ptr(out), n, h, w, c, block_size, m.shape[1], m.shape[2],
                                           k0, k1, k2, _s(frames_d)), frames_d.device)
@@ -102,31 +86,16 @@ def degrade_gaussian_device(frames_d: torch.Tensor, rounds_d: torch.Tensor, bloc
 def degrade_dct_device(frames_d: torch.Tensor, levels_d: torch.Tensor, out=None) -> torch.Tensor:
     _chk_u8(frames_d)
     n, h, w, c = frames_d.shape
-    m = _maps(levels_d, n)
+    m = _block_maps(levels_d, n, "degrade")
     basis, gain = _dct_tables(frames_d.device)
-    out = _out_for(frames_d, out)
+    out = _block_out(frames_d, 8, out, "degrade")
     check(lib().elvis_degrade_dct_u8(ptr(frames_d), ptr(m), ptr(out), ptr(basis), ptr(gain), DCT_LEVELS, n, h, w, c,
                                      m.shape[1], m.shape[2], _s(frames_d)), frames_d.device)
     return out
 
 
-def _one_frame(image: np.ndarray, maps: np.ndarray, device, fn, *args) -> np.ndarray:
-    dev = torch.device("cuda:0" if str(device) == "cuda" else device)
-    L.require_gpu(dev)
-    if image.dtype != np.uint8 or image.ndim != 3:
-        raise ValueError("degrade filters take uint8 (H,W,C) images")
-    with torch.cuda.device(dev):
-        img_d = torch.from_numpy(np.ascontiguousarray(image)[None]).to(dev)
-        map_d = torch.from_numpy(np.ascontiguousarray(maps.astype(np.int32))[None]).to(dev)
-        return fn(img_d, map_d, *args)[0].cpu().numpy()
-
-
 def _check_grid(image: np.ndarray, scores: np.ndarray, block_size: int):
-    h, w = image.shape[:2]
-    if h % block_size or w % block_size:
-        raise ValueError("Image dimensions must be divisible by block_size.")   # split_image_into_blocks, elvis.py:1376
-    if scores.shape != (h // block_size, w // block_size):
-        raise ValueError(f"scores {scores.shape} do not match the block grid {(h // block_size, w // block_size)}")
+    _check_image_grid(image, scores, block_size, "degrade filters", "scores {} do")
 
 
 def filter_frame_downsample(image: np.ndarray, frame_scores: np.ndarray, block_size: int, device="cuda:0"):
@@ -134,7 +103,7 @@ def filter_frame_downsample(image: np.ndarray, frame_scores: np.ndarray, block_s
     INTER_AREA-downscaled by 2**L and INTER_LINEAR-upscaled back.  Returns (image, int32 level map)."""
     _check_grid(image, frame_scores, block_size)
     levels = np.round(frame_scores * int(np.log2(block_size))).astype(np.int32)
-    return _one_frame(image, levels, device, degrade_downsample_device, block_size), levels
+    return _one_image(image, levels, device, degrade_downsample_device, block_size), levels
 
 
 def filter_frame_gaussian(image: np.ndarray, frame_scores: np.ndarray, block_size: int, device="cuda:0", *,
@@ -154,7 +123,7 @@ def filter_frame_gaussian(image: np.ndarray, frame_scores: np.ndarray, block_siz
     _check_grid(image, frame_scores, block_size)
     rounds = np.round(frame_scores * 10).astype(np.int32)
     fn = degrade_gaussian_device if arithmetic == "float32" else degrade_gaussian_fx_device
-    return _one_frame(image, rounds, device, fn, block_size), rounds
+    return _one_image(image, rounds, device, fn, block_size), rounds
 
 
 def filter_frame_dct(image: np.ndarray, frame_scores: np.ndarray, block_size: int = 8, device="cuda:0"):
@@ -164,7 +133,7 @@ def filter_frame_dct(image: np.ndarray, frame_scores: np.ndarray, block_size: in
         raise ValueError("the DCT degrade works on 8x8 blocks")
     _check_grid(image, frame_scores, block_size)
     levels = np.round(frame_scores * (DCT_LEVELS - 1)).astype(np.int32)
-    return _one_frame(image, levels, device, degrade_dct_device), levels
+    return _one_image(image, levels, device, degrade_dct_device), levels
 
 
 # ----------------------------------------------------------------------------- Presley's adaptive degraders
@@ -228,16 +197,10 @@ def _presley_args(frames_d: torch.Tensor, map_d: torch.Tensor, block_size: int, 
     n, h, w, c = frames_d.shape
     if not 1 <= c <= 4:
         raise ValueError("degrade: 1..4 channels are supported")
-    m = _maps(map_d, n)
+    m = _block_maps(map_d, n, "degrade")
     if tuple(m.shape[1:]) != (h // block_size, w // block_size):
         raise ValueError(f"degrade: map {tuple(m.shape[1:])} does not match the block grid {(h // block_size, w // block_size)}")
-    if out is not None:
-        out = _out_for(frames_d, out)
-    elif h % block_size or w % block_size:
-        out = frames_d.clone()
-    else:
-        out = torch.empty_like(frames_d)
-    return m, out, m.shape[1] > 0 and m.shape[2] > 0
+    return m, _block_out(frames_d, block_size, out, "degrade"), m.shape[1] > 0 and m.shape[2] > 0
 
 
 def degrade_scale_device(frames_d: torch.Tensor, scales_d: torch.Tensor, block_size: int, out=None) -> torch.Tensor:
@@ -309,7 +272,7 @@ def degrade_adaptive_downsample(frame: np.ndarray, importance: np.ndarray, block
     PARITY UNPINNED vs cv2; an importance that is not the block grid raises ValueError (module docstring)."""
     _check_frame(frame, importance, block_size, "importance")
     degradation_map = _scale_map(importance, max_scale)
-    return _one_frame(frame, degradation_map, device, degrade_scale_device, block_size), degradation_map
+    return _one_image(frame, degradation_map, device, degrade_scale_device, block_size), degradation_map
 
 
 def degrade_adaptive_blur(frame: np.ndarray, importance: np.ndarray, block_size: int, max_rounds: int = 10,
@@ -321,13 +284,13 @@ def degrade_adaptive_blur(frame: np.ndarray, importance: np.ndarray, block_size:
     _check_frame(frame, importance, block_size, "importance")
     degradation_map = generate_degradation_map(importance, max_rounds)
     _check_rounds(degradation_map)
-    return _one_frame(frame, degradation_map, device, degrade_gaussian_fx_device, block_size), degradation_map
+    return _one_image(frame, degradation_map, device, degrade_gaussian_fx_device, block_size), degradation_map
 
 
 def _one_block(block: np.ndarray, value: int, device, fn) -> np.ndarray:
     if not isinstance(block, np.ndarray) or block.dtype != np.uint8 or block.ndim != 3 or block.shape[0] != block.shape[1]:
         raise ValueError("degrade: a block is a square uint8 (b,b,C) array")
-    return _one_frame(block, np.full((1, 1), int(value), np.int32), device, fn, block.shape[0])
+    return _one_image(block, np.full((1, 1), int(value), np.int32), device, fn, block.shape[0])
 
 
 def downscale_block(block: np.ndarray, scale: int, device="cuda:0") -> np.ndarray:
@@ -368,7 +331,7 @@ def degrade_frame(frame: np.ndarray, degradation_map: np.ndarray, block_size: in
     levels = np.asarray(degradation_map).astype(np.int32)
     if fn is degrade_gaussian_fx_device:
         _check_rounds(levels)
-    return _one_frame(frame, levels, device, fn, block_size)
+    return _one_image(frame, levels, device, fn, block_size)
 
 
 def degrade_video_adaptive(frames: Sequence[np.ndarray], importance_scores: Sequence[np.ndarray], block_size: int,
@@ -388,8 +351,7 @@ def degrade_video_adaptive(frames: Sequence[np.ndarray], importance_scores: Sequ
     levels = np.stack(maps).astype(np.int32)
     if fn is degrade_gaussian_fx_device:
         _check_rounds(levels)
-    dev = torch.device("cuda:0" if str(device) == "cuda" else device)
-    L.require_gpu(dev)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         out = fn(frames_to_device(frames, dev), torch.from_numpy(np.ascontiguousarray(levels)).to(dev), block_size)
         return frames_to_host(out), maps

@@ -67,12 +67,6 @@ def rgb_to_i420_device(frames_d: torch.Tensor, order: str = "rgb", out=None) -> 
 
 
 # ----------------------------------------------------------------------------- the reference's call surface
-def _device(device) -> torch.device:
-    dev = torch.device("cuda:0" if str(device) == "cuda" else device)
-    L.require_gpu(dev)
-    return dev
-
-
 def _chunk_frames(frame_shape, chunk_frames) -> int:
     if chunk_frames is not None:
         if int(chunk_frames) < 1:
@@ -84,7 +78,7 @@ def _chunk_frames(frame_shape, chunk_frames) -> int:
 
 def _i420_chunks(frames: Sequence[np.ndarray], device, chunk_frames):
     """Upload, convert and download `frames` a chunk at a time; yields host arrays [k, H*3//2, W]."""
-    dev = _device(device)
+    dev = L.resolve_device(device)
     step = _chunk_frames(frames[0].shape, chunk_frames)
     with torch.cuda.device(dev):
         for at in range(0, len(frames), step):
@@ -117,7 +111,7 @@ def write_y4m(frames: List[np.ndarray], y4m_path: str, framerate: float, device=
     height, width = frames[0].shape[:2]
     if height % 2 or width % 2:
         raise ValueError(f"write_y4m: I420 needs an even height and width, got {height} x {width}")
-    _device(device)
+    L.resolve_device(device)
     with open(y4m_path, "wb") as f:
         f.write(y4m_header(width, height, framerate))
         for planes in _i420_chunks(frames, device, chunk_frames):

@@ -32,14 +32,8 @@ from .recompose import frames_to_device
 from .tiler import _nearest_rows
 
 
-def _dev(device) -> torch.device:
-    dev = torch.device("cuda:0" if str(device) == "cuda" else device)
-    L.require_gpu(dev)
-    return dev
-
-
 def _sse(reference_frames, distorted_frames, device, masks=None):
-    dev = _dev(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         a, b = frames_to_device(list(reference_frames), dev), frames_to_device(list(distorted_frames), dev)
         if a.shape != b.shape:
@@ -102,7 +96,7 @@ def calculate_block_ssim(frames1: Sequence[np.ndarray], frames2: Sequence[np.nda
     """Per-block SSIM maps (utils.py:572-608), one (H // b, W // b) float32 array per frame pair."""
     if not len(frames1):
         return []
-    dev = _dev(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         m = block_ssim_device(frames_to_device(list(frames1), dev), frames_to_device(list(frames2), dev), block_size).cpu().numpy()
     return [m[i] for i in range(m.shape[0])]
@@ -219,7 +213,7 @@ def masked_ssim(ref: np.ndarray, dec: np.ndarray, mask: Optional[np.ndarray] = N
         raise ValueError(f"the luma SSIM needs 3-channel BGR frames, got {ref.shape[2]} channels")
     if mask is not None and np.asarray(mask).shape != ref.shape[:2]:
         raise ValueError(f"mask {np.asarray(mask).shape} does not match frame {ref.shape[:2]}")
-    dev = _dev(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         m = None if mask is None else masks_to_device([mask], ref.shape[:2], dev)
         return float(masked_ssim_device(frames_to_device([ref], dev), frames_to_device([dec], dev), m).cpu()[0])
@@ -233,7 +227,7 @@ def calculate_ssim(reference_frames: Sequence[np.ndarray], distorted_frames: Seq
         return []
     if any(p[0].shape != pairs[0][0].shape for p in pairs):
         raise ValueError("frame sequences differ in shape")
-    dev = _dev(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         a, b = frames_to_device([p[0] for p in pairs], dev), frames_to_device([p[1] for p in pairs], dev)
         return [float(v) for v in calculate_ssim_device(a, b, data_range).cpu()]
@@ -292,7 +286,7 @@ def apply_binary_mask(frame: np.ndarray, mask: np.ndarray, invert: bool = False,
     frame = np.asarray(frame)
     if frame.ndim != 3 or np.asarray(mask).shape != frame.shape[:2]:
         raise ValueError(f"mask {np.asarray(mask).shape} does not match frame {frame.shape}")
-    dev = _dev(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         out = apply_mask_device(frames_to_device([frame], dev), masks_to_device([mask], frame.shape[:2], dev), invert)
         return out[0].cpu().numpy()
@@ -317,7 +311,7 @@ def compute_mask_union_bbox(masks: Sequence[np.ndarray], width: int, height: int
     if not masks:
         return (0, 0, width, height)
     _chk_mask_shapes(masks, (height, width))
-    dev = _dev(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         boxes = mask_bbox_device(masks_to_device(masks, (height, width), dev)).cpu().numpy()
     return _padded_union_bbox(boxes, width, height, padding_ratio)
@@ -350,7 +344,7 @@ def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frame
     if any(r.shape != refs[0].shape for r in refs):
         raise ValueError("frame sequences differ in shape")
     _chk_mask_shapes([fg_masks[i] for i in idx], refs[0].shape[:2])
-    dev = _dev(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         a, b = frames_to_device(list(refs), dev), frames_to_device(list(decs), dev)          # uploaded once
         fg = masks_to_device([fg_masks[i] for i in idx], refs[0].shape[:2], dev)

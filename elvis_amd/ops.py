@@ -10,6 +10,7 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -56,6 +57,47 @@ def _chk_u8(*ts):
     for t in ts:
         if t.dtype != torch.uint8 or not t.is_contiguous() or not t.is_cuda:
             raise ValueError("expected contiguous CUDA uint8 tensors")
+
+
+# What the per-block families (classical.py, degrade.py) share; `who` is the family's message prefix.
+def _block_maps(map_d: torch.Tensor, n: int, who: str) -> torch.Tensor:
+    if map_d.dtype != torch.int32 or map_d.dim() != 3 or map_d.shape[0] != n or not map_d.is_cuda:
+        raise ValueError(f"{who}: the map must be a CUDA int32 tensor [n, by, bx]")
+    return map_d.contiguous()
+
+
+def _block_out(frames_d: torch.Tensor, block_size: int, out, who: str) -> torch.Tensor:
+    """`out` goes to the kernel as a bare pointer: it must be the frames' twin (shape, uint8, device, contiguous).  Rows
+    and columns past the last whole block are not written by the kernels: without `out` the result starts as a copy of the
+    frames when there are any; a given `out` keeps there what the caller put."""
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda \
+                or out.device != frames_d.device or out.shape != frames_d.shape:
+            raise ValueError(f"{who}: out must be a contiguous uint8 tensor of the frames' shape on the frames' device")
+        return out
+    h, w = frames_d.shape[1:3]
+    ragged = block_size > 0 and (h % block_size or w % block_size)
+    return frames_d.clone() if ragged else torch.empty_like(frames_d)
+
+
+def _check_image_grid(image: np.ndarray, maps: np.ndarray, block_size: int, who: str, what: str):
+    """One uint8 (H,W,C) image of whole blocks and its per-block array; `what` names the array, as "map {} does"."""
+    if image.dtype != np.uint8 or image.ndim != 3:
+        raise ValueError(f"{who} take uint8 (H,W,C) images")
+    h, w = image.shape[:2]
+    if h % block_size or w % block_size:
+        raise ValueError("Image dimensions must be divisible by block_size.")   # split_image_into_blocks, elvis.py:1376
+    if maps.shape != (h // block_size, w // block_size):
+        raise ValueError(f"{what.format(maps.shape)} not match the block grid {(h // block_size, w // block_size)}")
+
+
+def _one_image(image: np.ndarray, maps: np.ndarray, device, fn, *args) -> np.ndarray:
+    """fn(frames [1,H,W,C], map [1,by,bx], *args) for one host image and its int32 map: upload, run, download."""
+    dev = L.resolve_device(device)
+    with torch.cuda.device(dev):
+        img_d = torch.from_numpy(np.ascontiguousarray(image)[None]).to(dev)
+        map_d = torch.from_numpy(np.ascontiguousarray(maps.astype(np.int32))[None]).to(dev)
+        return fn(img_d, map_d, *args)[0].cpu().numpy()
 
 
 def recompose_u8(a, b, map_i32, block, thr, out=None, map_out=None, clamp_to=0):

@@ -285,7 +285,7 @@ def restore_with_sinsr_naive(frames: List[np.ndarray], device="cuda", seed: int 
     which runs the 4x net and resizes back).  Accepts and ignores unknown kwargs."""
     if not frames:
         return []
-    dev = torch.device("cuda:0" if str(device) == "cuda" else device)
+    dev = L.resolve_device(device)
     model = get_sinsr_model(dev, fp32=bool(kwargs.get("fp32", False)), cfg=kwargs.get("cfg"))
     t0 = tile_coords[0] if tile_coords else 0
     with torch.cuda.device(model.device):

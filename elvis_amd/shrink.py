@@ -210,12 +210,6 @@ def stretch_device(shrunk_d: torch.Tensor, masks_d: torch.Tensor, block_size: in
 
 
 # ----------------------------------------------------------------------------- the reference's call surface
-def _device(device) -> torch.device:
-    dev = torch.device("cuda:0" if str(device) == "cuda" else device)
-    L.require_gpu(dev)
-    return dev
-
-
 def _frame(frame, what: str) -> np.ndarray:
     f = np.asarray(frame)
     if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] not in (1, 3):
@@ -262,7 +256,7 @@ def apply_selective_removal(image: np.ndarray, frame_scores: np.ndarray, block_s
     if sc.size == 0:
         raise ValueError("apply_selective_removal: the frame is smaller than one block")
     topk_count(shrink_amount, sc.shape[1])
-    dev = _device(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         out, mask, _ = shrink_topk_device(_up(img[None], dev), _up(sc[None], dev), block_size, shrink_amount)
         mask_h = mask[0].cpu().numpy()
@@ -282,7 +276,7 @@ def stretch_frame(shrunk_frame: np.ndarray, binary_mask: np.ndarray, block_size:
     kept = int(m.size - m.sum())
     if kept != sby * sbx:
         raise ValueError(f"stretch_frame: cannot assign {sby * sbx} shrunk blocks to the {kept} positions the mask keeps")
-    dev = _device(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         return stretch_device(_up(f[None], dev), _up(m[None], dev), block_size, "flat")[0].cpu().numpy()
 
@@ -294,7 +288,7 @@ def _shrink_passes(frame, importance, block_size, shrink_amount, mode, device, w
         raise ValueError(f"{what}: the frame is smaller than one block")
     sc = _scores(importance, (by, bx), what)
     passes_target(by, bx, shrink_amount)
-    dev = _device(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         out, mask, src_of, ridx, counts = shrink_passes_device(_up(f[None], dev), _up(sc[None], dev), block_size,
                                                                shrink_amount, mode)
@@ -338,7 +332,7 @@ def stretch_frame_row_only(shrunk_frame: np.ndarray, removal_mask: np.ndarray, b
     m = _mask(removal_mask, "stretch_frame_row_only")
     if f.shape[0] % block_size or f.shape[1] % block_size:
         raise ValueError("Image dimensions must be divisible by block_size.")
-    dev = _device(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         return stretch_device(_up(f[None], dev), _up(m[None], dev), block_size, "rows")[0].cpu().numpy()
 
@@ -371,7 +365,7 @@ def stretch_frame_position_map(shrunk_frame: np.ndarray, removal_mask: np.ndarra
         raise ValueError(f"position_map {np.asarray(position_map).shape} does not match the shrunk grid {sgrid}")
     if grid[0] < 1 or grid[1] < 1:
         return np.zeros((grid[0] * block_size, grid[1] * block_size, f.shape[2]), np.uint8)
-    return _gather_host_map(f, position_map_to_src_of(position_map, grid), block_size, sgrid, _device(device))
+    return _gather_host_map(f, position_map_to_src_of(position_map, grid), block_size, sgrid, L.resolve_device(device))
 
 
 def _open_gap(g: np.ndarray, where) -> np.ndarray:
@@ -412,7 +406,7 @@ def stretch_frame_removal_indices(shrunk_frame: np.ndarray, removal_indices: lis
     src_of = removal_indices_to_src_of(removal_indices, sgrid)[:orig_blocks_y, :orig_blocks_x]
     if src_of.size == 0:
         return np.zeros((src_of.shape[0] * block_size, src_of.shape[1] * block_size, f.shape[2]), np.uint8)
-    return _gather_host_map(f, src_of, block_size, sgrid, _device(device))
+    return _gather_host_map(f, src_of, block_size, sgrid, L.resolve_device(device))
 
 
 def _uniform(arrays) -> bool:
@@ -442,7 +436,7 @@ def shrink_video_frames(frames: List[np.ndarray], importance_scores: List[np.nda
         raise ValueError("shrink_video_frames: the frame is smaller than one block")
     sc = np.stack([_scores(s, (by, bx), "shrink_video_frames") for _, s in pairs])
     passes_target(by, bx, shrink_amount)
-    dev = _device(device)
+    dev = L.resolve_device(device)
     with torch.cuda.device(dev):
         out, mask, _, _, _ = shrink_passes_device(frames_to_device(fs, dev), _up(sc, dev), block_size, shrink_amount, "rows")
         out_h, mask_h = out.cpu().numpy(), mask.cpu().numpy()
@@ -461,7 +455,7 @@ def stretch_video_frames(shrunken_frames: List[np.ndarray], removal_masks: List[
     for f in fs:
         if f.shape[0] % block_size or f.shape[1] % block_size:
             raise ValueError("Image dimensions must be divisible by block_size.")
-    dev = _device(device)
+    dev = L.resolve_device(device)
     groups = [range(len(fs))] if _uniform(fs) and _uniform(ms) else [[i] for i in range(len(fs))]
     out: List[np.ndarray] = []
     with torch.cuda.device(dev):

@@ -280,4 +280,11 @@ def test_degrade_out_must_match_the_frames(gpu_device):
                 call(o)
         good = torch.full_like(f, 7)
         assert call(good) is good
+    # the classical device forms take the same check: a host `out` is refused, not handed to the kernel
+    from elvis_amd import classical
+    f1 = torch.zeros((1, 8, 8, 3), dtype=torch.uint8, device=dev)
+    m1 = torch.ones((1, 2, 2), dtype=torch.int32, device=dev)
+    for fn in (classical.lanczos_restore_device, classical.unsharp_restore_device):
+        with pytest.raises(ValueError):
+            fn(f1, m1, 4, out=torch.zeros((1, 8, 8, 3), dtype=torch.uint8))
     torch.cuda.synchronize()
