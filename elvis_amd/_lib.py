@@ -93,6 +93,9 @@ SIGNATURES = {
     "elvis_shrink_passes_plan": [i32, i32, i32, i32, vp, vp, vp, i32],
     "elvis_shrink_select_passes": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_stretch_index": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_inpaint_workspace_bytes": [i32, i32, i32],
+    "elvis_inpaint_prepare": [vp, i32, vp, i32, i32, i32, vp],
+    "elvis_inpaint_fill": [vp, vp, i32, i32, i32, i32, vp, i32, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
@@ -128,6 +131,7 @@ def lib() -> C.CDLL:
         handle.elvis_groupnorm_workspace_floats.restype = C.c_size_t
         handle.elvis_swin_packed_bytes.restype = C.c_size_t
         handle.elvis_ssim_workspace_bytes.restype = C.c_size_t
+        handle.elvis_inpaint_workspace_bytes.restype = C.c_size_t
         if handle.elvis_abi_version() != 1:
             raise RuntimeError("libelvis_amd.so ABI version mismatch")
         _lib = handle

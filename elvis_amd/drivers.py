@@ -6,6 +6,8 @@
   restore_dct_adaptive             -  the DCT slot the reference never wrote, given the
                                       Blur driver's shape
   stretch_shrunk_frames            <- the ELVIS v1 client-side stretch loop   (elvis.py:4534-4580)
+  restore_shrunk_frames            <- the same loop and the CV2 inpaint loop after it (elvis.py:4534-4610), with the
+                                      build-defined wavefront Telea (inpaint.py) in cv2.inpaint's place
 
 Same arguments, file naming and errors as the reference: a directory of PNG frames (BGR on read) and a
 `(frames, blocks_y, blocks_x)` map; the Downsample driver writes `output_dir/<same names>`, the Blur /
@@ -66,6 +68,28 @@ def _stretch_shard(frames, maps, block_size, device, first_frame_index, fullres_
             for i in range(len(frames)):
                 save_mask(full_h[i], os.path.join(fullres_masks_dir, f"{first_frame_index + i + 1:05d}.png"))
         return frames_to_host(out)
+
+
+def _restore_shard(frames, maps, block_size, device, first_frame_index, stretched_dir=None, fullres_masks_dir=None, **kw):
+    """Stretch a run of decoded shrunk frames and inpaint their holes without leaving the device: the hole mask goes
+    from the gather to the inpainter as a resident tensor.  The stretched frames and the masks come down only where a
+    directory asks for them, under the global frame numbers."""
+    from .inpaint import inpaint_device
+    from .recompose import frames_to_device, frames_to_host
+    from .shrink import stretch_device
+    with torch.cuda.device(device):
+        fd = frames_to_device(frames, device)
+        md = torch.from_numpy(np.ascontiguousarray(np.asarray(maps) != 0).view(np.uint8)).to(device)
+        out, full = stretch_device(fd, md, block_size, "flat", fullres_mask=True)
+        names = [f"{first_frame_index + i + 1:05d}.png" for i in range(len(frames))]
+        if stretched_dir is not None:
+            for name, f in zip(names, frames_to_host(out)):
+                save_frame(f, os.path.join(stretched_dir, name))
+        if fullres_masks_dir is not None:
+            full_h = full.cpu().numpy()
+            for i, name in enumerate(names):
+                save_mask(full_h[i], os.path.join(fullres_masks_dir, name))
+        return frames_to_host(inpaint_device(out, full, out=out))
 
 
 def _shard_worker(shard_fn: ShardFn, in_dir: str, out_dir: str, names: Sequence[str], start: int, end: int,
@@ -245,6 +269,26 @@ def restore_dct_adaptive(
                       max(0, int(temporal_radius)), kw, "strength_maps", _shard_fn is not None)
 
 
+def _v1_clip(frames_dir: str, masks_npz: str, block_size: int):
+    """The removal masks of `masks_npz` and the names `00001.png` ... of the shrunk frames they belong to, checked:
+    every frame exists and holds exactly as many blocks as its mask keeps (`stretch_frame`'s rule)."""
+    masks = load_block_masks(masks_npz)
+    if masks.ndim != 3 or masks.shape[0] == 0:
+        raise ValueError(f"removal masks must be (frames, blocks_y, blocks_x); got {masks.shape}")
+    names = [f"{i + 1:05d}.png" for i in range(masks.shape[0])]
+    missing = [n for n in names if not os.path.isfile(os.path.join(frames_dir, n))]
+    if missing:
+        raise ValueError(f"No frame {missing[0]} in {frames_dir} ({len(missing)} of {len(names)} frames missing)")
+    from PIL import Image
+    for i, n in enumerate(names):
+        with Image.open(os.path.join(frames_dir, n)) as im:
+            w, h = im.size
+        kept = int(masks[i].size - np.count_nonzero(masks[i]))
+        if h % block_size or w % block_size or (h // block_size) * (w // block_size) != kept:
+            raise ValueError(f"{n}: a {h}x{w} frame does not hold the {kept} blocks of {block_size} its mask keeps")
+    return masks, names
+
+
 def stretch_shrunk_frames(
     frames_dir: str,
     masks_npz: str,
@@ -264,20 +308,7 @@ def stretch_shrunk_frames(
 
     Every frame must hold exactly as many blocks as its mask keeps (`stretch_frame`'s rule): ValueError otherwise,
     before anything is written."""
-    masks = load_block_masks(masks_npz)
-    if masks.ndim != 3 or masks.shape[0] == 0:
-        raise ValueError(f"removal masks must be (frames, blocks_y, blocks_x); got {masks.shape}")
-    names = [f"{i + 1:05d}.png" for i in range(masks.shape[0])]
-    missing = [n for n in names if not os.path.isfile(os.path.join(frames_dir, n))]
-    if missing:
-        raise ValueError(f"No frame {missing[0]} in {frames_dir} ({len(missing)} of {len(names)} frames missing)")
-    from PIL import Image
-    for i, n in enumerate(names):
-        with Image.open(os.path.join(frames_dir, n)) as im:
-            w, h = im.size
-        kept = int(masks[i].size - np.count_nonzero(masks[i]))
-        if h % block_size or w % block_size or (h // block_size) * (w // block_size) != kept:
-            raise ValueError(f"{n}: a {h}x{w} frame does not hold the {kept} blocks of {block_size} its mask keeps")
+    masks, names = _v1_clip(frames_dir, masks_npz, block_size)
     for d in (out_dir, fullres_masks_dir, block_masks_dir):
         if d is not None:
             os.makedirs(d, exist_ok=True)
@@ -289,4 +320,42 @@ def stretch_shrunk_frames(
     workers = gpus or (devs if _shard_fn is not None else devs[:1])
     _run_shards(_shard_fn or _stretch_shard, frames_dir, out_dir or frames_dir, names, chunk_for_devices(len(names), workers),
                 masks, block_size, 0, dict(fullres_masks_dir=fullres_masks_dir))
+    return masks
+
+
+def restore_shrunk_frames(
+    frames_dir: str,
+    masks_npz: str,
+    block_size: int,
+    out_dir: str,
+    stretched_dir: Optional[str] = None,
+    fullres_masks_dir: Optional[str] = None,
+    block_masks_dir: Optional[str] = None,
+    devices: Optional[Sequence[DeviceSpec]] = None,
+    *,
+    _shard_fn: Optional[ShardFn] = None,
+) -> np.ndarray:
+    """The whole ELVIS v1 client side over a directory (elvis.py:4534-4610): unpack the removal masks of `masks_npz`,
+    stretch the decoded shrunk frames `00001.png` ... of `frames_dir` (one per mask) and inpaint the holes - the
+    reference's `cv2.inpaint(frame, mask, 3, cv2.INPAINT_TELEA)` loop, here the build-defined wavefront Telea of
+    `inpaint.py` (not cv2's bytes).  The inpainted frames go to `out_dir` under the same names and
+    `frames_dir` is left as it is.  The hole masks stay on the device between the two steps; the stretched frames
+    (`stretched_dir`), the 0/255 masks at frame resolution (`fullres_masks_dir`) and at block resolution
+    (`block_masks_dir`) are written only where a directory is given.  Validation and sharding are those of
+    `stretch_shrunk_frames`: ValueError before anything is written, frames dealt by the `chunk_for_devices` rule,
+    one worker per GPU.  Returns the unpacked masks."""
+    if out_dir is None:
+        raise ValueError("restore_shrunk_frames: out_dir is required")
+    masks, names = _v1_clip(frames_dir, masks_npz, block_size)
+    for d in (out_dir, stretched_dir, fullres_masks_dir, block_masks_dir):
+        if d is not None:
+            os.makedirs(d, exist_ok=True)
+    if block_masks_dir is not None:
+        for i, n in enumerate(names):
+            save_mask((masks[i] * 255).astype(np.uint8), os.path.join(block_masks_dir, n))
+    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
+    gpus = [d for d in devs if d.type == "cuda"]
+    workers = gpus or (devs if _shard_fn is not None else devs[:1])
+    _run_shards(_shard_fn or _restore_shard, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
+                block_size, 0, dict(stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir))
     return masks

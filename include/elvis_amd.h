@@ -302,7 +302,8 @@ int elvis_swin_proj_mlp(const void* attn, const void* y, void* out, const void* 
                         int attn_pitch, int y_pitch, int out_pitch, float eps, elvis_stream_t stream);
 
 /* Normalised instantiation name (e.g. "swin_fused_kernel<192,2,1,true>", "dcnv2_tile_kernel<7>") of the last kernel that
- * elvis_window_attention, elvis_swin_*, elvis_dcnv2, elvis_block_gather_u8, or an entry point of csrc/norm.hip / csrc/misc.hip
+ * elvis_window_attention, elvis_swin_*, elvis_dcnv2, elvis_block_gather_u8, elvis_inpaint_prepare ("inpaint_scatter_kernel", its
+ * last), elvis_inpaint_fill ("inpaint_fill_kernel<3>"; unchanged when it launches nothing), or an entry point of csrc/norm.hip / csrc/misc.hip
  * (elvis_groupnorm_sums reports its gn_channel_sums_kernel, elvis_gn_partials_to_sums which of its two reductions it chose)
  * launched on the calling thread; "" before the first.  Static storage:
  * no allocation, no device synchronisation. */
@@ -498,6 +499,37 @@ int elvis_shrink_select_passes(const double* scores, uint8_t* mask, int32_t* src
  * itself raises when the kept count differs from sby * sbx: a precondition here, checked by the Python layer. */
 int elvis_stretch_index(const uint8_t* mask, int32_t* src_of, int n, int by, int bx, int sby, int sbx, int mode,
                         elvis_stream_t stream);
+
+/* ------------------------------------------------------------------ ELVIS v1 inpaint
+ * The step after the stretch: cv2.inpaint(stretched_frame, mask, inpaintRadius=3, flags=cv2.INPAINT_TELEA) in the
+ * reference (elvis.py:4601-4606; Presley's inpaint_with_opencv, presley.py:838-850).  This is a BUILD-DEFINED
+ * inpainter, "wavefront Telea": Telea's estimator and weights (radius 3) on a fill order a GPU can run - waves by the
+ * exact Euclidean distance to the nearest known pixel, every pixel of a wave computed from known pixels and earlier
+ * waves only.  It does not claim parity with cv2; DESIGN.md 7 is the contract, tests/_inpaint_ref.py states it in numpy
+ * and the kernels equal that bit for bit.
+ *
+ * Two calls per clip with one small download between them (the caller synchronises, no entry point does):
+ *   1. elvis_inpaint_prepare fills the workspace (elvis_inpaint_workspace_bytes bytes, 256-byte aligned).  Its first
+ *      h + w + 2 int32 are the number of hole pixels of every wave (entry 0 is 0) over the whole clip.
+ *   2. the caller copies those counts to the host (after the stream has finished the prepare) and passes the first
+ *      K + 1 of them, K = the last wave with pixels, to elvis_inpaint_fill: one launch per non-empty wave, one thread
+ *      per hole pixel.  A clip without holes needs no call (num_counts = 1 launches nothing).
+ * n * h * w < 2^31, h and w at most 32767. */
+
+/* Host only: bytes of the workspace of an [n, h, w] clip; 0 for a shape the entry points reject. */
+size_t elvis_inpaint_workspace_bytes(int n, int h, int w);
+
+/* mask u8, non-zero = hole (as for cv2.inpaint): [n, h, w] with block_size 0, or [n, h / block_size, w / block_size]
+ * expanded over whole blocks with block_size > 0 (pixels past the last whole block are known).  Launches
+ * inpaint_rows_kernel, inpaint_columns_kernel (the exact distance transform, T and the wave of every pixel, the
+ * histogram), inpaint_scan_kernel and inpaint_scatter_kernel (the per-wave pixel lists). */
+int elvis_inpaint_prepare(const uint8_t* mask, int block_size, void* workspace, int n, int h, int w, elvis_stream_t stream);
+
+/* Fills the holes of frames u8 [n, h, w, c] (c in {1, 3}) IN PLACE from the workspace of the same clip.  The bytes
+ * under the holes are never read, known pixels are never written; frames without a hole or without a known pixel
+ * stay as they are.  wave_counts_host: HOST int32 [num_counts], the first num_counts entries of the workspace. */
+int elvis_inpaint_fill(uint8_t* frames, const void* workspace, int n, int h, int w, int c, const int32_t* wave_counts_host,
+                       int num_counts, elvis_stream_t stream);
 
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
