@@ -227,8 +227,8 @@ def mutant_cases():
 
 
 def cases():
-    """name -> (frames [n,H,W,C] u8, masks [n,H,W] u8): the matrix of tests/test_gpu_inpaint.py.  Frames are at most
-    96 x 128."""
+    """name -> (frames [n,H,W,C] u8, masks [n,H,W] u8): the matrix of tests/test_gpu_inpaint.py.  The block cases are at
+    most 96 x 128; the preparation cases (`preparation_cases`) reach 300 rows, 513 columns and 130 x 125."""
     out = {}
     rng = np.random.default_rng(11)
     for b in (8, 16):
@@ -260,4 +260,62 @@ def cases():
     mixed[2, 3:38, 5:47] = 255
     mixed[3] = _blocks(40, 50, 8, [(1, 1), (3, 4)])
     out["mixed_clip"] = (np.stack([make_image(40, 50, 3, seed=30 + i) for i in range(4)]), mixed)
+    out.update(preparation_cases())
     return out
+
+
+LOCAL_BINS, THREADS = 64, 256        # kLocalBins and the workgroup size of csrc/inpaint.hip (the ledger reads them there)
+
+
+def preparation_cases():
+    """The cases derived from the constants of the preparation kernels: waves at and past kLocalBins (global atomics in
+    the histogram and the scatter), rows wider than a workgroup (a thread owns 2 or 3 pixels of a row), h + w + 2 bins
+    past 256 (a thread of the scan owns 2 bins), frames of one row and of one column.
+
+    A row or column with a single known pixel fills with nearly constant values (2 to 3 distinct bytes): those cases test
+    the preparation pass and the lists, not the estimator.  The textured ones (`wide_5x257`, `deep_70x40`, `bins_25x`)
+    test the estimator at these shapes too."""
+    out = {}
+    rng = np.random.default_rng(12)
+
+    def one_known(h, w, y, x, c=3, seed=0):
+        m = np.full((1, h, w), 255, np.uint8)
+        m[0, y, x] = 0
+        return make_image(h, w, c, seed=seed)[None], m
+
+    out["row_1x300_left"] = one_known(1, 300, 0, 0, seed=41)            # 299 waves, 303 bins, two pixels per thread
+    out["row_1x300_mid"] = one_known(1, 300, 0, 137, seed=42)           # the known pixel is the second of a thread's run
+    out["row_1x65"] = one_known(1, 65, 0, 0, seed=43)                   # waves 1..64: exactly one pixel on the global-atomic path
+    out["row_1x64"] = one_known(1, 64, 0, 0, seed=44)                   # its twin: no pixel on that path
+    out["col_300x1"] = one_known(300, 1, 299, 0, seed=45)
+    m = np.full((1, 3, 513), 255, np.uint8)                             # three pixels per thread; the outer rows have no known pixel
+    m[0, 1, [0, 2, 3, 5, 256, 257, 512]] = 0
+    out["wide_3x513"] = (make_image(3, 513, 3, seed=46)[None], m)
+    m = ((rng.random((1, 5, 257)) < 0.6) * 255).astype(np.uint8)        # two pixels per thread, the trailing threads own empty runs
+    m[0, 2] = 255
+    m[0, 3] = 255
+    m[0, 3, 256] = 0
+    out["wide_5x257"] = (make_image(5, 257, 3, seed=47)[None], m)
+    m = np.full((2, 70, 40), 255, np.uint8)                             # both frames add to the same waves >= 64
+    m[0, 0] = 0                                                         # frame 0: row 0 known, waves 1..69
+    m[1, 69, ::2] = 0                                                   # frame 1: every second pixel of the last row, waves 1..70
+    deep = np.stack([make_image(70, 40, 3, seed=48), make_image(70, 40, 3, seed=49)])
+    out["deep_70x40"] = (deep, m)
+    out["deep_70x40_c1"] = (np.ascontiguousarray(deep[..., 1:2]), m)
+    for w in (124, 125):                                                # h + w + 2 = 256 and 257
+        m = np.full((1, 130, w), 255, np.uint8)
+        m[0, 0, ::3] = 0
+        out[f"bins_{130 + w + 2}"] = (make_image(130, w, 1, seed=50 + w)[None], m)
+    return out
+
+
+def wave_counts(masks):
+    """int64 [h + w + 2]: per wave, the hole pixels of the frames that have a known pixel - the first h + w + 2 int32 of
+    the workspace after elvis_inpaint_prepare (include/elvis_amd.h)."""
+    masks = np.asarray(masks) != 0
+    n, h, w = masks.shape
+    counts = np.zeros(h + w + 2, np.int64)
+    for hole in masks:
+        if hole.any() and not hole.all():
+            counts += np.bincount(level_set(hole)[1][hole], minlength=h + w + 2)
+    return counts

@@ -53,7 +53,33 @@ def test_device_equals_the_numpy_statement(gpu_device, name):
     assert _launch() == f"inpaint_fill_kernel<{frames.shape[3]}>"
 
 
-@pytest.mark.parametrize("name", ["merged_2_3_L", "odd_random60", "mixed_clip", "interior_b8_c1"])
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_prepare_counts_the_pixels_of_every_wave(gpu_device, name):
+    """The first h + w + 2 int32 of the workspace (include/elvis_amd.h) against np.bincount of the reference's wave index
+    over the hole pixels of the frames that have a known pixel.  Nothing else of the workspace is read: its layout is
+    not ABI."""
+    frames, masks = CASES[name]
+    n, h, w = masks.shape
+    bins = h + w + 2
+    want = R.wave_counts(masks)
+    nbytes = _lib.lib().elvis_inpaint_workspace_bytes(n, h, w)
+    assert nbytes >= 4 * bins
+    md = _dev(masks, gpu_device)
+    for sentinel in (0x00, 0xFF):                                        # whatever the workspace held before
+        ws = torch.full((nbytes,), sentinel, dtype=torch.uint8, device=gpu_device)
+        assert ws.data_ptr() % 256 == 0
+        _lib.check(_lib.lib().elvis_inpaint_prepare(_lib.ptr(md), 0, _lib.ptr(ws), n, h, w, torch.cuda.current_stream(gpu_device).cuda_stream),
+                   gpu_device)
+        assert _launch() == "inpaint_scatter_kernel"
+        got = ws[:4 * bins].view(torch.int32).cpu().numpy()
+        assert got.shape == want.shape and np.array_equal(got, want), \
+            f"{name}: first difference at wave {int(np.flatnonzero(got != want)[0])}: device {got[got != want][:4]} reference {want[got != want][:4]}"
+        deepest = int(np.flatnonzero(want)[-1]) if want.any() else 0
+        assert got[0] == 0 and not got[deepest + 1:].any()
+    assert np.array_equal(md.cpu().numpy(), masks)
+
+
+@pytest.mark.parametrize("name", ["merged_2_3_L", "odd_random60", "mixed_clip", "interior_b8_c1", "deep_70x40", "wide_3x513"])
 def test_in_place_garbage_under_the_holes_and_guarded_out(gpu_device, name):
     frames, masks = CASES[name]
     ref = expected(name)

@@ -116,8 +116,11 @@ def test_every_mutant_gives_other_bytes_on_its_case(mutant):
 def test_the_case_list_covers_the_matrix():
     cases = R.cases()
     assert {f.shape[3] for f, _ in cases.values()} == {1, 3}
-    assert all(f.shape[1] <= 96 and f.shape[2] <= 128 and f.dtype == m.dtype == np.uint8 and m.shape == f.shape[:3]
-               for f, m in cases.values())
+    prep = R.preparation_cases()
+    assert set(prep) < set(cases) and all(np.array_equal(cases[k][0], prep[k][0]) and np.array_equal(cases[k][1], prep[k][1]) for k in prep)
+    assert all(f.dtype == m.dtype == np.uint8 and m.shape == f.shape[:3] for f, m in cases.values())
+    assert all(f.shape[1] <= 96 and f.shape[2] <= 128 for k, (f, m) in cases.items() if k not in prep)
+    assert all(f.shape[1] <= 300 and f.shape[2] <= 513 and f.shape[1] * f.shape[2] <= 130 * 125 for f, m in prep.values())
     assert set(np.unique(cases["mask_values_1_2_255"][1])) == {0, 1, 2, 255}
     for name in ("corners", "edges"):
         m = cases[name][1][0] != 0
