@@ -31,8 +31,10 @@ from .shrink import (apply_selective_removal, block_gather_device, shrink_frame_
                      stretch_frame_removal_indices, stretch_frame_row_only, stretch_index_device, stretch_video_frames)
 from .inpaint import (inpaint_blocks_device, inpaint_device, inpaint_frame, inpaint_with_opencv,  # noqa: F401
                       stretch_and_inpaint_device)
-from .drivers import (restore_blur_adaptive, restore_dct_adaptive, restore_downsampled_with_sinsr,  # noqa: F401
-                      restore_shrunk_frames, stretch_shrunk_frames)
+from .complexity import (BlockComplexity, EVCAConfig, analyze_frames, block_complexity_device,  # noqa: F401
+                         removability_from_complexity, resize_masks_nearest)
+from .drivers import (calculate_removability_scores_from_frames, restore_blur_adaptive, restore_dct_adaptive,  # noqa: F401
+                      restore_downsampled_with_sinsr, restore_shrunk_frames, stretch_shrunk_frames)
 from .restore import (get_sinsr_model, get_sinsr_upsample_fn, restore_frames_blur,  # noqa: F401
                       restore_frames_dct, restore_frames_rounds, restore_frames_sinsr,
                       restore_with_sinsr_naive)

@@ -96,6 +96,7 @@ SIGNATURES = {
     "elvis_inpaint_workspace_bytes": [i32, i32, i32],
     "elvis_inpaint_prepare": [vp, i32, vp, i32, i32, i32, vp],
     "elvis_inpaint_fill": [vp, vp, i32, i32, i32, i32, vp, i32, vp],
+    "elvis_block_complexity_f64": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],

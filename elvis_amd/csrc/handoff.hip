@@ -3,22 +3,7 @@
 // presley.py:590-599).  Integer arithmetic only (OpenCV 4.x RGB8toYUV420pInvoker, 20-bit fixed point); memory-bound:
 // 6 bytes read and 3 written per 2x1 pixels, no LDS, no atomics.
 #include "common.h"
-
-#define I420_SHIFT 20
-#define I420_HALF (1 << (I420_SHIFT - 1))
-
-// 900726 * 255 + (1 << 19) + (16 << 20) = 247 510 922 and 460324 * 255 + (1 << 19) + (128 << 20) = 252 124 636 are the
-// largest sums, 128 << 20 less 460323 * 255 the smallest: int32 holds them all, every sum is positive and every result
-// lies in [16, 240] - saturate_cast has nothing to do.
-__device__ __forceinline__ uint8_t i420_y(int r, int g, int b) {
-    return (uint8_t)((269484 * r + 528482 * g + 102760 * b + I420_HALF + (16 << I420_SHIFT)) >> I420_SHIFT);
-}
-__device__ __forceinline__ uint8_t i420_u(int r, int g, int b) {
-    return (uint8_t)((-155188 * r - 305135 * g + 460324 * b + I420_HALF + (128 << I420_SHIFT)) >> I420_SHIFT);
-}
-__device__ __forceinline__ uint8_t i420_v(int r, int g, int b) {
-    return (uint8_t)((460324 * r - 385875 * g - 74448 * b + I420_HALF + (128 << I420_SHIFT)) >> I420_SHIFT);
-}
+#include "i420.h"
 
 // One lane per strip of 2 rows x 8 pixels; consecutive lanes take consecutive strips of a row pair, then the next row
 // pair, then the next frame, so a wave's loads and stores are contiguous.  WIDE (w % 4 == 0, src and dst 4-byte aligned)

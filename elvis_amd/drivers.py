@@ -8,6 +8,9 @@
   stretch_shrunk_frames            <- the ELVIS v1 client-side stretch loop   (elvis.py:4534-4580)
   restore_shrunk_frames            <- the same loop and the CV2 inpaint loop after it (elvis.py:4534-4610), with the
                                       build-defined wavefront Telea (inpaint.py) in cv2.inpaint's place
+  calculate_removability_scores_from_frames
+                                   <- calculate_removability_scores (elvis.py:968-1224) from frames and masks in memory,
+                                      with the build-defined block complexity (complexity.py) in EVCA's place
 
 Same arguments, file naming and errors as the reference: a directory of PNG frames (BGR on read) and a
 `(frames, blocks_y, blocks_x)` map; the Downsample driver writes `output_dir/<same names>`, the Blur /
@@ -359,3 +362,21 @@ def restore_shrunk_frames(
     _run_shards(_shard_fn or _restore_shard, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
                 block_size, 0, dict(stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir))
     return masks
+
+
+def calculate_removability_scores_from_frames(frames, foreground_masks, block_size: int, alpha: float = 0.5,
+                                              smoothing_beta: float = 1, device="cuda:0", *, order: str = "bgr",
+                                              chunk_frames: Optional[int] = None) -> np.ndarray:
+    """The server side's first stage from frames in memory: stands in for `calculate_removability_scores`
+    (elvis.py:968-1224), which runs EVCA and UFO as outside programs over files and then combines their outputs
+    (elvis.py:1159-1218).  Here `analyze_frames` gives the SC / TC maps on the device in EVCA's place
+    (elvis.py:1014-1055 and the CSV reads of :1160-1170) and `removability_from_complexity` is the reference's own
+    combination (elvis.py:1172-1218).  UFO stays outside: `foreground_masks` are its masks, one 2-D array of any size
+    (0 = background) or None per frame, or None for no masks at all.  `frames` is a uint8 clip [F,H,W,C] (or a list of
+    frames), BGR as the reference holds decoded frames (`order`).  Returns float64 [F, H // block_size,
+    W // block_size] in [0, 1], what `apply_selective_removal` and the shrinks take per frame as it is.
+    EVCA'S PIXELS ARE NOT REPRODUCED: the maps are the build-defined block complexity of complexity.py (DESIGN.md 7);
+    what is pinned against the reference's own code is the combination after them."""
+    from .complexity import EVCAConfig, analyze_frames, removability_from_complexity
+    maps = analyze_frames(frames, EVCAConfig(block_size=block_size), device, order=order, chunk_frames=chunk_frames)
+    return removability_from_complexity(maps.SC, maps.TC, foreground_masks, alpha, smoothing_beta)

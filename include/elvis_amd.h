@@ -531,6 +531,34 @@ int elvis_inpaint_prepare(const uint8_t* mask, int block_size, void* workspace, 
 int elvis_inpaint_fill(uint8_t* frames, const void* workspace, int n, int h, int w, int c, const int32_t* wave_counts_host,
                        int num_counts, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ block complexity (complexity.hip)
+ * The first server-side stage: the per-block spatial (SC) and temporal (TC) complexity maps that the reference takes
+ * from EVCA - elvis.py:968-1224 runs it as a subprocess and reads evca_SC_blocks.csv / evca_TC_blocks.csv,
+ * presley.py:202 calls analyze_frames(frames, EVCAConfig(block_size=...)) and reads .SC and .TC.  EVCA is available
+ * neither to the reference tree nor to this build, so this is a BUILD-DEFINED analyser behind that call surface: a
+ * DCT-energy block complexity in the published VCA form.  The contract below is stated in numpy float64 in
+ * tests/_complexity_ref.py and the kernel agrees with it to 1e-9 * max(1, |value|); it does not claim EVCA's pixels.
+ *
+ *   frames  u8 [n, h, w, c], c in {1, 3}; block B in {8, 16, 32}; By = h / B, Bx = w / B (floored).  Rows and columns
+ *           past the last whole block belong to no block and are never read (elvis.py:1163-1164).
+ *   prev    NULL, or u8 [h, w, c]: the frame before frames[0].
+ *   luma    c == 1: the byte.  c == 3: the Y of elvis_rgb_to_i420_u8 above (the same device function), order 0 = RGB,
+ *           1 = BGR.
+ *   dct     f64 [B, B], built by the host: dct[k][m] = s_k cos(pi (2m + 1) k / 2B), s_0 = sqrt(1 / B), s_k = sqrt(2 / B).
+ *   weight  f64 [B, B], built by the host: weight[i][j] = exp(|(i j / B^2)^2 - 1|), weight[0][0] = 0 (no DC term).
+ *   SC      of a block X (B x B luma, integers): X' = X - X[0][0]; Cf = D X' D^T in float64;
+ *           SC = (sum_ij weight[i][j] |Cf[i][j]|) / B^2.  A flat block gives exactly 0.0.
+ *   TC      of frame f against its predecessor p (frames[f - 1]; prev for f = 0): E = X_f - X_p in integers,
+ *           E' = E - E[0][0], TC = (sum weight |D E' D^T|) / B^2.  A block whose luma did not change gives exactly 0.0;
+ *           without a predecessor TC[0] is 0.0 everywhere.
+ *   sc, tc  f64 [n, By, Bx], dense.  Nothing else is written.  No atomics and a fixed summation order: the same input
+ *           gives the same bytes, whatever n it is analysed with.
+ * ELVIS_E_INVALID: a block other than 8, 16, 32; c other than 1, 3; order other than 0, 1; h < block or w < block; a
+ * null frames / dct / weight / sc / tc.  n == 0 is a no-op. */
+int elvis_block_complexity_f64(const uint8_t* frames, const uint8_t* prev, const double* dct, const double* weight,
+                               double* sc, double* tc, int n, int h, int w, int c, int order, int block,
+                               elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
