@@ -33,6 +33,8 @@ from .inpaint import (inpaint_blocks_device, inpaint_device, inpaint_frame, inpa
                       stretch_and_inpaint_device)
 from .complexity import (BlockComplexity, EVCAConfig, analyze_frames, block_complexity_device,  # noqa: F401
                          removability_from_complexity, resize_masks_nearest)
+from .lpips import (LpipsAlex, calculate_lpips, calculate_lpips_per_frame, get_lpips_model,  # noqa: F401
+                    load_lpips_state_dict, lpips_device)
 from .drivers import (calculate_removability_scores_from_frames, restore_blur_adaptive, restore_dct_adaptive,  # noqa: F401
                       restore_downsampled_with_sinsr, restore_shrunk_frames, stretch_shrunk_frames)
 from .restore import (get_sinsr_model, get_sinsr_upsample_fn, restore_frames_blur,  # noqa: F401

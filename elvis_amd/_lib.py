@@ -97,6 +97,11 @@ SIGNATURES = {
     "elvis_inpaint_prepare": [vp, i32, vp, i32, i32, i32, vp],
     "elvis_inpaint_fill": [vp, vp, i32, i32, i32, i32, vp, i32, vp],
     "elvis_block_complexity_f64": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_lpips_stem_u8": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_lpips_conv5_f32": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "elvis_lpips_maxpool_f32": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_lpips_distance_workspace_bytes": [i32, i32, i32],
+    "elvis_lpips_distance_f64": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
@@ -133,6 +138,7 @@ def lib() -> C.CDLL:
         handle.elvis_swin_packed_bytes.restype = C.c_size_t
         handle.elvis_ssim_workspace_bytes.restype = C.c_size_t
         handle.elvis_inpaint_workspace_bytes.restype = C.c_size_t
+        handle.elvis_lpips_distance_workspace_bytes.restype = C.c_size_t
         if handle.elvis_abi_version() != 1:
             raise RuntimeError("libelvis_amd.so ABI version mismatch")
         _lib = handle

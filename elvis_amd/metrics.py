@@ -326,10 +326,15 @@ def metric_frame_indices(frame_count: int, metric_stride: int) -> List[int]:
 
 
 def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frames: Sequence[np.ndarray],
-                           fg_masks: Sequence[np.ndarray], metric_stride: int = 1, device="cuda:0") -> Dict[str, Dict[str, float]]:
+                           fg_masks: Sequence[np.ndarray], metric_stride: int = 1, device="cuda:0",
+                           lpips_model=None) -> Dict[str, Dict[str, float]]:
     """The numeric core of _evaluate_single_video_metrics (elvis.py:3799-3878): masked PSNR, SSIM and MSE of the
-    sampled frames, foreground (inside fg_masks) and background (outside), each as _mean and _std.  Bitrate, LPIPS,
-    VMAF and FVMD keys are not produced.  Per-frame MSE is a float32 number, as the reference's is (see below)."""
+    sampled frames, foreground (inside fg_masks) and background (outside), each as _mean and _std.  Bitrate, VMAF and
+    FVMD keys are not produced.  Per-frame MSE is a float32 number, as the reference's is (see below).
+    With `lpips_model` (an `elvis_amd.lpips.LpipsAlex` on `device`) both regions gain `lpips_mean` / `lpips_std` as
+    elvis.py:3853-3893 forms them, on the tensors already uploaded: the foreground from the fg-masked frames cropped to
+    the ROI around the union of all foreground masks (elvis.py:3639-3646), the background from the bg-masked whole
+    frames.  An ROI under 31 x 31 raises ValueError.  Without it (None) the result is what it was."""
     if metric_stride < 1:
         raise ValueError("metric_stride must be at least 1")
     count = min(len(reference_frames), len(decoded_frames))
@@ -353,6 +358,12 @@ def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frame
         # 3846-3852).  Every foreground mask lies inside that ROI, so masked sums and counts over the ROI equal those over
         # the frame, and _masked_ssim crops to the mask's own box whichever it is given: no crop copy is needed.
         result = {}
+        roi = None
+        if lpips_model is not None:
+            from .lpips import lpips_device
+            h, w = refs[0].shape[:2]
+            bx, by, bw, bh = compute_mask_union_bbox(list(fg_masks[:count]), w, h, device=dev)
+            roi = (by, min(h, by + max(1, bh)), bx, min(w, bx + max(1, bw)))
         for region, m in (("foreground", fg), ("background", bg)):
             sse, cnt = (t.cpu().numpy() for t in ops.sse_u8(a, b, m))
             ssim = masked_ssim_device(a, b, m).cpu().numpy()
@@ -364,4 +375,7 @@ def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frame
             psnr = [100.0 if k == 0 or e < 1e-10 else float(min(20.0 * math.log10(255.0 / math.sqrt(e)), 100.0)) for e, k in zip(mse, cnt)]
             result[region] = {f"{name}_{stat}": float(getattr(np, stat)(vals))
                               for name, vals in (("psnr", psnr), ("ssim", [float(v) for v in ssim]), ("mse", mse)) for stat in ("mean", "std")}
+            if lpips_model is not None:
+                scores = lpips_device(a, b, lpips_model, masks=m, rect=roi if region == "foreground" else None, order="bgr").cpu().numpy()
+                result[region]["lpips_mean"], result[region]["lpips_std"] = float(np.mean(scores)), float(np.std(scores))
         return result

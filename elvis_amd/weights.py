@@ -337,3 +337,21 @@ def make_deblur_weights(cfg: SwinDeblurConfig = SwinDeblurConfig(), seed: int = 
     blocks("dec1", C, cfg.blocks[0])
     I.conv("out", C, 3, 3, gain=0.3)
     return I.sd
+
+
+# ----------------------------------------------------------------------------- LPIPS (AlexNet)
+LPIPS_CONVS = ((0, 3, 64, 11), (3, 64, 192, 5), (6, 192, 384, 3), (8, 384, 256, 3), (10, 256, 256, 3))   # features index, cin, cout, k
+LPIPS_TAP_CHANNELS = (64, 192, 384, 256, 256)
+
+
+def make_lpips_weights(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded synthetic weights of the LPIPS AlexNet slot (elvis_amd.lpips): the five convs as torchvision's
+    `features.{0,3,6,8,10}.{weight,bias}` (He-scaled, so that activations survive five ReLUs) and the five non-negative
+    1x1 weightings as `lin{0..4}.model.1.weight` of shape [1, C, 1, 1].  The package's trained weights are not
+    available to this build; a real state_dict goes through `lpips.load_lpips_state_dict`."""
+    I = _Init(seed + 303)
+    for idx, cin, cout, k in LPIPS_CONVS:
+        I.conv(f"features.{idx}", cin, cout, k, gain=math.sqrt(2.0))
+    for tap, c in enumerate(LPIPS_TAP_CHANNELS):
+        I.sd[f"lin{tap}.model.1.weight"] = I.randn(1, c, 1, 1).abs() / math.sqrt(c)
+    return I.sd

@@ -559,6 +559,51 @@ int elvis_block_complexity_f64(const uint8_t* frames, const uint8_t* prev, const
                                double* sc, double* tc, int n, int h, int w, int c, int order, int block,
                                elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ LPIPS, AlexNet (lpips.hip)
+ * The perceptual distance of the evaluation report, which the reference takes from lpips.LPIPS(net='alex') for every
+ * sampled frame (elvis.py:437-447, 3163-3195, 3887-3893; presley.py:329-357).  The package and its weights are available
+ * neither to the reference tree nor to this build, so this is a BUILD-DEFINED restatement behind that call surface,
+ * stated in torch float64 in tests/_lpips_ref.py.  It does not claim parity with the lpips package.
+ *
+ *   stem      x = ((byte / 127.5 - 1) - shift_c) / scale_c in RGB order, shift (-0.030, -0.088, -0.188), scale (0.458,
+ *             0.448, 0.450); the byte of a pixel whose mask is 0 is 0 (a masked pixel is affine(0), not 0); the conv's
+ *             zero padding is 0 after the affine.  conv 3 -> 64, 11x11, stride 4, pad 2, ReLU      -> tap 0
+ *   max-pool  3x3 stride 2, no padding, floor
+ *   conv      64 -> 192, 5x5, pad 2, ReLU                                                          -> tap 1
+ *   max-pool  the same; then conv 192 -> 384, 384 -> 256, 256 -> 256, 3x3, pad 1, ReLU (elvis_conv2d) -> taps 2, 3, 4
+ *   distance  per tap and pixel xh = x / (sqrt(sum_c x^2) + 1e-10), yh likewise, v = sum_c w_c (xh_c - yh_c)^2 in fp32
+ *             in a fixed order; the tap's value is the mean of v over its pixels, summed and divided in float64; the
+ *             score is the sum of the five tap values in tap order.
+ * fp32 with fp32 accumulation throughout.  Activations are NHWC fp32 [n, h, w, pitch], 16-byte aligned, the pitch a
+ * multiple of 8.  No atomics: a frame's result does not depend on n or on how a clip is cut into calls.  Every entry
+ * point returns ELVIS_E_INVALID before any launch for a null pointer, a bad order, a rect outside the frame or under
+ * 31 x 31, and a pitch that is not a multiple of 8 (or smaller than the channel count); n == 0 is a no-op. */
+
+/* elvis.py:3163-3195 (calculate_lpips_per_frame: the BGR -> RGB flip, / 127.5 - 1, and the net's scaling layer and first
+ * conv).  frames u8 [n, h, w, 3], order 0 = RGB, 1 = BGR; mask u8 [n, h, w] or null (0: the pixel's three bytes are
+ * taken as 0, elvis.py:615-624); the network sees rows y0 .. y1 - 1, columns x0 .. x1 - 1 of the masked frame (the
+ * reference's roi_slice crop, elvis.py:3853-3854) - no byte outside the rect is read.  weight f32 [363][64] with row
+ * (ky 11 + kx) 3 + c, c in RGB order; bias f32 [64]; out f32 [n, ho, wo, out_pitch], ho = (y1 - y0 - 7) / 4 + 1. */
+int elvis_lpips_stem_u8(const uint8_t* frames, const uint8_t* mask, const float* weight, const float* bias, float* out,
+                        int n, int h, int w, int y0, int y1, int x0, int x1, int order, int out_pitch,
+                        elvis_stream_t stream);
+/* elvis.py:3163-3195 (the net's second conv).  x f32 [n, h, w, in_pitch], 64 channels; weight f32 [1600][192] with row
+ * (ky 5 + kx) 64 + c; bias f32 [192]; out f32 [n, h, w, out_pitch]: relu(conv 5x5 pad 2 + bias). */
+int elvis_lpips_conv5_f32(const float* x, const float* weight, const float* bias, float* out, int n, int h, int w,
+                          int in_pitch, int out_pitch, elvis_stream_t stream);
+/* elvis.py:3163-3195 (the net's max-pools).  x f32 [n, h, w, in_pitch] -> out f32 [n, (h - 3) / 2 + 1, (w - 3) / 2 + 1,
+ * out_pitch], the first c channels (c a multiple of 4; h, w >= 3). */
+int elvis_lpips_maxpool_f32(const float* x, float* out, int n, int h, int w, int c, int in_pitch, int out_pitch,
+                            elvis_stream_t stream);
+/* elvis.py:3163-3195: bytes of the workspace elvis_lpips_distance_f64 needs for n feature maps of h x w pixels (one
+ * float64 partial sum per 64 pixels); 0 for a bad shape. */
+size_t elvis_lpips_distance_workspace_bytes(int n, int h, int w);
+/* elvis.py:3163-3195 (the net's normalize_tensor, squared difference, 1x1 weighting and spatial average of one tap).
+ * x, y f32 [n, h, w, pitch] with c <= 384 channels; weight f32 [c]; out f64 [n]: the tap's value, added to out where
+ * accumulate is 1 and stored where it is 0.  Two launches: partial sums per workgroup, then their sum in index order. */
+int elvis_lpips_distance_f64(const float* x, const float* y, const float* weight, void* workspace, double* out, int n,
+                             int h, int w, int c, int pitch, int accumulate, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
