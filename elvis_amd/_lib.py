@@ -102,6 +102,8 @@ SIGNATURES = {
     "elvis_lpips_maxpool_f32": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_lpips_distance_workspace_bytes": [i32, i32, i32],
     "elvis_lpips_distance_f64": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_png_stats": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_png_pack": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],

@@ -1,0 +1,491 @@
+// Lossless PNG encoding on the device (include/elvis_amd.h "PNG writer"): row filters and the filter choice,
+// symbol statistics, Huffman bit packing, Adler-32 partials and the chunk CRC-32s.  The host only plans the layout between
+// the two phases (elvis_amd/png.py); tests/_png_ref.py states the stream in numpy and Python ints, and the files written
+// here equal that statement bit for bit.
+//
+//   png_stats_kernel   phase 1: a workgroup per (frame, segment).  Rows are staged in LDS (the current row and the raw row
+//                      above it, tiles of kPngTile bytes with a bpp-byte halo on the left), the five filter costs are
+//                      reduced per row, the chosen type is written, and the filtered bytes (type bytes included) go into
+//                      a 256-bin LDS histogram and the segment's Adler partial.
+//   png_pack_kernel    phase 2: a workgroup per (frame, segment) owns the segment's IDAT chunk.  It re-filters the rows
+//                      from the input (no filtered stream is ever stored), looks the codes up in an LDS table, gets every
+//                      symbol's bit offset from a workgroup scan of the code lengths and ORs the bits into an LDS bit buffer
+//                      that mirrors the dword grid of the output; whole dwords go out with dword stores, the bytes of a
+//                      dword that the chunk shares with its neighbour with byte stores.  No global atomics.
+//   png_crc_kernel     phase 2: a workgroup per chunk; every lane takes a slice, the slices are combined with x^(8 len) mod P.
+//
+// Every global store of phase 2 is clipped to the chunk's own byte range and to the output buffer, and every code length
+// is read through a 4-bit mask, so tables that disagree with the plan give a wrong file, never a write elsewhere.
+#include "common.h"
+
+namespace {
+
+constexpr int kPngThreads = 256;
+constexpr int kPngWaves = kPngThreads / ELVIS_WAVE;
+constexpr int kPngTile = 4096;                          // row bytes staged at a time
+constexpr int kPngPerThread = kPngTile / kPngThreads;   // consecutive symbols a lane packs
+constexpr int kPngHalo = 4;                             // >= bpp; keeps the staged row dword aligned
+constexpr int kPngRowBuf = kPngTile + kPngHalo;
+constexpr int kPngBitWords = 4096;                      // the LDS bit buffer, dwords
+constexpr int kPngMaxLen = 15;
+// before a tile the buffer holds at most kPngFlushAt bits; a row's type code and a full tile add at most 15 + 15 * kPngTile,
+// and the segment's tail (EOB, the empty stored block or the Adler trailer) fits in the 128 bits kept free
+constexpr int kPngFlushAt = kPngBitWords * 32 - (kPngMaxLen * kPngTile + kPngMaxLen) - 128;
+constexpr int kPngHeaderBits = 1106;                    // 3 + 5 + 5 + 4 + 19 * 3 + 258 * 4
+constexpr int kPngHeaderWords = 35;
+constexpr int kPngStatsStride = 260;                    // 256 bins, Adler A, Adler B, length, 0
+constexpr int kPngFrameTab = 304;                       // 257 code entries, the Adler trailer, 35 header words, padding
+constexpr int kPngTabAdler = 257;
+constexpr int kPngTabHeader = 258;
+constexpr uint32_t kAdlerMod = 65521u;
+constexpr uint32_t kCrcPoly = 0xEDB88320u;
+
+struct PngX2n {
+    uint32_t v[32];   // x^(2^k) mod P, reflected
+};
+
+__device__ __forceinline__ int png_paeth(int a, int b, int c) {
+    const int p = a + b - c;
+    const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+}
+
+__device__ __forceinline__ int png_filter(int ft, int x, int a, int b, int c) {
+    int pred = 0;
+    if (ft == 1) pred = a;
+    else if (ft == 2) pred = b;
+    else if (ft == 3) pred = (a + b) >> 1;
+    else if (ft == 4) pred = png_paeth(a, b, c);
+    return (x - pred) & 255;
+}
+
+__device__ __forceinline__ uint32_t png_cost(int v) { return (uint32_t)(v < 128 ? v : 256 - v); }
+
+// buf[kPngHalo + i] = byte t0 + i of row `row` in PNG channel order, i in [-kPngHalo, len); bytes left of the row and rows
+// above the frame are 0
+__device__ __forceinline__ void png_stage(uint8_t* buf, const uint8_t* frame, int row, int t0, int len, int rowbytes, int swap) {
+    for (int i = (int)threadIdx.x - kPngHalo; i < len; i += kPngThreads) {
+        const int j = t0 + i;
+        uint8_t v = 0;
+        if (row >= 0 && j >= 0) {
+            // swap is 0 or 2: byte j of a BGR row is byte j + 2, j, j - 2 of the pixel.  Arithmetic on purpose - a branch
+            // on the (uniform) flag inside this divergent loop was compiled to a test of a stale lane mask
+            const int src = j + swap * (1 - j % 3);
+            v = frame[(size_t)row * rowbytes + src];
+        }
+        buf[kPngHalo + i] = v;
+    }
+}
+
+// Stages tile `tile` of row r.  A row of one tile keeps the row above in the other buffer from the row before (the
+// caller staged row r0 - 1 once); wider rows stage both buffers per tile.  Returns the buffer of the current row.
+__device__ __forceinline__ int png_stage_pair(uint8_t (*rows)[kPngRowBuf], int cur, bool& staged, const uint8_t* frame, int r, int t0,
+                                              int len, int rowbytes, int swap, int ntiles) {
+    if (ntiles > 1) {
+        __syncthreads();
+        png_stage(rows[1], frame, r - 1, t0, len, rowbytes, swap);
+        png_stage(rows[0], frame, r, t0, len, rowbytes, swap);
+        __syncthreads();
+        return 0;
+    }
+    if (!staged) {
+        png_stage(rows[cur], frame, r, t0, len, rowbytes, swap);
+        staged = true;
+        __syncthreads();
+    }
+    return cur;
+}
+
+__global__ __launch_bounds__(kPngThreads) void png_stats_kernel(const uint8_t* __restrict__ frames, uint8_t* __restrict__ types,
+                                                                uint32_t* __restrict__ stats, int h, int rowbytes, int c, int swap,
+                                                                int filter, int seg_rows, int nseg) {
+    __shared__ __attribute__((aligned(16))) uint8_t rows[2][kPngRowBuf];
+    __shared__ uint32_t hist[256];
+    __shared__ unsigned long long red[5][kPngWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int seg = blockIdx.x % nseg, f = blockIdx.x / nseg;
+    const uint8_t* frame = frames + (size_t)f * h * rowbytes;
+    const int r0 = seg * seg_rows, r1 = min(h, r0 + seg_rows);
+    const uint32_t seglen = (uint32_t)(r1 - r0) * (uint32_t)(rowbytes + 1);
+    const int ntiles = (rowbytes + kPngTile - 1) / kPngTile;
+    hist[tid] = 0;
+    int cur = 0;
+    if (ntiles == 1) png_stage(rows[1], frame, r0 - 1, 0, rowbytes, rowbytes, swap);
+    __syncthreads();
+    unsigned long long sa = 0, sb = 0;   // Adler partial: sum d, sum (weight mod 65521) * d
+    int runv = 0;
+    uint32_t runc = 0;                   // equal bytes in a row cost one LDS atomic
+    for (int r = r0; r < r1; ++r) {
+        bool staged = false;
+        int ft = filter;
+        if (filter < 0) {
+            uint32_t cost[5] = {0, 0, 0, 0, 0};
+            for (int tile = 0; tile < ntiles; ++tile) {
+                const int t0 = tile * kPngTile, len = min(kPngTile, rowbytes - t0);
+                const int cb = png_stage_pair(rows, cur, staged, frame, r, t0, len, rowbytes, swap, ntiles);
+                const uint8_t* pc = rows[cb] + kPngHalo;
+                const uint8_t* pp = rows[cb ^ 1] + kPngHalo;
+                for (int i = tid; i < len; i += kPngThreads) {
+                    const int x = pc[i], a = pc[i - c], b = pp[i], d = pp[i - c];
+                    cost[0] += png_cost(x);
+                    cost[1] += png_cost((x - a) & 255);
+                    cost[2] += png_cost((x - b) & 255);
+                    cost[3] += png_cost((x - ((a + b) >> 1)) & 255);
+                    cost[4] += png_cost((x - png_paeth(a, b, d)) & 255);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                unsigned long long v = cost[k];
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                if (lane == 0) red[k][wave] = v;
+            }
+            __syncthreads();
+            unsigned long long best = 0;
+            ft = 0;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                unsigned long long v = 0;
+#pragma unroll
+                for (int w = 0; w < kPngWaves; ++w) v += red[k][w];
+                if (k == 0 || v < best) {   // a tie keeps the lower type
+                    best = v;
+                    ft = k;
+                }
+            }
+        }
+        const uint32_t rowoff = (uint32_t)(r - r0) * (uint32_t)(rowbytes + 1);
+        if (tid == 0) {
+            types[(size_t)f * h + r] = (uint8_t)ft;
+            atomicAdd(&hist[ft], 1u);
+            sa += (unsigned)ft;
+            sb += (unsigned long long)((seglen - rowoff) % kAdlerMod) * (unsigned)ft;
+        }
+        for (int tile = 0; tile < ntiles; ++tile) {
+            const int t0 = tile * kPngTile, len = min(kPngTile, rowbytes - t0);
+            const int cb = png_stage_pair(rows, cur, staged, frame, r, t0, len, rowbytes, swap, ntiles);
+            const uint8_t* pc = rows[cb] + kPngHalo;
+            const uint8_t* pp = rows[cb ^ 1] + kPngHalo;
+            for (int i = tid; i < len; i += kPngThreads) {
+                const int v = png_filter(ft, pc[i], pc[i - c], pp[i], pp[i - c]);
+                if (v == runv) {
+                    ++runc;
+                } else {
+                    if (runc) atomicAdd(&hist[runv], runc);
+                    runv = v;
+                    runc = 1;
+                }
+                const uint32_t pos = rowoff + 1u + (uint32_t)(t0 + i);
+                sa += (unsigned)v;
+                sb += (unsigned long long)((seglen - pos) % kAdlerMod) * (unsigned)v;
+            }
+        }
+        __syncthreads();   // the row above of the next row is this row's buffer; red[] is free again
+        cur ^= 1;
+    }
+    if (runc) atomicAdd(&hist[runv], runc);
+    uint32_t a = (uint32_t)(sa % kAdlerMod), b = (uint32_t)(sb % kAdlerMod);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+    }
+    if (lane == 0) {
+        red[0][wave] = a;
+        red[1][wave] = b;
+    }
+    __syncthreads();
+    uint32_t* dst = stats + (size_t)blockIdx.x * kPngStatsStride;
+    dst[tid] = hist[tid];
+    if (tid == 0) {
+        unsigned long long ta = 0, tb = 0;
+        for (int w = 0; w < kPngWaves; ++w) {
+            ta += red[0][w];
+            tb += red[1][w];
+        }
+        dst[256] = (uint32_t)(ta % kAdlerMod);
+        dst[257] = (uint32_t)(tb % kAdlerMod);
+        dst[258] = seglen;
+        dst[259] = 0;
+    }
+}
+
+// Thread 0 ORs `n` bits (n <= 32, v < 2^n) into the zeroed buffer at bit `pos`; every thread advances its copy of `pos`.
+__device__ __forceinline__ void png_put(uint32_t* bits, int& pos, uint32_t v, int n) {
+    if (threadIdx.x == 0 && n > 0) {
+        const int w = pos >> 5, s = pos & 31;
+        bits[w] |= v << s;
+        if (s + n > 32) bits[w + 1] |= v >> (32 - s);
+    }
+    pos += n;
+}
+
+// Stores dwords [0, nwords) of the bit buffer at byte gword * 4 of `out`: a dword store where the dword lies inside
+// [lo, hi), byte stores for the bytes of an edge dword that do.
+__device__ __forceinline__ void png_store_words(const uint32_t* bits, int nwords, long long gword, uint8_t* out, long long lo, long long hi) {
+    for (int d = threadIdx.x; d < nwords; d += kPngThreads) {
+        const long long g = (gword + d) * 4;
+        const uint32_t v = bits[d];
+        if (g >= lo && g + 4 <= hi) {
+            *reinterpret_cast<uint32_t*>(out + g) = v;
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (g + b >= lo && g + b < hi) out[g + b] = (uint8_t)(v >> (8 * b));
+        }
+    }
+}
+
+__global__ __launch_bounds__(kPngThreads) void png_pack_kernel(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ types,
+                                                               const long long* __restrict__ chunks, const uint32_t* __restrict__ frame_tab,
+                                                               uint8_t* __restrict__ out, long long out_bytes, int h, int rowbytes, int c,
+                                                               int swap, int seg_rows, int nseg) {
+    __shared__ __attribute__((aligned(16))) uint8_t rows[2][kPngRowBuf];
+    __shared__ uint32_t bits[kPngBitWords];
+    __shared__ uint32_t code[257];
+    __shared__ int wsum[kPngWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int seg = blockIdx.x % nseg, f = blockIdx.x / nseg;
+    const uint8_t* frame = frames + (size_t)f * h * rowbytes;
+    const uint32_t* tab = frame_tab + (size_t)f * kPngFrameTab;
+    const int r0 = seg * seg_rows, r1 = min(h, r0 + seg_rows);
+    const bool first = seg == 0, last = seg == nseg - 1;
+    const int ntiles = (rowbytes + kPngTile - 1) / kPngTile;
+    const long long cbeg = chunks[2 * (size_t)blockIdx.x], datalen = chunks[2 * (size_t)blockIdx.x + 1];
+    if (cbeg < 0 || datalen < 0 || datalen > 0xffffffffLL) return;   // uniform
+    const long long lo = cbeg, hi = min(cbeg + 8 + datalen, out_bytes);
+
+    for (int i = tid; i < kPngBitWords; i += kPngThreads) bits[i] = 0;
+    for (int i = tid; i < 257; i += kPngThreads) code[i] = tab[i];
+    int cur = 0;
+    if (ntiles == 1) png_stage(rows[1], frame, r0 - 1, 0, rowbytes, rowbytes, swap);
+    __syncthreads();
+
+    long long gword = cbeg >> 2;          // the dword of `out` that bits[0] mirrors
+    int pos = (int)(cbeg & 3) * 8;        // bits in the buffer, the bytes before the chunk included (they stay 0)
+    const uint32_t dl = (uint32_t)datalen;
+    png_put(bits, pos, dl >> 24, 8);
+    png_put(bits, pos, (dl >> 16) & 255, 8);
+    png_put(bits, pos, (dl >> 8) & 255, 8);
+    png_put(bits, pos, dl & 255, 8);
+    png_put(bits, pos, 'I', 8);
+    png_put(bits, pos, 'D', 8);
+    png_put(bits, pos, 'A', 8);
+    png_put(bits, pos, 'T', 8);
+    if (first) {
+        png_put(bits, pos, 0x78, 8);
+        png_put(bits, pos, 0x01, 8);
+    }
+    for (int k = 0; k < kPngHeaderWords; ++k) {
+        const int nb = min(32, kPngHeaderBits - 32 * k);
+        uint32_t v = tab[kPngTabHeader + k];
+        if (k == 0) v = (v & ~1u) | (last ? 1u : 0u);          // BFINAL
+        if (nb < 32) v &= (1u << nb) - 1u;
+        png_put(bits, pos, v, nb);
+    }
+
+    for (int r = r0; r < r1; ++r) {
+        bool staged = false;
+        const int ft = min((int)types[(size_t)f * h + r], 4);
+        __syncthreads();                                        // code[] is loaded; the serial puts do not race the lanes' ORs
+        png_put(bits, pos, code[ft] >> 4, (int)(code[ft] & 15u));
+        for (int tile = 0; tile < ntiles; ++tile) {
+            const int t0 = tile * kPngTile, len = min(kPngTile, rowbytes - t0);
+            const int cb = png_stage_pair(rows, cur, staged, frame, r, t0, len, rowbytes, swap, ntiles);
+            const uint8_t* pc = rows[cb] + kPngHalo;
+            const uint8_t* pp = rows[cb ^ 1] + kPngHalo;
+            uint32_t ent[kPngPerThread];
+            int mylen = 0;
+#pragma unroll
+            for (int k = 0; k < kPngPerThread; ++k) {
+                const int i = tid * kPngPerThread + k;
+                uint32_t e = 0;
+                if (i < len) e = code[png_filter(ft, pc[i], pc[i - c], pp[i], pp[i - c])];
+                ent[k] = e;
+                mylen += (int)(e & 15u);
+            }
+            int incl = mylen;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int t = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += t;
+            }
+            if (lane == 63) wsum[wave] = incl;
+            __syncthreads();                                    // also orders thread 0's type code before the ORs below
+            int woff = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < kPngWaves; ++w) {
+                if (w < wave) woff += wsum[w];
+                total += wsum[w];
+            }
+            const int bp = pos + woff + incl - mylen;
+            int w = bp >> 5, na = bp & 31;
+            unsigned long long acc = 0;
+#pragma unroll
+            for (int k = 0; k < kPngPerThread; ++k) {
+                const uint32_t e = ent[k];
+                acc |= (unsigned long long)(e >> 4) << na;
+                na += (int)(e & 15u);
+                if (na >= 32) {
+                    atomicOr(&bits[w++], (uint32_t)acc);
+                    acc >>= 32;
+                    na -= 32;
+                }
+            }
+            if (acc) atomicOr(&bits[w], (uint32_t)acc);
+            pos += total;
+            __syncthreads();
+            if (pos > kPngFlushAt) {                            // uniform
+                const int nfull = pos >> 5;
+                png_store_words(bits, nfull, gword, out, lo, hi);
+                const uint32_t carry = bits[nfull];
+                __syncthreads();
+                for (int i = tid; i <= nfull; i += kPngThreads) bits[i] = i == 0 ? carry : 0u;
+                gword += nfull;
+                pos &= 31;
+                __syncthreads();
+            }
+        }
+        if (ntiles == 1) __syncthreads();                       // the row above of the next row is this row's buffer
+        cur ^= 1;
+    }
+    __syncthreads();
+    png_put(bits, pos, code[256] >> 4, (int)(code[256] & 15u));  // EOB
+    if (!last) png_put(bits, pos, 0, 3);                        // an empty stored block: 000, pad, 00 00 FF FF
+    pos = (pos + 7) & ~7;
+    if (!last) {
+        png_put(bits, pos, 0xFFFF0000u, 32);
+    } else {
+        const uint32_t ad = tab[kPngTabAdler];
+        png_put(bits, pos, ad >> 24, 8);
+        png_put(bits, pos, (ad >> 16) & 255, 8);
+        png_put(bits, pos, (ad >> 8) & 255, 8);
+        png_put(bits, pos, ad & 255, 8);
+    }
+    __syncthreads();
+    png_store_words(bits, (pos + 31) >> 5, gword, out, lo, hi);
+}
+
+__device__ __forceinline__ uint32_t png_mulmod(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 0; i < 32; ++i) {
+        if (a & (0x80000000u >> i)) p ^= b;
+        b = (b >> 1) ^ ((b & 1u) ? kCrcPoly : 0u);
+    }
+    return p;
+}
+
+// CRC-32 of a chunk's type and data, written big-endian behind them.  Lane t runs the byte-table CRC over slice t (the
+// first from the register 0xFFFFFFFF, the others from 0); a slice's register times x^(8 * bytes behind it) mod P is its
+// share of the final register, and the shares XOR together.
+__global__ __launch_bounds__(kPngThreads) void png_crc_kernel(const long long* __restrict__ chunks, uint8_t* __restrict__ out,
+                                                              long long out_bytes, PngX2n x2n) {
+    __shared__ uint32_t tab[256];
+    __shared__ uint32_t wred[kPngWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t e = (uint32_t)tid;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) e = (e >> 1) ^ ((e & 1u) ? kCrcPoly : 0u);
+    tab[tid] = e;
+    __syncthreads();
+    const long long cbeg = chunks[2 * (size_t)blockIdx.x], datalen = chunks[2 * (size_t)blockIdx.x + 1];
+    if (cbeg < 0 || datalen < 0 || datalen > 0xffffffffLL) return;   // uniform
+    const long long start = cbeg + 4, len = datalen + 4;
+    if (start + len + 4 > out_bytes) return;
+    const long long m = (len + kPngThreads - 1) / kPngThreads;
+    const long long s0 = min(len, (long long)tid * m), s1 = min(len, s0 + m);
+    uint32_t s = tid == 0 ? 0xFFFFFFFFu : 0u;
+    const uint8_t* p = out + start;
+    for (long long i = s0; i < s1; ++i) s = tab[(s ^ p[i]) & 255u] ^ (s >> 8);
+    if (s0 < s1) {
+        unsigned long long behind = (unsigned long long)(len - s1);
+        uint32_t xp = 0x80000000u;   // x^0
+        for (int k = 3; behind; behind >>= 1, ++k)
+            if (behind & 1ull) xp = png_mulmod(x2n.v[k & 31], xp);
+        s = png_mulmod(xp, s);
+    } else {
+        s = 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s ^= __shfl_xor(s, o, 64);
+    if (lane == 0) wred[wave] = s;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t crc = 0xFFFFFFFFu;
+        for (int w = 0; w < kPngWaves; ++w) crc ^= wred[w];
+        uint8_t* q = out + start + len;
+        q[0] = (uint8_t)(crc >> 24);
+        q[1] = (uint8_t)(crc >> 16);
+        q[2] = (uint8_t)(crc >> 8);
+        q[3] = (uint8_t)crc;
+    }
+}
+
+uint32_t png_mulmod_host(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 0; i < 32; ++i) {
+        if (a & (0x80000000u >> i)) p ^= b;
+        b = (b >> 1) ^ ((b & 1u) ? kCrcPoly : 0u);
+    }
+    return p;
+}
+
+PngX2n png_x2n_table() {
+    PngX2n t;
+    uint32_t p = 0x40000000u;   // x^1
+    for (int k = 0; k < 32; ++k) {
+        t.v[k] = p;
+        p = png_mulmod_host(p, p);
+    }
+    return t;
+}
+
+int png_check_shape(const char* who, int n, int h, int w, int c, int order, int segment_rows, long long* segments) {
+    ELVIS_REQUIRE(c == 1 || c == 3, "%s: 1 or 3 channels, got %d", who, c);
+    ELVIS_REQUIRE(order == 0 || order == 1, "%s: order must be 0 (rgb) or 1 (bgr), got %d", who, order);
+    ELVIS_REQUIRE(n >= 0 && h >= 1 && w >= 1, "%s: bad shape n=%d h=%d w=%d", who, n, h, w);
+    ELVIS_REQUIRE(segment_rows >= 1, "%s: segment_rows must be at least 1, got %d", who, segment_rows);
+    ELVIS_REQUIRE((long long)w * c + 1 < 0x80000000LL && (long long)n * h < 0x80000000LL &&
+                      (long long)n * h * ((long long)w * c + 1) < 0x80000000LL,
+                  "%s: n * h * (w * c + 1) must be under 2^31 (n=%d h=%d w=%d c=%d)", who, n, h, w, c);
+    *segments = (long long)n * ((h + segment_rows - 1) / segment_rows);
+    return ELVIS_OK;
+}
+
+}  // namespace
+
+extern "C" int elvis_png_stats(const uint8_t* frames, uint8_t* types, uint32_t* stats, int n, int h, int w, int c, int order, int filter,
+                               int segment_rows, elvis_stream_t stream) {
+    long long segments = 0;
+    if (int rc = png_check_shape("elvis_png_stats", n, h, w, c, order, segment_rows, &segments)) return rc;
+    ELVIS_REQUIRE(filter >= -1 && filter <= 4, "elvis_png_stats: filter must be -1 (adaptive) or 0..4, got %d", filter);
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(frames && types && stats, "elvis_png_stats: null pointer");
+    const int nseg = (h + segment_rows - 1) / segment_rows;
+    hipLaunchKernelGGL(png_stats_kernel, dim3((unsigned)segments), dim3(kPngThreads), 0, (hipStream_t)stream, frames, types, stats, h,
+                       w * c, c, (c == 3 && order == 1) ? 2 : 0, filter, segment_rows, nseg);
+    ELVIS_CHECK_LAUNCH("elvis_png_stats");
+    elvis_note_launch("png_stats_kernel");
+    return ELVIS_OK;
+}
+
+extern "C" int elvis_png_pack(const uint8_t* frames, const uint8_t* types, const int64_t* chunks, const uint32_t* frame_tab, uint8_t* out,
+                              int64_t out_bytes, int n, int h, int w, int c, int order, int segment_rows, elvis_stream_t stream) {
+    long long segments = 0;
+    if (int rc = png_check_shape("elvis_png_pack", n, h, w, c, order, segment_rows, &segments)) return rc;
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(frames && types && chunks && frame_tab && out, "elvis_png_pack: null pointer");
+    ELVIS_REQUIRE(out_bytes > 0 && ((uintptr_t)out & 3) == 0, "elvis_png_pack: out must be 4-byte aligned and out_bytes positive");
+    const int nseg = (h + segment_rows - 1) / segment_rows;
+    static const PngX2n x2n = png_x2n_table();
+    hipLaunchKernelGGL(png_pack_kernel, dim3((unsigned)segments), dim3(kPngThreads), 0, (hipStream_t)stream, frames, types,
+                       (const long long*)chunks, frame_tab, out, (long long)out_bytes, h, w * c, c, (c == 3 && order == 1) ? 2 : 0,
+                       segment_rows, nseg);
+    ELVIS_CHECK_LAUNCH("elvis_png_pack");
+    hipLaunchKernelGGL(png_crc_kernel, dim3((unsigned)segments), dim3(kPngThreads), 0, (hipStream_t)stream, (const long long*)chunks, out,
+                       (long long)out_bytes, x2n);
+    ELVIS_CHECK_LAUNCH("elvis_png_pack");
+    elvis_note_launch("png_crc_kernel");
+    return ELVIS_OK;
+}

@@ -20,6 +20,12 @@ rule.  One device: in-process.  Several devices: one spawned process per GPU (wh
 writing its own files - the file system is the gather, exactly as in the reference (elvis.py:2983-2985).
 Sampler noise is keyed on the global frame index and the DCT restorer reads its temporal halo frames
 from the directory, so results do not depend on the device count.
+
+Every driver that writes frames takes `png_writer="pil"` (the default: frameio.save_frame / save_mask, files as before)
+or `"device"`: the PNGs are then written by the GPU (png.py) - decodable by any PNG reader to the same pixels, bytes not
+PIL's or cv2's.  The v1 shards hand their resident stretched frames and full-resolution masks to the writer directly;
+a worker's restored frames go up once more (`png.save_frames`).  Any other value is a ValueError; "device" without a
+GPU raises.  Reading stays PIL.
 """
 from __future__ import annotations
 
@@ -36,6 +42,17 @@ from .sharding import ChunkSpec, chunk_for_devices, resolve_device_list
 DeviceSpec = Union[int, str, torch.device]
 # (frames, maps, block_size, device, first_frame_index, **kw) -> frames ; replaceable for host-only tests
 ShardFn = Callable[..., List[np.ndarray]]
+
+
+PNG_WRITERS = ("pil", "device")
+
+
+def _check_png_writer(png_writer) -> str:
+    """`png_writer=` of the directory drivers: "pil" (frameio.save_frame / save_mask, the default) or "device" (png.py:
+    the files are written by the GPU - any PNG reader decodes them to the same pixels, the bytes are not PIL's)."""
+    if png_writer not in PNG_WRITERS:
+        raise ValueError(f"png_writer must be one of {PNG_WRITERS}, got {png_writer!r}")
+    return png_writer
 
 
 def _device_str(dev: torch.device) -> str:
@@ -57,7 +74,7 @@ def _dct_shard(frames, maps, block_size, device, first_frame_index, **kw):
     return restore_frames_dct(frames, maps, block_size, device, **kw)
 
 
-def _stretch_shard(frames, maps, block_size, device, first_frame_index, fullres_masks_dir=None, **kw):
+def _stretch_shard(frames, maps, block_size, device, first_frame_index, fullres_masks_dir=None, png_writer="pil", **kw):
     """Stretch a run of decoded shrunk frames in one launch pair; the inpainter's full-resolution masks come out of
     the same gather and are written here under the global frame numbers."""
     from .recompose import frames_to_device, frames_to_host
@@ -67,13 +84,19 @@ def _stretch_shard(frames, maps, block_size, device, first_frame_index, fullres_
         md = torch.from_numpy(np.ascontiguousarray(np.asarray(maps) != 0).view(np.uint8)).to(device)
         out, full = stretch_device(fd, md, block_size, "flat", fullres_mask=True)
         if fullres_masks_dir is not None:
-            full_h = full.cpu().numpy()
-            for i in range(len(frames)):
-                save_mask(full_h[i], os.path.join(fullres_masks_dir, f"{first_frame_index + i + 1:05d}.png"))
+            names = [f"{first_frame_index + i + 1:05d}.png" for i in range(len(frames))]
+            if png_writer == "device":
+                from .png import save_frames_device
+                save_frames_device(full.contiguous(), [os.path.join(fullres_masks_dir, name) for name in names])
+            else:
+                full_h = full.cpu().numpy()
+                for i, name in enumerate(names):
+                    save_mask(full_h[i], os.path.join(fullres_masks_dir, name))
         return frames_to_host(out)
 
 
-def _restore_shard(frames, maps, block_size, device, first_frame_index, stretched_dir=None, fullres_masks_dir=None, **kw):
+def _restore_shard(frames, maps, block_size, device, first_frame_index, stretched_dir=None, fullres_masks_dir=None,
+                   png_writer="pil", **kw):
     """Stretch a run of decoded shrunk frames and inpaint their holes without leaving the device: the hole mask goes
     from the gather to the inpainter as a resident tensor.  The stretched frames and the masks come down only where a
     directory asks for them, under the global frame numbers."""
@@ -85,21 +108,30 @@ def _restore_shard(frames, maps, block_size, device, first_frame_index, stretche
         md = torch.from_numpy(np.ascontiguousarray(np.asarray(maps) != 0).view(np.uint8)).to(device)
         out, full = stretch_device(fd, md, block_size, "flat", fullres_mask=True)
         names = [f"{first_frame_index + i + 1:05d}.png" for i in range(len(frames))]
-        if stretched_dir is not None:
-            for name, f in zip(names, frames_to_host(out)):
-                save_frame(f, os.path.join(stretched_dir, name))
-        if fullres_masks_dir is not None:
-            full_h = full.cpu().numpy()
-            for i, name in enumerate(names):
-                save_mask(full_h[i], os.path.join(fullres_masks_dir, name))
+        if png_writer == "device":
+            # the resident clip and its masks go to the PNG writer as they are: only finished files come down
+            from .png import save_frames_device
+            if stretched_dir is not None:
+                save_frames_device(out.contiguous(), [os.path.join(stretched_dir, name) for name in names])
+            if fullres_masks_dir is not None:
+                save_frames_device(full.contiguous(), [os.path.join(fullres_masks_dir, name) for name in names])
+        else:
+            if stretched_dir is not None:
+                for name, f in zip(names, frames_to_host(out)):
+                    save_frame(f, os.path.join(stretched_dir, name))
+            if fullres_masks_dir is not None:
+                full_h = full.cpu().numpy()
+                for i, name in enumerate(names):
+                    save_mask(full_h[i], os.path.join(fullres_masks_dir, name))
         return frames_to_host(inpaint_device(out, full, out=out))
 
 
 def _shard_worker(shard_fn: ShardFn, in_dir: str, out_dir: str, names: Sequence[str], start: int, end: int,
-                  maps: np.ndarray, block_size: int, device_str: str, halo: int, kw: dict) -> None:
+                  maps: np.ndarray, block_size: int, device_str: str, halo: int, kw: dict, png_writer: str = "pil") -> None:
     """Restore frames [start, end) of the sorted file list `names` on one device and write them to
     `out_dir` under the same names.  `halo` extra frames on each side are read (never written) for
-    restorers with a temporal window; their maps are taken as given."""
+    restorers with a temporal window; their maps are taken as given.  `png_writer="device"` writes the frame range
+    through png.save_frames (one more upload, no host pass over the pixels) in place of the save_frame loop."""
     device = torch.device(device_str)
     if device.type == "cuda":
         torch.cuda.set_device(device)
@@ -108,6 +140,10 @@ def _shard_worker(shard_fn: ShardFn, in_dir: str, out_dir: str, names: Sequence[
     restored = shard_fn(frames, np.asarray(maps[lo:hi]), block_size, device, lo, **kw)
     if len(restored) != hi - lo:
         raise RuntimeError(f"restorer returned {len(restored)} frames for {hi - lo} inputs on {device_str}")
+    if png_writer == "device":
+        from .png import save_frames
+        save_frames([restored[i - lo] for i in range(start, end)], [os.path.join(out_dir, names[i]) for i in range(start, end)], device)
+        return
     for i in range(start, end):
         save_frame(restored[i - lo], os.path.join(out_dir, names[i]))
 
@@ -131,8 +167,12 @@ def _shard_process(err_path: str, job: tuple) -> None:
 
 
 def _run_shards(shard_fn: ShardFn, in_dir: str, out_dir: str, names: List[str], chunks: List[ChunkSpec],
-                maps: np.ndarray, block_size: int, halo: int, kw: dict) -> None:
-    jobs = [(shard_fn, in_dir, out_dir, names, c.start, c.end, maps, block_size, _device_str(c.device), halo, kw)
+                maps: np.ndarray, block_size: int, halo: int, kw: dict, png_writer: str = "pil") -> None:
+    if png_writer == "device":
+        for c in chunks:
+            if c.device.type != "cuda":
+                raise RuntimeError(f"png_writer='device' needs a GPU (got device '{c.device}'); there is no CPU path")
+    jobs = [(shard_fn, in_dir, out_dir, names, c.start, c.end, maps, block_size, _device_str(c.device), halo, kw, png_writer)
             for c in chunks]
     if len(jobs) == 1:
         _shard_worker(*jobs[0])
@@ -177,6 +217,7 @@ def restore_downsampled_with_sinsr(
     per_device_workers: int = 1,
     seed: int = 42,
     schedule: str = "staged",
+    png_writer: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
     **model_kwargs,
 ) -> None:
@@ -188,6 +229,7 @@ def restore_downsampled_with_sinsr(
     are accepted and ignored, as are `parallel_chunk_length` / `per_device_workers` (the reference ignores
     them too, elvis.py:2698-2699)."""
     _ = (parallel_chunk_length, per_device_workers)
+    _check_png_writer(png_writer)
     names, maps = _frames_and_maps(input_frames_dir, downscale_maps, "Downscale maps")
     clear_directory(output_frames_dir)
     os.makedirs(output_frames_dir, exist_ok=True)
@@ -195,11 +237,12 @@ def restore_downsampled_with_sinsr(
     kw = dict(fp32=fp32, seed=seed, schedule=schedule)
     kw.update({k: v for k, v in model_kwargs.items() if k in ("cfg",)})
     _run_shards(_shard_fn or _sinsr_shard, input_frames_dir, output_frames_dir, names,
-                chunk_for_devices(len(names), devs), maps, block_size, 0, kw if _shard_fn is None else {})
+                chunk_for_devices(len(names), devs), maps, block_size, 0, kw if _shard_fn is None else {}, png_writer)
 
 
 def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int, devices, halo: int, kw: dict,
-                      what: str, allow_cpu: bool) -> None:
+                      what: str, allow_cpu: bool, png_writer: str = "pil") -> None:
+    _check_png_writer(png_writer)
     names, maps = _frames_and_maps(frames_dir, maps, what)
     if maps.size == 0 or int(np.max(maps)) <= 0:
         return   # nothing degraded: the frames stay as decoded (elvis.py:3042-3044)
@@ -213,7 +256,7 @@ def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int,
         scratch = os.path.join(frames_dir, ".elvis_restore_tmp")
         os.makedirs(scratch, exist_ok=True)
         try:
-            _run_shards(shard_fn, frames_dir, scratch, names, chunks, maps, block_size, halo, kw)
+            _run_shards(shard_fn, frames_dir, scratch, names, chunks, maps, block_size, halo, kw, png_writer)
             for n in names:
                 os.replace(os.path.join(scratch, n), os.path.join(frames_dir, n))
         finally:
@@ -221,7 +264,7 @@ def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int,
                 os.unlink(os.path.join(scratch, n))
             os.rmdir(scratch)
     else:
-        _run_shards(shard_fn, frames_dir, frames_dir, names, chunks, maps, block_size, halo, kw)
+        _run_shards(shard_fn, frames_dir, frames_dir, names, chunks, maps, block_size, halo, kw, png_writer)
 
 
 def restore_blur_adaptive(
@@ -237,6 +280,7 @@ def restore_blur_adaptive(
     parallel_chunk_length: Optional[int] = None,
     *,
     fp32: bool = False,
+    png_writer: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
 ) -> None:
     """ELVIS v2 Blur client side over a directory, IN PLACE: drop-in for `restore_with_instantir_adaptive`
@@ -246,11 +290,12 @@ def restore_blur_adaptive(
     (cfg, creative_start, preview_start) and the seed have no meaning for a deterministic forward pass
     and are ignored; `parallel_chunk_length` is ignored like in the reference (elvis.py:3015)."""
     _ = (cfg, creative_start, preview_start, seed, parallel_chunk_length)
+    _check_png_writer(png_writer)
     if batch_size < 1:
         raise ValueError("`batch_size` must be at least 1.")
     kw = {} if _shard_fn is not None else dict(batch_size=batch_size, fp32=fp32)
     _restore_in_place(_shard_fn or _blur_shard, input_frames_dir, blur_maps, block_size, devices, 0, kw,
-                      "blur_maps", _shard_fn is not None)
+                      "blur_maps", _shard_fn is not None, png_writer)
 
 
 def restore_dct_adaptive(
@@ -261,6 +306,7 @@ def restore_dct_adaptive(
     *,
     fp32: bool = False,
     temporal_radius: int = 3,
+    png_writer: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
 ) -> None:
     """ELVIS v2 DCT client side over a directory, IN PLACE (the build's definition of the slot; the
@@ -269,7 +315,7 @@ def restore_dct_adaptive(
     overlap, the expand-then-trim pattern of elvis.py:1550-1566, 1650-1657)."""
     kw = {} if _shard_fn is not None else dict(fp32=fp32)
     _restore_in_place(_shard_fn or _dct_shard, input_frames_dir, strength_maps, block_size, devices,
-                      max(0, int(temporal_radius)), kw, "strength_maps", _shard_fn is not None)
+                      max(0, int(temporal_radius)), kw, "strength_maps", _shard_fn is not None, png_writer)
 
 
 def _v1_clip(frames_dir: str, masks_npz: str, block_size: int):
@@ -292,6 +338,12 @@ def _v1_clip(frames_dir: str, masks_npz: str, block_size: int):
     return masks, names
 
 
+def _v1_kw(png_writer: str, **dirs) -> dict:
+    """The keywords of a v1 shard step: its directories, and the writer where it is not the default (a replaced
+    `_shard_fn` of the default path sees the keywords it always saw)."""
+    return dict(dirs, png_writer=png_writer) if png_writer != "pil" else dirs
+
+
 def stretch_shrunk_frames(
     frames_dir: str,
     masks_npz: str,
@@ -301,6 +353,7 @@ def stretch_shrunk_frames(
     block_masks_dir: Optional[str] = None,
     devices: Optional[Sequence[DeviceSpec]] = None,
     *,
+    png_writer: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
 ) -> np.ndarray:
     """ELVIS v1 client side over a directory (elvis.py:4534-4580): unpack the removal masks of `masks_npz`
@@ -311,6 +364,7 @@ def stretch_shrunk_frames(
 
     Every frame must hold exactly as many blocks as its mask keeps (`stretch_frame`'s rule): ValueError otherwise,
     before anything is written."""
+    _check_png_writer(png_writer)
     masks, names = _v1_clip(frames_dir, masks_npz, block_size)
     for d in (out_dir, fullres_masks_dir, block_masks_dir):
         if d is not None:
@@ -322,7 +376,7 @@ def stretch_shrunk_frames(
     gpus = [d for d in devs if d.type == "cuda"]
     workers = gpus or (devs if _shard_fn is not None else devs[:1])
     _run_shards(_shard_fn or _stretch_shard, frames_dir, out_dir or frames_dir, names, chunk_for_devices(len(names), workers),
-                masks, block_size, 0, dict(fullres_masks_dir=fullres_masks_dir))
+                masks, block_size, 0, _v1_kw(png_writer, fullres_masks_dir=fullres_masks_dir), png_writer)
     return masks
 
 
@@ -336,6 +390,7 @@ def restore_shrunk_frames(
     block_masks_dir: Optional[str] = None,
     devices: Optional[Sequence[DeviceSpec]] = None,
     *,
+    png_writer: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
 ) -> np.ndarray:
     """The whole ELVIS v1 client side over a directory (elvis.py:4534-4610): unpack the removal masks of `masks_npz`,
@@ -349,6 +404,7 @@ def restore_shrunk_frames(
     one worker per GPU.  Returns the unpacked masks."""
     if out_dir is None:
         raise ValueError("restore_shrunk_frames: out_dir is required")
+    _check_png_writer(png_writer)
     masks, names = _v1_clip(frames_dir, masks_npz, block_size)
     for d in (out_dir, stretched_dir, fullres_masks_dir, block_masks_dir):
         if d is not None:
@@ -360,7 +416,7 @@ def restore_shrunk_frames(
     gpus = [d for d in devs if d.type == "cuda"]
     workers = gpus or (devs if _shard_fn is not None else devs[:1])
     _run_shards(_shard_fn or _restore_shard, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
-                block_size, 0, dict(stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir))
+                block_size, 0, _v1_kw(png_writer, stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir), png_writer)
     return masks
 
 

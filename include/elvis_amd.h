@@ -604,6 +604,39 @@ size_t elvis_lpips_distance_workspace_bytes(int n, int h, int w);
 int elvis_lpips_distance_f64(const float* x, const float* y, const float* weight, void* workspace, double* out, int n,
                              int h, int w, int c, int pitch, int accumulate, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ PNG writer (png.hip)
+ * Lossless PNG files written by the device in place of the cv2.imwrite(...png) that ends every client-side entry point
+ * of the reference (elvis.py:131-135, 4566-4579).  Decodable by any PNG reader; the bytes are this build's own, not
+ * cv2's or PIL's.  tests/_png_ref.py states the stream and the kernels equal it bit for bit.
+ *
+ *   frames   u8 [n, h, w, c] dense, c in {1, 3}; order 0 = RGB (or gray), 1 = BGR (swapped in the loads); 8-bit colour
+ *            type 2 or 0, no interlace.  A row of the filtered stream is its type byte and w * c filtered bytes.
+ *   filters  0 None, 1 Sub, 2 Up, 3 Average floor((a + b) / 2), 4 Paeth (p = a + b - c, the nearest of a, b, c, ties in
+ *            that order), bpp = c, on the raw neighbours; left of the row and above row 0 is 0.  filter -1 picks per row
+ *            the type with the least sum of min(v, 256 - v), a tie going to the lower type; 0..4 forces a type.
+ *   stream   zlib header 78 01.  A segment is segment_rows rows (the last may be shorter), one dynamic-Huffman block of
+ *            literals only (HLIT 257, HDIST 0 with one distance code of length 0, HCLEN 19: a flat 4-bit code-length
+ *            code for 0..15, 1106 header bits), BFINAL on the last; every other segment ends with an empty stored block
+ *            and so on a byte boundary.  All segments of a frame share one literal code.  Each segment is one IDAT
+ *            chunk; the first also holds the zlib header, the last the big-endian Adler-32 of the filtered stream.
+ * Two calls per clip with one download between them (the caller synchronises, no entry point does):
+ *   1. elvis_png_stats writes types u8 [n, h] and stats u32 [n, segments, 260]: the 256-bin histogram of the segment's
+ *      filtered bytes (type bytes included), then its Adler partial A = sum d_i, B = sum (len - i) d_i (both mod
+ *      65521), its length and a 0.
+ *   2. the host builds every frame's code (lengths <= 15, complete), sums the bit lengths, lays the files out and calls
+ *      elvis_png_pack with chunks i64 [n * segments, 2] = (byte offset of the chunk in out, length of its data) and
+ *      frame_tab u32 [n, 304] = 257 entries (bit-reversed code << 4 | length), the Adler-32 trailer, the 35 dwords of
+ *      the block header with BFINAL 0, padding.  It writes every chunk whole - length, "IDAT", data, CRC-32
+ *      (png_pack_kernel, png_crc_kernel) - and nothing outside the chunks: the 33 bytes in front of a frame's first
+ *      chunk (signature, IHDR) and the 12 behind its last (IEND) are the host's.  No global atomics; the same input
+ *      gives the same bytes.
+ * ELVIS_E_INVALID before any launch: c outside {1, 3}, h or w under 1, a bad order or filter, segment_rows under 1,
+ * n * h * (w * c + 1) >= 2^31, a null pointer, out not 4-byte aligned.  n == 0 is a no-op. */
+int elvis_png_stats(const uint8_t* frames, uint8_t* types, uint32_t* stats, int n, int h, int w, int c, int order, int filter,
+                    int segment_rows, elvis_stream_t stream);
+int elvis_png_pack(const uint8_t* frames, const uint8_t* types, const int64_t* chunks, const uint32_t* frame_tab, uint8_t* out,
+                   int64_t out_bytes, int n, int h, int w, int c, int order, int segment_rows, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
