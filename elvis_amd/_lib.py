@@ -104,6 +104,9 @@ SIGNATURES = {
     "elvis_lpips_distance_f64": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_png_stats": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_png_pack": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_png_gather": [vp, i64, vp, i32, vp, i64, vp, vp],
+    "elvis_png_inflate": [vp, i64, vp, vp, i64, vp, vp, i32, vp],
+    "elvis_png_unfilter": [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],

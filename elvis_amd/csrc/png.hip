@@ -17,11 +17,10 @@
 // Every global store of phase 2 is clipped to the chunk's own byte range and to the output buffer, and every code length
 // is read through a 4-bit mask, so tables that disagree with the plan give a wrong file, never a write elsewhere.
 #include "common.h"
+#include "png_crc.h"
 
 namespace {
 
-constexpr int kPngThreads = 256;
-constexpr int kPngWaves = kPngThreads / ELVIS_WAVE;
 constexpr int kPngTile = 4096;                          // row bytes staged at a time
 constexpr int kPngPerThread = kPngTile / kPngThreads;   // consecutive symbols a lane packs
 constexpr int kPngHalo = 4;                             // >= bpp; keeps the staged row dword aligned
@@ -38,11 +37,6 @@ constexpr int kPngFrameTab = 304;                       // 257 code entries, the
 constexpr int kPngTabAdler = 257;
 constexpr int kPngTabHeader = 258;
 constexpr uint32_t kAdlerMod = 65521u;
-constexpr uint32_t kCrcPoly = 0xEDB88320u;
-
-struct PngX2n {
-    uint32_t v[32];   // x^(2^k) mod P, reflected
-};
 
 __device__ __forceinline__ int png_paeth(int a, int b, int c) {
     const int p = a + b - c;
@@ -367,78 +361,25 @@ __global__ __launch_bounds__(kPngThreads) void png_pack_kernel(const uint8_t* __
     png_store_words(bits, (pos + 31) >> 5, gword, out, lo, hi);
 }
 
-__device__ __forceinline__ uint32_t png_mulmod(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b >> 1) ^ ((b & 1u) ? kCrcPoly : 0u);
-    }
-    return p;
-}
-
-// CRC-32 of a chunk's type and data, written big-endian behind them.  Lane t runs the byte-table CRC over slice t (the
-// first from the register 0xFFFFFFFF, the others from 0); a slice's register times x^(8 * bytes behind it) mod P is its
-// share of the final register, and the shares XOR together.
+// CRC-32 of a chunk's type and data, written big-endian behind them (png_crc.h has the slices and their combination).
 __global__ __launch_bounds__(kPngThreads) void png_crc_kernel(const long long* __restrict__ chunks, uint8_t* __restrict__ out,
                                                               long long out_bytes, PngX2n x2n) {
     __shared__ uint32_t tab[256];
     __shared__ uint32_t wred[kPngWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t e = (uint32_t)tid;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) e = (e >> 1) ^ ((e & 1u) ? kCrcPoly : 0u);
-    tab[tid] = e;
+    png_crc_table(tab);
     __syncthreads();
     const long long cbeg = chunks[2 * (size_t)blockIdx.x], datalen = chunks[2 * (size_t)blockIdx.x + 1];
     if (cbeg < 0 || datalen < 0 || datalen > 0xffffffffLL) return;   // uniform
     const long long start = cbeg + 4, len = datalen + 4;
     if (start + len + 4 > out_bytes) return;
-    const long long m = (len + kPngThreads - 1) / kPngThreads;
-    const long long s0 = min(len, (long long)tid * m), s1 = min(len, s0 + m);
-    uint32_t s = tid == 0 ? 0xFFFFFFFFu : 0u;
-    const uint8_t* p = out + start;
-    for (long long i = s0; i < s1; ++i) s = tab[(s ^ p[i]) & 255u] ^ (s >> 8);
-    if (s0 < s1) {
-        unsigned long long behind = (unsigned long long)(len - s1);
-        uint32_t xp = 0x80000000u;   // x^0
-        for (int k = 3; behind; behind >>= 1, ++k)
-            if (behind & 1ull) xp = png_mulmod(x2n.v[k & 31], xp);
-        s = png_mulmod(xp, s);
-    } else {
-        s = 0;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s ^= __shfl_xor(s, o, 64);
-    if (lane == 0) wred[wave] = s;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t crc = 0xFFFFFFFFu;
-        for (int w = 0; w < kPngWaves; ++w) crc ^= wred[w];
+    const uint32_t crc = png_crc_workgroup(out + start, len, x2n, tab, wred);
+    if (threadIdx.x == 0) {
         uint8_t* q = out + start + len;
         q[0] = (uint8_t)(crc >> 24);
         q[1] = (uint8_t)(crc >> 16);
         q[2] = (uint8_t)(crc >> 8);
         q[3] = (uint8_t)crc;
     }
-}
-
-uint32_t png_mulmod_host(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b >> 1) ^ ((b & 1u) ? kCrcPoly : 0u);
-    }
-    return p;
-}
-
-PngX2n png_x2n_table() {
-    PngX2n t;
-    uint32_t p = 0x40000000u;   // x^1
-    for (int k = 0; k < 32; ++k) {
-        t.v[k] = p;
-        p = png_mulmod_host(p, p);
-    }
-    return t;
 }
 
 int png_check_shape(const char* who, int n, int h, int w, int c, int order, int segment_rows, long long* segments) {

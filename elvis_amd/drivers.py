@@ -23,9 +23,14 @@ from the directory, so results do not depend on the device count.
 
 Every driver that writes frames takes `png_writer="pil"` (the default: frameio.save_frame / save_mask, files as before)
 or `"device"`: the PNGs are then written by the GPU (png.py) - decodable by any PNG reader to the same pixels, bytes not
-PIL's or cv2's.  The v1 shards hand their resident stretched frames and full-resolution masks to the writer directly;
-a worker's restored frames go up once more (`png.save_frames`).  Any other value is a ValueError; "device" without a
-GPU raises.  Reading stays PIL.
+PIL's or cv2's.  The v1 shards hand their resident stretched, inpainted frames and full-resolution masks to the writer
+directly (`png.save_frames_device`); a model worker's restored frames go up once more (`png.save_frames`).  Any other value is a ValueError; "device" without a
+GPU raises.
+
+Every driver also takes `png_reader="pil"` (the default: frameio.load_frame per file) or `"device"`: a worker's frame
+range is then decoded by the GPU (png.load_frames_device) into one resident clip.  The v1 shards take that clip as it
+is - with both options "device" a v1 shard's pixels never visit the host; the model restorers' `restore_frames_*` are
+host-to-host functions and get `frames_to_host` of it, as does a replaced `_shard_fn`.  Same errors as `png_writer`.
 """
 from __future__ import annotations
 
@@ -53,6 +58,17 @@ def _check_png_writer(png_writer) -> str:
     if png_writer not in PNG_WRITERS:
         raise ValueError(f"png_writer must be one of {PNG_WRITERS}, got {png_writer!r}")
     return png_writer
+
+
+PNG_READERS = ("pil", "device")
+
+
+def _check_png_reader(png_reader) -> str:
+    """`png_reader=` of the directory drivers: "pil" (frameio.load_frame, the default) or "device" (png.py: the files are
+    decoded by the GPU into a resident clip - the same pixels)."""
+    if png_reader not in PNG_READERS:
+        raise ValueError(f"png_reader must be one of {PNG_READERS}, got {png_reader!r}")
+    return png_reader
 
 
 def _device_str(dev: torch.device) -> str:
@@ -92,7 +108,8 @@ def _stretch_shard(frames, maps, block_size, device, first_frame_index, fullres_
                 full_h = full.cpu().numpy()
                 for i, name in enumerate(names):
                     save_mask(full_h[i], os.path.join(fullres_masks_dir, name))
-        return frames_to_host(out)
+        # the device writer takes the resident clip from the worker: the stretched frames do not come down
+        return out if png_writer == "device" else frames_to_host(out)
 
 
 def _restore_shard(frames, maps, block_size, device, first_frame_index, stretched_dir=None, fullres_masks_dir=None,
@@ -123,26 +140,42 @@ def _restore_shard(frames, maps, block_size, device, first_frame_index, stretche
                 full_h = full.cpu().numpy()
                 for i, name in enumerate(names):
                     save_mask(full_h[i], os.path.join(fullres_masks_dir, name))
-        return frames_to_host(inpaint_device(out, full, out=out))
+        done = inpaint_device(out, full, out=out)
+        return done if png_writer == "device" else frames_to_host(done)
 
 
 def _shard_worker(shard_fn: ShardFn, in_dir: str, out_dir: str, names: Sequence[str], start: int, end: int,
-                  maps: np.ndarray, block_size: int, device_str: str, halo: int, kw: dict, png_writer: str = "pil") -> None:
+                  maps: np.ndarray, block_size: int, device_str: str, halo: int, kw: dict, png_writer: str = "pil",
+                  png_reader: str = "pil") -> None:
     """Restore frames [start, end) of the sorted file list `names` on one device and write them to
     `out_dir` under the same names.  `halo` extra frames on each side are read (never written) for
     restorers with a temporal window; their maps are taken as given.  `png_writer="device"` writes the frame range
-    through png.save_frames (one more upload, no host pass over the pixels) in place of the save_frame loop."""
+    through png.save_frames_device where the shard function returned its resident clip (the v1 shards), else through
+    png.save_frames (one more upload, no host pass over the pixels), in place of the save_frame loop;
+    `png_reader="device"` decodes the range with png.load_frames_device in place of the load_frame loop - the v1 shards
+    take the resident clip, every other shard function its frames_to_host."""
     device = torch.device(device_str)
     if device.type == "cuda":
         torch.cuda.set_device(device)
     lo, hi = max(0, start - halo), min(len(names), end + halo)
-    frames = [load_frame(os.path.join(in_dir, names[i])) for i in range(lo, hi)]
+    if png_reader == "device":
+        from .png import load_frames_device
+        from .recompose import frames_to_host
+        frames = load_frames_device([os.path.join(in_dir, names[i]) for i in range(lo, hi)], device)
+        if shard_fn not in (_stretch_shard, _restore_shard):
+            frames = frames_to_host(frames)
+    else:
+        frames = [load_frame(os.path.join(in_dir, names[i])) for i in range(lo, hi)]
     restored = shard_fn(frames, np.asarray(maps[lo:hi]), block_size, device, lo, **kw)
     if len(restored) != hi - lo:
         raise RuntimeError(f"restorer returned {len(restored)} frames for {hi - lo} inputs on {device_str}")
     if png_writer == "device":
-        from .png import save_frames
-        save_frames([restored[i - lo] for i in range(start, end)], [os.path.join(out_dir, names[i]) for i in range(start, end)], device)
+        from .png import save_frames, save_frames_device
+        paths = [os.path.join(out_dir, names[i]) for i in range(start, end)]
+        if isinstance(restored, torch.Tensor):     # a v1 shard's resident clip: only finished files come down
+            save_frames_device(restored[start - lo:end - lo].contiguous(), paths)
+        else:
+            save_frames([restored[i - lo] for i in range(start, end)], paths, device)
         return
     for i in range(start, end):
         save_frame(restored[i - lo], os.path.join(out_dir, names[i]))
@@ -167,12 +200,13 @@ def _shard_process(err_path: str, job: tuple) -> None:
 
 
 def _run_shards(shard_fn: ShardFn, in_dir: str, out_dir: str, names: List[str], chunks: List[ChunkSpec],
-                maps: np.ndarray, block_size: int, halo: int, kw: dict, png_writer: str = "pil") -> None:
-    if png_writer == "device":
-        for c in chunks:
-            if c.device.type != "cuda":
-                raise RuntimeError(f"png_writer='device' needs a GPU (got device '{c.device}'); there is no CPU path")
-    jobs = [(shard_fn, in_dir, out_dir, names, c.start, c.end, maps, block_size, _device_str(c.device), halo, kw, png_writer)
+                maps: np.ndarray, block_size: int, halo: int, kw: dict, png_writer: str = "pil", png_reader: str = "pil") -> None:
+    for what, value in (("png_writer", png_writer), ("png_reader", png_reader)):
+        if value == "device":
+            for c in chunks:
+                if c.device.type != "cuda":
+                    raise RuntimeError(f"{what}='device' needs a GPU (got device '{c.device}'); there is no CPU path")
+    jobs = [(shard_fn, in_dir, out_dir, names, c.start, c.end, maps, block_size, _device_str(c.device), halo, kw, png_writer, png_reader)
             for c in chunks]
     if len(jobs) == 1:
         _shard_worker(*jobs[0])
@@ -218,6 +252,7 @@ def restore_downsampled_with_sinsr(
     seed: int = 42,
     schedule: str = "staged",
     png_writer: str = "pil",
+    png_reader: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
     **model_kwargs,
 ) -> None:
@@ -230,6 +265,7 @@ def restore_downsampled_with_sinsr(
     them too, elvis.py:2698-2699)."""
     _ = (parallel_chunk_length, per_device_workers)
     _check_png_writer(png_writer)
+    _check_png_reader(png_reader)
     names, maps = _frames_and_maps(input_frames_dir, downscale_maps, "Downscale maps")
     clear_directory(output_frames_dir)
     os.makedirs(output_frames_dir, exist_ok=True)
@@ -237,12 +273,13 @@ def restore_downsampled_with_sinsr(
     kw = dict(fp32=fp32, seed=seed, schedule=schedule)
     kw.update({k: v for k, v in model_kwargs.items() if k in ("cfg",)})
     _run_shards(_shard_fn or _sinsr_shard, input_frames_dir, output_frames_dir, names,
-                chunk_for_devices(len(names), devs), maps, block_size, 0, kw if _shard_fn is None else {}, png_writer)
+                chunk_for_devices(len(names), devs), maps, block_size, 0, kw if _shard_fn is None else {}, png_writer, png_reader)
 
 
 def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int, devices, halo: int, kw: dict,
-                      what: str, allow_cpu: bool, png_writer: str = "pil") -> None:
+                      what: str, allow_cpu: bool, png_writer: str = "pil", png_reader: str = "pil") -> None:
     _check_png_writer(png_writer)
+    _check_png_reader(png_reader)
     names, maps = _frames_and_maps(frames_dir, maps, what)
     if maps.size == 0 or int(np.max(maps)) <= 0:
         return   # nothing degraded: the frames stay as decoded (elvis.py:3042-3044)
@@ -256,7 +293,7 @@ def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int,
         scratch = os.path.join(frames_dir, ".elvis_restore_tmp")
         os.makedirs(scratch, exist_ok=True)
         try:
-            _run_shards(shard_fn, frames_dir, scratch, names, chunks, maps, block_size, halo, kw, png_writer)
+            _run_shards(shard_fn, frames_dir, scratch, names, chunks, maps, block_size, halo, kw, png_writer, png_reader)
             for n in names:
                 os.replace(os.path.join(scratch, n), os.path.join(frames_dir, n))
         finally:
@@ -264,7 +301,7 @@ def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int,
                 os.unlink(os.path.join(scratch, n))
             os.rmdir(scratch)
     else:
-        _run_shards(shard_fn, frames_dir, frames_dir, names, chunks, maps, block_size, halo, kw, png_writer)
+        _run_shards(shard_fn, frames_dir, frames_dir, names, chunks, maps, block_size, halo, kw, png_writer, png_reader)
 
 
 def restore_blur_adaptive(
@@ -281,6 +318,7 @@ def restore_blur_adaptive(
     *,
     fp32: bool = False,
     png_writer: str = "pil",
+    png_reader: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
 ) -> None:
     """ELVIS v2 Blur client side over a directory, IN PLACE: drop-in for `restore_with_instantir_adaptive`
@@ -291,11 +329,12 @@ def restore_blur_adaptive(
     and are ignored; `parallel_chunk_length` is ignored like in the reference (elvis.py:3015)."""
     _ = (cfg, creative_start, preview_start, seed, parallel_chunk_length)
     _check_png_writer(png_writer)
+    _check_png_reader(png_reader)
     if batch_size < 1:
         raise ValueError("`batch_size` must be at least 1.")
     kw = {} if _shard_fn is not None else dict(batch_size=batch_size, fp32=fp32)
     _restore_in_place(_shard_fn or _blur_shard, input_frames_dir, blur_maps, block_size, devices, 0, kw,
-                      "blur_maps", _shard_fn is not None, png_writer)
+                      "blur_maps", _shard_fn is not None, png_writer, png_reader)
 
 
 def restore_dct_adaptive(
@@ -307,6 +346,7 @@ def restore_dct_adaptive(
     fp32: bool = False,
     temporal_radius: int = 3,
     png_writer: str = "pil",
+    png_reader: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
 ) -> None:
     """ELVIS v2 DCT client side over a directory, IN PLACE (the build's definition of the slot; the
@@ -315,7 +355,7 @@ def restore_dct_adaptive(
     overlap, the expand-then-trim pattern of elvis.py:1550-1566, 1650-1657)."""
     kw = {} if _shard_fn is not None else dict(fp32=fp32)
     _restore_in_place(_shard_fn or _dct_shard, input_frames_dir, strength_maps, block_size, devices,
-                      max(0, int(temporal_radius)), kw, "strength_maps", _shard_fn is not None, png_writer)
+                      max(0, int(temporal_radius)), kw, "strength_maps", _shard_fn is not None, png_writer, png_reader)
 
 
 def _v1_clip(frames_dir: str, masks_npz: str, block_size: int):
@@ -354,6 +394,7 @@ def stretch_shrunk_frames(
     devices: Optional[Sequence[DeviceSpec]] = None,
     *,
     png_writer: str = "pil",
+    png_reader: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
 ) -> np.ndarray:
     """ELVIS v1 client side over a directory (elvis.py:4534-4580): unpack the removal masks of `masks_npz`
@@ -365,6 +406,7 @@ def stretch_shrunk_frames(
     Every frame must hold exactly as many blocks as its mask keeps (`stretch_frame`'s rule): ValueError otherwise,
     before anything is written."""
     _check_png_writer(png_writer)
+    _check_png_reader(png_reader)
     masks, names = _v1_clip(frames_dir, masks_npz, block_size)
     for d in (out_dir, fullres_masks_dir, block_masks_dir):
         if d is not None:
@@ -376,7 +418,7 @@ def stretch_shrunk_frames(
     gpus = [d for d in devs if d.type == "cuda"]
     workers = gpus or (devs if _shard_fn is not None else devs[:1])
     _run_shards(_shard_fn or _stretch_shard, frames_dir, out_dir or frames_dir, names, chunk_for_devices(len(names), workers),
-                masks, block_size, 0, _v1_kw(png_writer, fullres_masks_dir=fullres_masks_dir), png_writer)
+                masks, block_size, 0, _v1_kw(png_writer, fullres_masks_dir=fullres_masks_dir), png_writer, png_reader)
     return masks
 
 
@@ -391,6 +433,7 @@ def restore_shrunk_frames(
     devices: Optional[Sequence[DeviceSpec]] = None,
     *,
     png_writer: str = "pil",
+    png_reader: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
 ) -> np.ndarray:
     """The whole ELVIS v1 client side over a directory (elvis.py:4534-4610): unpack the removal masks of `masks_npz`,
@@ -405,6 +448,7 @@ def restore_shrunk_frames(
     if out_dir is None:
         raise ValueError("restore_shrunk_frames: out_dir is required")
     _check_png_writer(png_writer)
+    _check_png_reader(png_reader)
     masks, names = _v1_clip(frames_dir, masks_npz, block_size)
     for d in (out_dir, stretched_dir, fullres_masks_dir, block_masks_dir):
         if d is not None:
@@ -416,7 +460,7 @@ def restore_shrunk_frames(
     gpus = [d for d in devs if d.type == "cuda"]
     workers = gpus or (devs if _shard_fn is not None else devs[:1])
     _run_shards(_shard_fn or _restore_shard, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
-                block_size, 0, _v1_kw(png_writer, stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir), png_writer)
+                block_size, 0, _v1_kw(png_writer, stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir), png_writer, png_reader)
     return masks
 
 

@@ -3,6 +3,8 @@ and the IO helpers the directory drivers need).
 
 * PNG / JPEG frames as BGR uint8 HWC arrays - what `cv2.imread(..., IMREAD_COLOR)` / `cv2.imwrite`
   give the reference (elvis.py:123-136); read and written through PIL here (cv2 is not a dependency).
+  png.py writes and reads PNG frames on the device instead (`save_frames_device`, `load_frames_device`); both are
+  opt-in and these functions stay the default.
 * strength maps: `np.savez_compressed(path, strength_maps=uint8[F,By,Bx])` (elvis.py:2247-2272).
 * block masks: `np.packbits` of a uint8 {0,1} array + its shape (elvis.py:4412-4418, 4537-4539).
 

@@ -9,13 +9,28 @@ headers per file.  Stands where the reference's client side ends, `cv2.imwrite(.
 The files are decodable by any PNG reader; their bytes are this build's own, NOT cv2's or PIL's (DESIGN.md 7 has the
 stream: literal-only dynamic-Huffman deflate, one block and one IDAT chunk per `segment_rows` rows, one length-limited
 literal code per frame).  Opt-in: `frameio.save_frame` / `save_mask` stay PIL and every directory driver writes through
-PIL unless it is called with `png_writer="device"`.  Reading stays PIL (`frameio.load_frame`).
+PIL unless it is called with `png_writer="device"`.
 
 Synchronisation: one per clip, as for the inpainter.  Phase 1 (`elvis_png_stats`) leaves every segment's histogram and
 Adler partial on the device; they are downloaded with one blocking copy on the current stream (1040 bytes a segment),
 the codes, bit lengths, chunk offsets and Adler trailers are worked out here, and phase 2 (`elvis_png_pack`) writes the
 chunks into one exactly sized buffer.  The host never passes over pixel or stream bytes.  tests/_png_ref.py states the
 stream in numpy and Python ints; the device files equal it bit for bit.
+
+PNG frames read by the device (csrc/png_read.hip, csrc/inflate.h), where the reference's client side starts with
+`cv2.imread` (elvis.py:123-128):
+
+  parse_png(data)                        host: signature, chunk headers and IHDR only -> PngInfo
+  decode_png_device(files, device)       PNG files in memory -> resident u8 [n,H,W,channels]
+  load_frames_device(paths, device)      the same from disk, uploaded in chunks
+  inflate_device(streams, sizes, device) the inflater alone, on arbitrary zlib streams
+
+8-bit, non-interlaced, colour type 0, 2 or 6 (alpha dropped); any number of IDAT chunks, any zlib stream.  The host
+uploads the file bytes as they are with a table of chunk spans; IDAT gather, chunk CRC-32s, inflate, Adler-32 and the
+unfilter run on the device, and one download of the per-frame status words ends a clip: IOError("Failed to load frame:
+<path>") for a corrupt file, as `frameio.load_frame`.  Unsupported files raise ValueError before any launch.  Opt-in
+too: `frameio.load_frame` stays PIL, and the directory drivers read through PIL unless called with
+`png_reader="device"`.  tests/_png_read_ref.py states the decoder; zlib and PIL are the oracles.
 """
 from __future__ import annotations
 
@@ -23,7 +38,7 @@ import os
 import struct
 import zlib
 from dataclasses import dataclass
-from typing import List, Sequence, Tuple, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -350,3 +365,335 @@ def _check_args_only(order, filter, segment_rows) -> None:
     _filter_code(filter)
     if isinstance(segment_rows, bool) or not isinstance(segment_rows, (int, np.integer)) or int(segment_rows) < 1:
         raise ValueError(f"save_frames: segment_rows must be an integer >= 1, got {segment_rows!r}")
+
+
+# ----------------------------------------------------------------------------- reading
+READ_CHUNK_BYTES = 512 << 20   # decoded pixels plus filtered streams of one upload chunk (41 frames at 1080p)
+STATUS_NAMES = ("ok", "input exhausted", "bad zlib header", "bad block type", "stored LEN/NLEN mismatch", "bad code-length set",
+                "invalid literal/length or distance symbol", "distance too far back", "output longer than the frame",
+                "output shorter than the frame", "Adler-32 mismatch", "chunk CRC mismatch", "filter type above 4")
+E_CRC, E_FILTER = 11, 12
+_BPP = {0: 1, 2: 3, 6: 4}
+
+
+@dataclass
+class PngInfo:
+    width: int
+    height: int
+    color_type: int                       # 0 gray, 2 RGB, 6 RGBA
+    bpp: int                              # bytes per pixel: 1, 3 or 4
+    chunks: List[Tuple[int, int, bool]]   # every chunk, IHDR and IEND included: (offset of its type field, data length, is IDAT)
+
+
+def _corrupt(name) -> IOError:
+    return IOError(f"Failed to load frame: {name}")
+
+
+def parse_png(data, name="<bytes>") -> PngInfo:
+    """Host only: the signature, the 8-byte chunk headers and IHDR of one PNG file; no stream byte is read.  ValueError
+    (naming `name` and the property) for a file that is no PNG or not of the supported kind - 8-bit, non-interlaced,
+    colour type 0, 2 or 6; IOError("Failed to load frame: <name>") where the chunks do not tile the file up to IEND,
+    IHDR is not first, or there is no IDAT."""
+    mv = memoryview(data)
+    if len(mv) < 8 or bytes(mv[:8]) != PNG_SIGNATURE:
+        raise ValueError(f"{name}: not a PNG file (bad signature)")
+    at, chunks, ihdr, ended = 8, [], None, False
+    while at + 12 <= len(mv):
+        (length,) = struct.unpack(">I", mv[at:at + 4])
+        kind = bytes(mv[at + 4:at + 8])
+        if length >= 1 << 31 or at + 12 + length > len(mv):
+            raise _corrupt(name)
+        if ihdr is None:
+            if kind != b"IHDR" or length != 13:
+                raise _corrupt(name)
+            ihdr = struct.unpack(">IIBBBBB", mv[at + 8:at + 21])
+        chunks.append((at + 4, length, kind == b"IDAT"))
+        at += 12 + length
+        if kind == b"IEND":
+            ended = True
+            break
+    if ihdr is None or not ended or not any(c[2] for c in chunks):
+        raise _corrupt(name)
+    w, h, depth, ctype, comp, filt, lace = ihdr
+    if ctype == 3:
+        raise ValueError(f"{name}: palette PNG (colour type 3) is not supported")
+    if ctype == 4:
+        raise ValueError(f"{name}: gray+alpha PNG (colour type 4) is not supported")
+    if ctype not in _BPP:
+        raise ValueError(f"{name}: colour type {ctype} is not supported")
+    if depth != 8:
+        raise ValueError(f"{name}: bit depth {depth} is not supported (8-bit only)")
+    if lace != 0:
+        raise ValueError(f"{name}: interlaced PNG is not supported")
+    if comp != 0 or filt != 0 or w < 1 or h < 1:
+        raise _corrupt(name)
+    return PngInfo(int(w), int(h), int(ctype), _BPP[ctype], chunks)
+
+
+def _check_read_args(order, channels, who: str) -> None:
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"{who}: order must be 'bgr' or 'rgb', got {order!r}")
+    if isinstance(channels, bool) or channels not in (1, 3):
+        raise ValueError(f"{who}: channels must be 1 or 3, got {channels!r}")
+
+
+def _check_infos(infos: Sequence[PngInfo], names: Sequence, channels: int, who: str, size=None) -> Tuple[int, int]:
+    """One size for all files, gray files only for channels=1, the size limit: (H, W)."""
+    for info, name in zip(infos, names):
+        if size is None:
+            size = (info.height, info.width)
+        if (info.height, info.width) != size:
+            raise ValueError(f"{who}: {name} is {info.height}x{info.width}, the files before it {size[0]}x{size[1]}")
+        if channels == 1 and info.bpp != 1:
+            raise ValueError(f"{who}: {name} is a colour file; channels=1 is for gray files only")
+    h, w = size
+    total = len(infos) * h * (w * max(i.bpp for i in infos) + 1)
+    if total >= 1 << 31:
+        raise ValueError(f"{who}: n * H * (W * bpp + 1) = {total} is 2^31 or more; decode the clip in parts")
+    return h, w
+
+
+@dataclass
+class _Pending:
+    """A launched clip whose status words are still on the device."""
+    status_d: torch.Tensor               # i32 [4 n + 2 n + nchunks]
+    n: int
+    caps: List[int]
+    rowlens: List[int]
+    chunk_frame: np.ndarray              # [nchunks] the frame of every chunk
+    chunk_stream_end: np.ndarray         # [nchunks] where the chunk's payload ends in its frame's stream (0 before the first IDAT)
+
+
+def _launch_decode(files: Sequence, infos: Sequence[PngInfo], frames_out: torch.Tensor, order: str, channels: int, *,
+                   guard: int = 0, upload_offset: int = 0):
+    """Gather, CRC check, inflate and unfilter of one clip into frames_out [n,H,W,channels] (resident, contiguous);
+    nothing is downloaded.  `guard` bytes of 0xA5 go on either side of the filtered-stream buffer, and the uploaded
+    bytes start `upload_offset` bytes past a dword (the tests' knobs).  Returns the _Pending and the filtered buffer
+    with its guards."""
+    dev = frames_out.device
+    n = len(files)
+    h, w = int(frames_out.shape[1]), int(frames_out.shape[2])
+    if guard % 4:
+        raise ValueError("guard must be a multiple of 4")
+    sizes = [len(memoryview(f)) for f in files]
+    file_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    if int(file_off[-1]) + upload_offset >= 1 << 31:
+        raise ValueError(f"decode_png_device: {int(file_off[-1])} bytes of files are 2^31 or more; decode the clip in parts")
+    host = np.empty(int(file_off[-1]) + upload_offset, dtype=np.uint8)
+    for f, data in enumerate(files):
+        host[upload_offset + int(file_off[f]):upload_offset + int(file_off[f + 1])] = np.frombuffer(data, dtype=np.uint8)
+    rows, chunk_frame, stream_end, in_spans = [], [], [], []
+    stream_at = 0
+    for f, info in enumerate(infos):
+        start = stream_at
+        for off, length, idat in info.chunks:
+            rows.append((int(file_off[f]) + off, length, stream_at if idat else -1))
+            if idat:
+                stream_at += length
+            chunk_frame.append(f)
+            stream_end.append(stream_at - start)
+        in_spans.append((start, stream_at - start))
+    stride = (h * (w * max(i.bpp for i in infos) + 1) + 3) // 4 * 4
+    caps = [h * (w * i.bpp + 1) for i in infos]
+    nchunks = len(rows)
+    with torch.cuda.device(dev):
+        files_d = torch.from_numpy(host).to(dev)[upload_offset:]
+        tables = np.concatenate([np.asarray(rows, dtype=np.int64).reshape(-1), np.asarray(in_spans, dtype=np.int64).reshape(-1),
+                                 np.asarray([(f * stride, caps[f]) for f in range(n)], dtype=np.int64).reshape(-1)])
+        tables_d = torch.from_numpy(tables).to(dev)
+        chunks_d, in_d, out_d = tables_d[:3 * nchunks], tables_d[3 * nchunks:3 * nchunks + 2 * n], tables_d[3 * nchunks + 2 * n:]
+        streams_d = torch.empty(max(stream_at, 1), dtype=torch.uint8, device=dev)
+        filt_buf = torch.empty(n * stride + 2 * guard, dtype=torch.uint8, device=dev)
+        if guard:
+            filt_buf[:guard] = 0xA5
+            filt_buf[guard + n * stride:] = 0xA5
+        filt_d = filt_buf[guard:guard + n * stride]
+        status_d = torch.zeros(6 * n + nchunks, dtype=torch.int32, device=dev)
+        s = _s(frames_out)
+        check(lib().elvis_png_gather(ptr(files_d), int(file_off[-1]), ptr(chunks_d), nchunks, ptr(streams_d), stream_at,
+                                     ptr(status_d) + 24 * n, s), dev)
+        check(lib().elvis_png_inflate(ptr(streams_d), stream_at, ptr(in_d), ptr(filt_d), n * stride, ptr(out_d), ptr(status_d), n, s), dev)
+        frame_bytes = h * w * channels
+        at = 0
+        while at < n:                      # a run of files of one colour type is one launch
+            end = at + 1
+            while end < n and infos[end].bpp == infos[at].bpp:
+                end += 1
+            check(lib().elvis_png_unfilter(ptr(filt_d) + at * stride, stride, ptr(frames_out) + at * frame_bytes,
+                                           ptr(status_d) + 16 * n + 8 * at, end - at, h, w, infos[at].bpp, channels, int(order == "bgr"), s), dev)
+            at = end
+    # the work buffers are not kept: every launch above is on the current stream, and the allocator hands a freed block only
+    # to later work on that stream, so an upload chunk's work space is reused by the next chunk
+    pending = _Pending(status_d, n, caps, [w * i.bpp + 1 for i in infos], np.asarray(chunk_frame), np.asarray(stream_end))
+    return pending, filt_buf
+
+
+def _frame_codes(pending: _Pending, status: np.ndarray) -> List[int]:
+    """One status code per frame from the downloaded words; the first defect in stream order wins: a chunk whose CRC is
+    wrong and whose payload begins at or before the byte the inflater stopped at, then a filter type above 4 in a row
+    that was produced, then the inflater's own code."""
+    n = pending.n
+    inf = status[:4 * n].reshape(n, 4)
+    unf = status[4 * n:6 * n].reshape(n, 2)
+    crc = status[6 * n:]
+    codes = []
+    for f in range(n):
+        code, produced, consumed = int(inf[f, 0]), int(inf[f, 1]), int(inf[f, 2])
+        mine = np.flatnonzero((pending.chunk_frame == f) & (crc != 0))
+        if unf[f, 0] != 0 and int(unf[f, 1]) * pending.rowlens[f] < produced:
+            code = E_FILTER
+        if mine.size:
+            first = int(mine[0])
+            begins = int(pending.chunk_stream_end[first - 1]) if first > 0 and pending.chunk_frame[first - 1] == f else 0
+            if int(inf[f, 0]) in (0, 9, 10) or begins <= consumed:
+                code = E_CRC
+        codes.append(code)
+    return codes
+
+
+def _decode_clip(files: Sequence, device, order: str, channels: int, names: Optional[Sequence] = None, *, guard: int = 0,
+                 upload_offset: int = 0, who: str = "decode_png_device"):
+    """decode_png_device without the raise: (frames [n,H,W,channels] as a view into a buffer with `guard` bytes of 0xA5 on
+    either side, that buffer, the filtered-stream buffer with its guards, one status code per frame)."""
+    _check_read_args(order, channels, who)
+    files = list(files)
+    names = [f"<file {i}>" for i in range(len(files))] if names is None else list(names)
+    if len(names) != len(files):
+        raise ValueError(f"{who}: {len(names)} name(s) for {len(files)} file(s)")
+    if not files:
+        raise ValueError(f"{who}: no files")
+    infos = [parse_png(data, name) for data, name in zip(files, names)]
+    h, w = _check_infos(infos, names, channels, who)
+    dev = L.resolve_device(device)
+    L.require_gpu(dev)
+    n = len(files)
+    with torch.cuda.device(dev):
+        buf = torch.empty(n * h * w * channels + 2 * guard, dtype=torch.uint8, device=dev)
+        if guard:
+            buf[:guard] = 0xA5
+            buf[guard + n * h * w * channels:] = 0xA5
+        frames = buf[guard:guard + n * h * w * channels].view(n, h, w, channels)
+        pending, filt_buf = _launch_decode(files, infos, frames, order, channels, guard=guard, upload_offset=upload_offset)
+        # the one synchronisation of a clip: the status words
+        codes = _frame_codes(pending, pending.status_d.cpu().numpy().view(np.uint32))
+    return frames, buf, filt_buf, codes
+
+
+def decode_png_device(files: Sequence, device="cuda:0", order: str = "bgr", channels: int = 3, names: Optional[Sequence] = None) -> torch.Tensor:
+    """PNG files in memory (bytes-like, one per frame) decoded on the device into a resident contiguous uint8
+    [n,H,W,channels] tensor.  `channels=3` (the default): gray is replicated and alpha dropped, as `frameio.load_frame`
+    does; `order` "bgr" (what `load_frame` gives) or "rgb".  `channels=1` is for gray files only.  All files have one
+    size.  ValueError before any launch for a bad argument or an unsupported file; IOError("Failed to load frame:
+    <name>") for a corrupt one (`names` default to "<file i>")."""
+    names = [f"<file {i}>" for i in range(len(files))] if names is None else list(names)
+    frames, _, _, codes = _decode_clip(files, device, order, channels, names)
+    for name, code in zip(names, codes):
+        if code:
+            raise _corrupt(name)
+    return frames
+
+
+def load_frames_device(paths: Sequence, device="cuda:0", order: str = "bgr", channels: int = 3, chunk_frames: Optional[int] = None) -> torch.Tensor:
+    """The PNG files `paths` decoded on the device into one resident contiguous uint8 [n,H,W,channels] tensor: what
+    `frameio.load_frame` per file and `recompose.frames_to_device` give, without a host pass over the pixels.  The files
+    are read and uploaded `chunk_frames` at a time (by default as many as make 512 MB of device work space, 41 at
+    1080p); every chunk's kernels are launched before the one download of all status words.  The result does not depend
+    on the chunk size.  Errors as `decode_png_device`, naming the path."""
+    _check_read_args(order, channels, "load_frames_device")
+    paths = list(paths)
+    if not paths:
+        raise ValueError("load_frames_device: no paths")
+    if chunk_frames is not None and (isinstance(chunk_frames, bool) or int(chunk_frames) < 1):
+        raise ValueError("chunk_frames must be at least 1")
+    dev = L.resolve_device(device)
+    L.require_gpu(dev)
+    out, size, pendings, at = None, None, [], 0
+    with torch.cuda.device(dev):
+        while at < len(paths):
+            files, infos = [], []
+            while at + len(files) < len(paths):
+                path = paths[at + len(files)]
+                try:
+                    with open(path, "rb") as fh:
+                        data = fh.read()
+                except OSError as exc:
+                    raise _corrupt(path) from exc
+                info = parse_png(data, path)
+                size = _check_infos([info], [path], channels, "load_frames_device", size)
+                files.append(data)
+                infos.append(info)
+                step = int(chunk_frames) if chunk_frames is not None else max(1, READ_CHUNK_BYTES // (2 * size[0] * (size[1] * 4 + 1)))
+                if len(files) >= step:
+                    break
+            _check_infos(infos, paths[at:at + len(files)], channels, "load_frames_device", size)
+            if out is None:
+                if len(paths) * size[0] * size[1] * channels >= 1 << 40:
+                    raise ValueError("load_frames_device: the clip is too large")
+                out = torch.empty((len(paths), size[0], size[1], channels), dtype=torch.uint8, device=dev)
+            pending, _ = _launch_decode(files, infos, out[at:at + len(files)], order, channels)
+            pendings.append((at, pending))
+            at += len(files)
+        # the one synchronisation: every chunk's status words in one copy
+        status = torch.cat([p.status_d for _, p in pendings]).cpu().numpy().view(np.uint32)
+    pos = 0
+    for start, p in pendings:
+        words = p.status_d.numel()
+        for f, code in enumerate(_frame_codes(p, status[pos:pos + words])):
+            if code:
+                raise _corrupt(paths[start + f])
+        pos += words
+    return out
+
+
+def _inflate_clip(streams: Sequence, sizes: Sequence[int], device, *, guard: int = 0, upload_offset: int = 0):
+    """The inflater alone: (the output buffer on the device with `guard` bytes of 0xA5 on either side, the offset of every
+    stream's output in it, status u32 [n, 4] = code, bytes produced, bytes consumed, Adler-32)."""
+    streams = list(streams)
+    sizes = [int(v) for v in sizes]
+    if len(streams) != len(sizes):
+        raise ValueError(f"inflate_device: {len(sizes)} size(s) for {len(streams)} stream(s)")
+    if any(v < 0 for v in sizes):
+        raise ValueError("inflate_device: sizes must not be negative")
+    if guard % 4:
+        raise ValueError("guard must be a multiple of 4")
+    dev = L.resolve_device(device)
+    L.require_gpu(dev)
+    n = len(streams)
+    lens = [len(memoryview(v)) for v in streams]
+    in_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    out_off = np.concatenate([[0], np.cumsum([(v + 3) // 4 * 4 for v in sizes])]).astype(np.int64)
+    if int(in_off[-1]) + upload_offset >= 1 << 31 or int(out_off[-1]) >= 1 << 31:
+        raise ValueError("inflate_device: 2^31 bytes or more; inflate the streams in parts")
+    if n == 0:
+        return None, out_off, np.zeros((0, 4), dtype=np.uint32)
+    host = np.empty(int(in_off[-1]) + upload_offset, dtype=np.uint8)
+    for i, v in enumerate(streams):
+        host[upload_offset + int(in_off[i]):upload_offset + int(in_off[i + 1])] = np.frombuffer(v, dtype=np.uint8)
+    spans = np.concatenate([np.stack([in_off[:-1], np.asarray(lens, dtype=np.int64)], axis=1).reshape(-1),
+                            np.stack([out_off[:-1], np.asarray(sizes, dtype=np.int64)], axis=1).reshape(-1)])
+    total = int(out_off[-1])
+    with torch.cuda.device(dev):
+        in_d = torch.from_numpy(host).to(dev)[upload_offset:]
+        spans_d = torch.from_numpy(spans).to(dev)
+        buf = torch.empty(max(total, 4) + 2 * guard, dtype=torch.uint8, device=dev)
+        if guard:
+            buf[:guard] = 0xA5
+            buf[guard + max(total, 4):] = 0xA5
+        status_d = torch.zeros(4 * n, dtype=torch.int32, device=dev)
+        check(lib().elvis_png_inflate(ptr(in_d), int(in_off[-1]), ptr(spans_d), ptr(buf) + guard, total, ptr(spans_d) + 16 * n,
+                                      ptr(status_d), n, _s(buf)), dev)
+        status = status_d.cpu().numpy().view(np.uint32).reshape(n, 4)
+    return buf, out_off, status
+
+
+def inflate_device(streams: Sequence, sizes: Sequence[int], device="cuda:0") -> List[bytes]:
+    """zlib streams (RFC 1950: stored, fixed and dynamic blocks in any mix) inflated on the device, one wave per stream;
+    sizes[i] is the exact length of stream i's output.  IOError naming the stream and the defect otherwise."""
+    buf, out_off, status = _inflate_clip(streams, sizes, device)
+    if buf is None:
+        return []
+    for i, row in enumerate(status):
+        if row[0]:
+            raise IOError(f"inflate_device: stream {i}: {STATUS_NAMES[int(row[0])] if int(row[0]) < len(STATUS_NAMES) else int(row[0])}")
+    host = buf.cpu().numpy()
+    return [host[int(out_off[i]):int(out_off[i]) + int(sizes[i])].tobytes() for i in range(len(sizes))]

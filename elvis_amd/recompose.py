@@ -30,7 +30,15 @@ def combine_blocks_into_image(blocks: np.ndarray) -> np.ndarray:
 
 
 def frames_to_device(frames: Sequence[np.ndarray], device) -> torch.Tensor:
+    """Host frames as one resident [n,H,W,C] clip.  A clip that is resident already - a contiguous uint8 [n,H,W,3] tensor
+    on `device`, what png.load_frames_device gives - is passed through unchanged, so that its pixels never come down."""
     L.require_gpu(device)
+    if isinstance(frames, torch.Tensor):
+        dev = torch.device(device)
+        if (frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] == 0 or not frames.is_cuda
+                or not frames.is_contiguous() or (dev.index is not None and dev.index != frames.device.index)):
+            raise ValueError("a resident clip must be a contiguous uint8 [n,H,W,3] tensor on the device it is used on")
+        return frames
     if not frames:
         raise ValueError("no frames")
     shp = frames[0].shape

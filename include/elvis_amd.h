@@ -637,6 +637,38 @@ int elvis_png_stats(const uint8_t* frames, uint8_t* types, uint32_t* stats, int 
 int elvis_png_pack(const uint8_t* frames, const uint8_t* types, const int64_t* chunks, const uint32_t* frame_tab, uint8_t* out,
                    int64_t out_bytes, int n, int h, int w, int c, int order, int segment_rows, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ PNG reader (png_read.hip, inflate.h)
+ * PNG files decoded by the device in place of the cv2.imread that starts every client-side entry point of the reference
+ * (elvis.py:123-128).  8-bit, non-interlaced, colour type 0, 2 or 6.  The host reads the signature, the chunk headers
+ * and IHDR, uploads the files as they are and tells where the chunks lie; it passes over no stream byte and no pixel.
+ * Three calls per clip and one download of the status words at the end (the caller synchronises, no entry point does):
+ *   1. elvis_png_gather: chunks i64 [nchunks, 3] = (offset of the chunk's type field in files, length of its data,
+ *      offset in streams where the data go, or -1 for a chunk that is not IDAT).  Copies the IDAT payloads into the
+ *      frames' zlib streams and checks EVERY chunk's CRC-32: crc_status u32 [nchunks] = 0 or 11.  A chunk whose span
+ *      lies outside files gets crc_status 11 and is not read; a payload whose destination lies outside streams is not
+ *      copied and leaves no status of its own (the inflater then reports what it finds in the stream).
+ *   2. elvis_png_inflate: stream i is streams[in_spans[i][0] .. + in_spans[i][1]), decoded into out[out_spans[i][0] ..
+ *      + out_spans[i][1]) (offsets multiples of 4); any zlib stream (RFC 1950 / 1951).  One wave per stream.
+ *      status u32 [n, 4] = code, bytes produced, bytes consumed, Adler-32 of the bytes produced.  Codes: 0 ok,
+ *      1 input exhausted, 2 bad zlib header, 3 bad block type, 4 stored LEN/NLEN mismatch, 5 bad code-length set,
+ *      6 invalid literal/length or distance symbol, 7 distance too far back, 8 output longer than its span,
+ *      9 output shorter, 10 Adler-32 mismatch (11 chunk CRC and 12 filter type are the other two calls').  The first
+ *      defect in stream order wins; nothing is written outside the span.
+ *   3. elvis_png_unfilter: filtered = n streams of h rows of 1 + w * bpp bytes, `stride` bytes apart (bpp 1, 3 or 4),
+ *      reconstructed per the PNG specification into frames u8 [n, h, w, channels]; channels 3 (gray replicated, alpha
+ *      dropped; order 0 = RGB, 1 = BGR, swapped in the stores) or 1 (bpp 1 only).  `filtered` is a workspace: some
+ *      of its rows are overwritten.  status u32 [n, 2] = (0 or 12, the first row whose filter type is above 4).
+ * The same input gives the same bytes, alone or in a batch; no global atomics.
+ * ELVIS_E_INVALID before any launch: a negative count or size, a buffer of 2^31 bytes or more, bpp outside {1, 3, 4},
+ * channels outside {1, 3} or 1 with bpp above 1, a bad order, h or w under 1, n * h * (w * bpp + 1) >= 2^31, a stride
+ * under h * (w * bpp + 1), a null pointer, out not 4-byte aligned.  n == 0 (nchunks == 0) is a no-op. */
+int elvis_png_gather(const uint8_t* files, int64_t files_bytes, const int64_t* chunks, int nchunks, uint8_t* streams,
+                     int64_t streams_bytes, uint32_t* crc_status, elvis_stream_t stream);
+int elvis_png_inflate(const uint8_t* streams, int64_t streams_bytes, const int64_t* in_spans, uint8_t* out, int64_t out_bytes,
+                      const int64_t* out_spans, uint32_t* status, int n, elvis_stream_t stream);
+int elvis_png_unfilter(uint8_t* filtered, int64_t stride, uint8_t* frames, uint32_t* status, int n, int h, int w, int bpp,
+                       int channels, int order, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
