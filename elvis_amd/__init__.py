@@ -19,6 +19,7 @@ from .degrade import (blur_block, degrade_adaptive_blur, degrade_adaptive_downsa
                       filter_frame_dct, filter_frame_downsample, filter_frame_gaussian, generate_degradation_map)
 from .handoff import (calculate_importance_scores, convert_frames_to_yuv420p, create_kvazaar_roi_file,  # noqa: F401
                       create_svtav1_roi_file, kvazaar_delta_qp, rgb_to_i420_device, svtav1_delta_qp, write_y4m)
+from .handoff import (Y4MInfo, i420_to_rgb_device, load_y4m_device, load_yuv420p_device, parse_y4m, read_y4m)  # noqa: F401
 from .classical import (lanczos_restore_device, restore_blur_opencv_unsharp_mask,  # noqa: F401
                         restore_downsample_opencv_lanczos, restore_with_opencv_lanczos, restore_with_opencv_unsharp,
                         temporal_blend_device, unsharp_restore_device)
@@ -37,9 +38,9 @@ from .lpips import (LpipsAlex, calculate_lpips, calculate_lpips_per_frame, get_l
                     load_lpips_state_dict, lpips_device)
 from .png import decode_png_device, encode_png_device, load_frames_device, save_frames, save_frames_device  # noqa: F401
 from .drivers import (calculate_removability_scores_from_frames, restore_blur_adaptive, restore_dct_adaptive,  # noqa: F401
-                      restore_downsampled_with_sinsr, restore_shrunk_frames, stretch_shrunk_frames)
-from .restore import (get_sinsr_model, get_sinsr_upsample_fn, restore_frames_blur,  # noqa: F401
-                      restore_frames_dct, restore_frames_rounds, restore_frames_sinsr,
-                      restore_with_sinsr_naive)
+                      restore_downsampled_with_sinsr, restore_shrunk_frames, restore_yuv_clip, stretch_shrunk_frames)
+from .restore import (get_sinsr_model, get_sinsr_upsample_fn, restore_frames_blur, restore_frames_blur_device,  # noqa: F401
+                      restore_frames_dct, restore_frames_dct_device, restore_frames_rounds, restore_frames_sinsr,
+                      restore_frames_sinsr_device, restore_with_sinsr_naive)
 
 __version__ = "0.1.0"

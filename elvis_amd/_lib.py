@@ -85,6 +85,7 @@ SIGNATURES = {
     "elvis_degrade_scale_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp],
     "elvis_degrade_gaussian_fx_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_rgb_to_i420_u8": [vp, vp, i32, i32, i32, i32, vp],
+    "elvis_i420_to_rgb_u8": [vp, vp, i32, i32, i32, i32, vp],
     "elvis_classical_lanczos_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "elvis_classical_unsharp_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp],
     "elvis_temporal_blend_u8": [vp, vp, i32, i64, f64, f64, vp],

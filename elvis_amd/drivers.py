@@ -11,6 +11,8 @@
   calculate_removability_scores_from_frames
                                    <- calculate_removability_scores (elvis.py:968-1224) from frames and masks in memory,
                                       with the build-defined block complexity (complexity.py) in EVCA's place
+  restore_yuv_clip                 -  the three model slots from a clip file (.y4m / raw .yuv, what a decoder emits) to
+                                      a clip file, no PNG directory in between (described at the function)
 
 Same arguments, file naming and errors as the reference: a directory of PNG frames (BGR on read) and a
 `(frames, blocks_y, blocks_x)` map; the Downsample driver writes `output_dir/<same names>`, the Blur /
@@ -181,13 +183,14 @@ def _shard_worker(shard_fn: ShardFn, in_dir: str, out_dir: str, names: Sequence[
         save_frame(restored[i - lo], os.path.join(out_dir, names[i]))
 
 
-def _shard_process(err_path: str, job: tuple) -> None:
-    """Entry point of a spawned per-GPU worker: a failure is written to stderr and to `err_path` as
+def _shard_process(err_path: str, job: tuple, worker: Optional[Callable[..., None]] = None) -> None:
+    """Entry point of a spawned per-GPU worker (`worker`, by default `_shard_worker`; every worker's job holds its frame
+    range at [4], [5] and its device at [8]): a failure is written to stderr and to `err_path` as
     `device / [start, end) / traceback`, so the parent can say WHICH shard failed and why."""
     import sys
     import traceback
     try:
-        _shard_worker(*job)
+        (worker or _shard_worker)(*job)
     except BaseException:
         start, end, device_str = job[4], job[5], job[8]
         msg = f"shard on {device_str}, frames [{start}, {end}):\n{traceback.format_exc()}"
@@ -208,14 +211,20 @@ def _run_shards(shard_fn: ShardFn, in_dir: str, out_dir: str, names: List[str], 
                     raise RuntimeError(f"{what}='device' needs a GPU (got device '{c.device}'); there is no CPU path")
     jobs = [(shard_fn, in_dir, out_dir, names, c.start, c.end, maps, block_size, _device_str(c.device), halo, kw, png_writer, png_reader)
             for c in chunks]
+    _run_jobs(_shard_worker, jobs)
+
+
+def _run_jobs(worker: Callable[..., None], jobs: List[tuple]) -> None:
+    """One job: `worker(*job)` in-process.  Several: one spawned process per job, failures gathered and reported by
+    device and frame range (`_shard_process`)."""
     if len(jobs) == 1:
-        _shard_worker(*jobs[0])
+        worker(*jobs[0])
         return
     import tempfile
     ctx = multiprocessing.get_context("spawn")   # never fork a process that may hold a GPU context
     with tempfile.TemporaryDirectory(prefix="elvis_shards_") as errdir:
         errs = [os.path.join(errdir, f"shard{i}.err") for i in range(len(jobs))]
-        procs = [ctx.Process(target=_shard_process, args=(e, job)) for e, job in zip(errs, jobs)]
+        procs = [ctx.Process(target=_shard_process, args=(e, job, worker)) for e, job in zip(errs, jobs)]
         for p in procs:
             p.start()
         failed = []
@@ -462,6 +471,151 @@ def restore_shrunk_frames(
     _run_shards(_shard_fn or _restore_shard, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
                 block_size, 0, _v1_kw(png_writer, stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir), png_writer, png_reader)
     return masks
+
+
+# ----------------------------------------------------------------------------- clip files: decoder output in, encoder input out
+YUV_CLIP_KINDS = {"sinsr": "Downscale maps", "blur": "blur_maps", "dct": "strength_maps"}
+# (clip, maps, block_size, device, first_frame_index, **kw) -> clip ; resident [n,H,W,3] u8 BGR in and out
+ClipShardFn = Callable[..., torch.Tensor]
+
+
+def _sinsr_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
+    from .restore import restore_frames_sinsr_device
+    return restore_frames_sinsr_device(clip, maps, block_size, first_frame_index=first_frame_index, **kw)
+
+
+def _blur_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
+    from .restore import restore_frames_blur_device
+    return restore_frames_blur_device(clip, maps, block_size, **kw)
+
+
+def _dct_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
+    from .restore import restore_frames_dct_device
+    return restore_frames_dct_device(clip, maps, block_size, **kw)
+
+
+_CLIP_SHARDS = {"sinsr": _sinsr_clip_shard, "blur": _blur_clip_shard, "dct": _dct_clip_shard}
+_FRAME_MARKER = b"FRAME\n"
+
+
+def _clip_format(path: str, what: str) -> str:
+    ext = os.path.splitext(os.fspath(path))[1].lower()
+    if ext not in (".y4m", ".yuv"):
+        raise ValueError(f"restore_yuv_clip: {what} must be a .y4m or a .yuv file, got {os.fspath(path)!r}")
+    return ext[1:]
+
+
+def _yuv_clip_worker(shard_fn: ClipShardFn, src: tuple, dst: tuple, total: int, start: int, end: int, maps: np.ndarray,
+                     block_size: int, device_str: str, halo: int, kw: dict) -> None:
+    """Restore frames [start, end) of the clip file `src` = (path, "y4m" | "yuv", width, height) on one device and write
+    their I420 planes into `dst` = (path, "y4m" | "yuv", header length) at the frames' own offsets; the file exists at
+    full length.  `halo` extra frames on each side are read from the input (never written) for restorers with a
+    temporal window.  The pixels go up as I420, stay resident as RGB from the conversion through the restorer to the
+    conversion back, and come down once as I420: 1.5 bytes per pixel each way."""
+    from .handoff import load_y4m_device, load_yuv420p_device, rgb_to_i420_device
+    device = torch.device(device_str)
+    torch.cuda.set_device(device)
+    (in_path, in_format, width, height), (out_path, out_format, head) = src, dst
+    lo, hi = max(0, start - halo), min(total, end + halo)
+    if in_format == "y4m":
+        clip = load_y4m_device(in_path, device, "bgr", start=lo, count=hi - lo)
+    else:
+        clip = load_yuv420p_device(in_path, width, height, device, "bgr", start=lo, count=hi - lo)
+    restored = shard_fn(clip, np.asarray(maps[lo:hi]), block_size, device, lo, **kw)
+    if not isinstance(restored, torch.Tensor) or tuple(restored.shape) != tuple(clip.shape) or restored.dtype != torch.uint8:
+        raise RuntimeError(f"restorer did not return the resident uint8 clip {tuple(clip.shape)} it was given on {device_str}")
+    planes = rgb_to_i420_device(restored[start - lo:end - lo].contiguous(), "bgr")
+    host = torch.empty(planes.shape, dtype=torch.uint8).pin_memory()
+    host.copy_(planes, non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    rows = host.numpy()
+    frame_bytes = width * height * 3 // 2
+    with open(out_path, "r+b") as f:
+        if out_format == "yuv":
+            f.seek(start * frame_bytes)
+            f.write(memoryview(rows).cast("B"))
+        else:
+            f.seek(head + start * (len(_FRAME_MARKER) + frame_bytes))
+            for i in range(end - start):
+                f.write(_FRAME_MARKER)
+                f.write(memoryview(rows[i]).cast("B"))
+
+
+def restore_yuv_clip(
+    kind: str,
+    input_path: str,
+    output_path: str,
+    maps: np.ndarray,
+    block_size: int,
+    *,
+    width: Optional[int] = None,
+    height: Optional[int] = None,
+    framerate: Optional[float] = None,
+    devices: Optional[Sequence[DeviceSpec]] = None,
+    _shard_fn: Optional[ClipShardFn] = None,
+    **kw,
+) -> None:
+    """One of the three model slots - `kind` "sinsr" (`restore_frames_sinsr`), "blur" (`restore_frames_blur`) or "dct"
+    (`restore_frames_dct`) - from a clip file to a clip file: what a decoder emits (`ffmpeg -f yuv4mpegpipe`, or
+    `-f rawvideo -pix_fmt yuv420p`) in, what the encoders and VMAF take out, no directory of PNGs in between.
+
+    `input_path` is a `.y4m` file, or a raw `.yuv` with `width` and `height`; `output_path` is a `.y4m` (`handoff.y4m_header`
+    and the `FRAME\\n` framing of `write_y4m`; the frame rate is the input's, or `framerate`, which a raw input needs) or
+    a `.yuv`, chosen by extension, and another file than the input.  `maps` is `(frames, blocks_y, blocks_x)`.  Keywords
+    are the restorer's (`fp32`, `seed`, `schedule`, `cfg`, `batch_size`, ...); `temporal_radius` (3) is the DCT
+    restorer's halo.
+
+    Frames are dealt to the devices by the `chunk_for_devices` rule: one device runs in-process, several use one
+    spawned process per GPU.  Every frame has a fixed size, so the output file is created at full length and each
+    worker writes its own frame range at its own offsets - the file system is the gather.  A worker loads its range
+    (`handoff.load_y4m_device` / `load_yuv420p_device`; for "dct" with `temporal_radius` halo frames on either side, read
+    from the input, never written), runs the `*_device` restorer, converts back (`handoff.rgb_to_i420_device`) and
+    downloads 1.5 bytes per pixel: RGB pixels never visit the host.  Decoded frames are BGR inside, as in the directory
+    drivers.  PARITY UNPINNED vs cv2 for both conversions (handoff.py)."""
+    from .handoff import parse_y4m, y4m_header, yuv420p_frame_count
+    if kind not in YUV_CLIP_KINDS:
+        raise ValueError(f"restore_yuv_clip: kind must be one of {tuple(YUV_CLIP_KINDS)}, got {kind!r}")
+    in_format, out_format = _clip_format(input_path, "input_path"), _clip_format(output_path, "output_path")
+    input_path, output_path = os.fspath(input_path), os.fspath(output_path)
+    if os.path.realpath(input_path) == os.path.realpath(output_path) or \
+            (os.path.exists(output_path) and os.path.exists(input_path) and os.path.samefile(input_path, output_path)):
+        raise ValueError(f"restore_yuv_clip: input and output must be different files, got {input_path!r} twice")
+    if in_format == "y4m":
+        info = parse_y4m(input_path)
+        for name, given, found in (("width", width, info.width), ("height", height, info.height)):
+            if given is not None and int(given) != found:
+                raise ValueError(f"restore_yuv_clip: {name}={given} but {input_path} says {found}")
+        width, height, total = info.width, info.height, info.frame_count
+        if framerate is None:
+            framerate = info.framerate
+    else:
+        if width is None or height is None:
+            raise ValueError("restore_yuv_clip: a raw .yuv input needs width= and height=")
+        width, height = int(width), int(height)
+        total = yuv420p_frame_count(os.path.getsize(input_path), width, height, input_path)
+    if out_format == "y4m" and framerate is None:
+        raise ValueError("restore_yuv_clip: a .y4m output needs a frame rate: pass framerate= (the input gives none)")
+    if total == 0:
+        raise ValueError(f"No frames found in {input_path}")
+    maps = np.asarray(maps)
+    if maps.ndim != 3 or maps.shape[0] != total:
+        raise ValueError(f"{YUV_CLIP_KINDS[kind]} length ({maps.shape[0] if maps.ndim else 0}) does not match frame count ({total}).")
+    if kind == "blur" and int(kw.get("batch_size", 4)) < 1:
+        raise ValueError("`batch_size` must be at least 1.")
+    halo = max(0, int(kw.pop("temporal_radius", 3))) if kind == "dct" else 0
+    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=False)
+    for d in devs:
+        if d.type != "cuda":
+            raise RuntimeError(f"restore_yuv_clip needs a GPU (got device '{d}'); there is no CPU path")
+    head = y4m_header(width, height, framerate) if out_format == "y4m" else b""
+    frame_bytes = width * height * 3 // 2
+    with open(output_path, "wb") as f:
+        f.write(head)
+        f.truncate(len(head) + total * (frame_bytes + (len(_FRAME_MARKER) if out_format == "y4m" else 0)))
+    src, dst = (input_path, in_format, width, height), (output_path, out_format, len(head))
+    jobs = [(_shard_fn or _CLIP_SHARDS[kind], src, dst, total, c.start, c.end, maps, block_size, _device_str(c.device), halo,
+             {} if _shard_fn is not None else kw) for c in chunk_for_devices(total, devs)]
+    _run_jobs(_yuv_clip_worker, jobs)
 
 
 def calculate_removability_scores_from_frames(frames, foreground_masks, block_size: int, alpha: float = 0.5,

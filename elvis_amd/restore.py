@@ -229,33 +229,20 @@ def restore_clip_single4x_host(model: SinSRModel, frames_h: torch.Tensor, levels
     return (out_h, pl.out_d) if want_device else out_h
 
 
-def restore_frames_sinsr(frames: List[np.ndarray], downscale_maps: np.ndarray, block_size: int, device,
-                         *, seed: int = DEFAULT_SEED, first_frame_index: int = 0, fp32: bool = False,
-                         schedule: str = "staged", staged_2x: bool = False, cfg: Optional[SinSRConfig] = None,
-                         precision: Optional[str] = None, **_ignored) -> List[np.ndarray]:
-    """Pure restoration function (no file IO, no parallelisation), drop-in for
-    `restore_frames_realesrgan` (elvis.py:2640-2682): BGR uint8 frames + per-block log2
-    downscale maps -> restored frames.
-
-    schedule="staged" (default: the reference's semantics): the coarse-to-fine loop of
-    elvis.py:2570-2598 generalised to 4x stages (`staged_2x=True`: the reference's 2x-per-stage loop
-    with the 4x net area-halved per stage).  schedule="single4x" (the north-star / benchmark path): one
-    SinSR 4x call from the /4 level per frame, whatever the map's maximum (README.md:50) - blocks of
-    level 1 lose the detail the staged loop would keep at the /2 stage.
-    Unknown model kwargs of the reference call (model_name, tile, ...) are accepted and ignored
-    (the `**kwargs` convention of the P3 surface, utils.py:1428).
-    """
-    if not frames:
-        return []
-    dev = torch.device(device)
-    model = get_sinsr_model(dev, cfg=cfg, fp32=fp32, precision=precision)
+def restore_frames_sinsr_device(frames_d: torch.Tensor, downscale_maps, block_size: int, *, seed: int = DEFAULT_SEED,
+                                first_frame_index: int = 0, fp32: bool = False, schedule: str = "staged",
+                                staged_2x: bool = False, cfg: Optional[SinSRConfig] = None,
+                                precision: Optional[str] = None, **_ignored) -> torch.Tensor:
+    """`restore_frames_sinsr` on a resident clip: [n,H,W,3] u8 BGR on the device and the host maps
+    in, the restored resident clip out, on the clip's device; no pixel visits the host."""
+    model = get_sinsr_model(frames_d.device, cfg=cfg, fp32=fp32, precision=precision)
     with torch.cuda.device(model.device):
-        frames_d = frames_to_device(frames, model.device)
+        frames_d = frames_to_device(frames_d, model.device)
         n = frames_d.shape[0]
         maps_d = maps_to_device(downscale_maps, n, model.device)
         if schedule == "single4x":
             gidx = [first_frame_index + i for i in range(n)]
-            return frames_to_host(restore_clip_single4x_device(model, frames_d, maps_d, block_size, gidx, seed))
+            return restore_clip_single4x_device(model, frames_d, maps_d, block_size, gidx, seed)
         if schedule != "staged":
             raise ValueError(f"unknown schedule '{schedule}'")
         out = torch.empty_like(frames_d)
@@ -275,7 +262,33 @@ def restore_frames_sinsr(frames: List[np.ndarray], downscale_maps: np.ndarray, b
                 return sr4x_device(model, cur, _g, seed)
 
             out[it] = upscale_adaptive_device(sub_f, sub_m, block_size, up, sr_scale=2 if staged_2x else 4)
-        return frames_to_host(out)
+        return out
+
+
+def restore_frames_sinsr(frames: List[np.ndarray], downscale_maps: np.ndarray, block_size: int, device,
+                         *, seed: int = DEFAULT_SEED, first_frame_index: int = 0, fp32: bool = False,
+                         schedule: str = "staged", staged_2x: bool = False, cfg: Optional[SinSRConfig] = None,
+                         precision: Optional[str] = None, **_ignored) -> List[np.ndarray]:
+    """Pure restoration function (no file IO, no parallelisation), drop-in for
+    `restore_frames_realesrgan` (elvis.py:2640-2682): BGR uint8 frames + per-block log2
+    downscale maps -> restored frames.  Host to host around `restore_frames_sinsr_device`.
+
+    schedule="staged" (default: the reference's semantics): the coarse-to-fine loop of
+    elvis.py:2570-2598 generalised to 4x stages (`staged_2x=True`: the reference's 2x-per-stage loop
+    with the 4x net area-halved per stage).  schedule="single4x" (the north-star / benchmark path): one
+    SinSR 4x call from the /4 level per frame, whatever the map's maximum (README.md:50) - blocks of
+    level 1 lose the detail the staged loop would keep at the /2 stage.
+    Unknown model kwargs of the reference call (model_name, tile, ...) are accepted and ignored
+    (the `**kwargs` convention of the P3 surface, utils.py:1428).
+    """
+    if not frames:
+        return []
+    dev = torch.device(device)
+    model = get_sinsr_model(dev, cfg=cfg, fp32=fp32, precision=precision)
+    with torch.cuda.device(model.device):
+        return frames_to_host(restore_frames_sinsr_device(
+            frames_to_device(frames, model.device), downscale_maps, block_size, seed=seed, first_frame_index=first_frame_index,
+            fp32=fp32, schedule=schedule, staged_2x=staged_2x, cfg=cfg, precision=precision))
 
 
 def restore_with_sinsr_naive(frames: List[np.ndarray], device="cuda", seed: int = DEFAULT_SEED,
@@ -339,34 +352,61 @@ def _get_restorer(kind: str, device, fp32: bool, cfg=None, state_dict=None):
     return m
 
 
+def restore_frames_blur_device(frames_d: torch.Tensor, blur_maps, block_size: int, *, batch_size: int = 4,
+                               max_rounds: Optional[int] = None, fp32: bool = False, cfg=None, state_dict=None,
+                               **_ignored) -> torch.Tensor:
+    """`restore_frames_blur` on a resident clip: [n,H,W,3] u8 BGR on the device and the host maps
+    in, the restored resident clip out, on the clip's device; no pixel visits the host."""
+    model = _get_restorer("blur", frames_d.device, fp32, cfg, state_dict)
+    dev = model.device
+    with torch.cuda.device(dev):
+        frames_d = frames_to_device(frames_d, dev)
+        maps_d = maps_to_device(blur_maps, frames_d.shape[0], dev)
+        return rounds_recompose_device(frames_d, maps_d, block_size, lambda d: model.restore(d, swap_rb=True), batch_size, max_rounds)
+
+
 def restore_frames_blur(frames: List[np.ndarray], blur_maps: np.ndarray, block_size: int, device, *,
                         batch_size: int = 4, max_rounds: Optional[int] = None, fp32: bool = False, cfg=None,
                         state_dict=None, **_ignored) -> List[np.ndarray]:
     """ELVIS v2 Blur client side (the loop of `_instantir_chunk_worker`, elvis.py:2947-2981) with the
     SwinTormer-style deblurrer in the model slot: for r in range(max(map)) restore every frame that
     still has map > 0, re-paste the ORIGINAL decoded blocks whose remaining level is <= 0,
-    decrement.  BGR uint8 frames in and out; `batch_size` as in the reference (elvis.py:91)."""
+    decrement.  BGR uint8 frames in and out; `batch_size` as in the reference (elvis.py:91).
+    Host to host around `restore_frames_blur_device`."""
     if not frames:
         return []
     model = _get_restorer("blur", device, fp32, cfg, state_dict)
-    return restore_frames_rounds(frames, blur_maps, block_size, model.device,
-                                 lambda d: model.restore(d, swap_rb=True), batch_size, max_rounds)
+    with torch.cuda.device(model.device):
+        return frames_to_host(restore_frames_blur_device(
+            frames_to_device(frames, model.device), blur_maps, block_size, batch_size=batch_size, max_rounds=max_rounds,
+            fp32=fp32, cfg=cfg, state_dict=state_dict))
+
+
+def restore_frames_dct_device(frames_d: torch.Tensor, strength_maps, block_size: int, *, fp32: bool = False, cfg=None,
+                              state_dict=None, **_ignored) -> torch.Tensor:
+    """`restore_frames_dct` on a resident clip: [n,H,W,3] u8 BGR on the device and the host maps
+    in, the restored resident clip out, on the clip's device; no pixel visits the host."""
+    model = _get_restorer("dct", frames_d.device, fp32, cfg, state_dict)
+    dev = model.device
+    with torch.cuda.device(dev):
+        frames_d = frames_to_device(frames_d, dev)
+        maps_d = maps_to_device(strength_maps, frames_d.shape[0], dev)
+        restored = model.restore(frames_d)
+        return ops.recompose_u8(frames_d, restored, maps_d, block_size, 0)
 
 
 def restore_frames_dct(frames: List[np.ndarray], strength_maps: np.ndarray, block_size: int, device, *,
                        fp32: bool = False, cfg=None, state_dict=None, **_ignored) -> List[np.ndarray]:
     """ELVIS v2 DCT client side.  The reference has no code for this slot; the build
     defines it with the round loop's signature and ONE pass: the LaplacianVCAR-style DCN restorer
-    sees the whole chunk (its temporal window crosses frames), then `level > 0 ? restored : decoded`."""
+    sees the whole chunk (its temporal window crosses frames), then `level > 0 ? restored : decoded`.
+    Host to host around `restore_frames_dct_device`."""
     if not frames:
         return []
     model = _get_restorer("dct", device, fp32, cfg, state_dict)
-    dev = model.device
-    with torch.cuda.device(dev):
-        frames_d = frames_to_device(frames, dev)
-        maps_d = maps_to_device(strength_maps, frames_d.shape[0], dev)
-        restored = model.restore(frames_d)
-        return frames_to_host(ops.recompose_u8(frames_d, restored, maps_d, block_size, 0))
+    with torch.cuda.device(model.device):
+        return frames_to_host(restore_frames_dct_device(
+            frames_to_device(frames, model.device), strength_maps, block_size, fp32=fp32, cfg=cfg, state_dict=state_dict))
 
 
 # ----------------------------------------------------------------------------- Blur / DCT slots, host to host

@@ -407,6 +407,24 @@ int elvis_degrade_gaussian_fx_u8(const uint8_t* src, const int32_t* rounds, uint
  * go out as dwords when w % 4 == 0 and both pointers are 4-byte aligned, byte by byte otherwise. */
 int elvis_rgb_to_i420_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int bgr, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ decoder hand-off (i420_in.hip) */
+
+/* cv2.cvtColor(planes, COLOR_YUV2RGB_I420) per frame, the way back from elvis_rgb_to_i420_u8: what a decoder emits
+ * (ffmpeg -f yuv4mpegpipe / rawvideo yuv420p in place of the decode_video(...%05d.png) of run_elvis) to the resident
+ * clip every restorer takes; bgr != 0 writes B,G,R (COLOR_YUV2BGR_I420).  src: [n, h*3/2, w] u8 - per frame the Y
+ * plane h x w, then U h/2 x w/2, then V h/2 x w/2, each dense; dst: [n,h,w,3] u8.  OpenCV 4.x YUV420p2RGB8Invoker
+ * restated (parity with cv2 unpinned), int32, 20-bit fixed point: with u = U[y/2][x/2] - 128, v = V[y/2][x/2] - 128
+ * (the quad's one chroma pair, replicated, not interpolated) and yy = max(0, Y[y][x] - 16) * 1220542 + (1 << 19),
+ *   R = sat8((yy + 1673527 v)             >> 20)
+ *   G = sat8((yy -  852492 v - 409993 u)  >> 20)
+ *   B = sat8((yy + 2116026 u)             >> 20)
+ * where >> is an arithmetic shift (a negative sum floors, then saturates to 0) and sat8 clamps to [0, 255].  An odd h
+ * or w, a negative dimension or a null pointer with work to do is ELVIS_E_INVALID before anything is launched; n == 0
+ * does nothing and succeeds.  Rows move 16 bytes at a time when w % 16 == 0 and both pointers are 16-byte aligned
+ * (i420_to_rgb_x16_kernel), as dwords when w % 4 == 0 and both are 4-byte aligned, byte by byte otherwise
+ * (i420_to_rgb_kernel); elvis_last_launch names the kernel, "<rgb>" or "<bgr>". */
+int elvis_i420_to_rgb_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int bgr, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ classical restorers
  * The OpenCV baselines of ELVIS and Presley, per block of a uint8 NHWC frame; map[n, by, bx] int32 with
  * by = H / block_size, bx = W / block_size (floor).  PIXELS OUTSIDE THE BLOCK GRID (the rows and columns past the last
