@@ -42,5 +42,9 @@ from .drivers import (calculate_removability_scores_from_frames, restore_blur_ad
 from .restore import (get_sinsr_model, get_sinsr_upsample_fn, restore_frames_blur, restore_frames_blur_device,  # noqa: F401
                       restore_frames_dct, restore_frames_dct_device, restore_frames_rounds, restore_frames_sinsr,
                       restore_frames_sinsr_device, restore_with_sinsr_naive)
+from .restore import (get_realesrgan_upsample_fn, get_realesrgan_upsampler, restore_frames_realesrgan,  # noqa: F401
+                      restore_frames_realesrgan_device, restore_with_realesrgan_naive)
+from .drivers import restore_downsampled_with_realesrgan  # noqa: F401
+from .weights import RRDBNetConfig, load_realesrgan_state_dict  # noqa: F401
 
 __version__ = "0.1.0"

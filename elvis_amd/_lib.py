@@ -108,6 +108,10 @@ SIGNATURES = {
     "elvis_png_gather": [vp, i64, vp, i32, vp, i64, vp, vp],
     "elvis_png_inflate": [vp, i64, vp, vp, i64, vp, vp, i32, vp],
     "elvis_png_unfilter": [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_rrdb_packed_weight_bytes": [i32, i32],
+    "elvis_rrdb_pack_weights": [vp, i32, i32, i32, i32, vp],
+    "elvis_rrdb_conv3x3": [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, i32, vp],
+    "elvis_rrdb_input_u8": [vp, vp, i32, i32, i32, i32, i32, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
@@ -145,6 +149,7 @@ def lib() -> C.CDLL:
         handle.elvis_ssim_workspace_bytes.restype = C.c_size_t
         handle.elvis_inpaint_workspace_bytes.restype = C.c_size_t
         handle.elvis_lpips_distance_workspace_bytes.restype = C.c_size_t
+        handle.elvis_rrdb_packed_weight_bytes.restype = C.c_size_t
         if handle.elvis_abi_version() != 1:
             raise RuntimeError("libelvis_amd.so ABI version mismatch")
         _lib = handle

@@ -2,6 +2,7 @@
 (elvis.py:4722, 4794) with the MI355X restorers in the model slots.
 
   restore_downsampled_with_sinsr   <- restore_downsampled_with_realesrgan  (elvis.py:2685-2769)
+  restore_downsampled_with_realesrgan  <- the same function, with the network the reference runs there (RRDBNet)
   restore_blur_adaptive            <- restore_with_instantir_adaptive      (elvis.py:3000-3160)
   restore_dct_adaptive             -  the DCT slot the reference never wrote, given the
                                       Blur driver's shape
@@ -285,6 +286,55 @@ def restore_downsampled_with_sinsr(
                 chunk_for_devices(len(names), devs), maps, block_size, 0, kw if _shard_fn is None else {}, png_writer, png_reader)
 
 
+def _realesrgan_shard(frames, maps, block_size, device, first_frame_index, **kw):
+    from .restore import restore_frames_realesrgan
+    return restore_frames_realesrgan(frames, maps, block_size, device, **kw)
+
+
+def restore_downsampled_with_realesrgan(
+    input_frames_dir: str,
+    output_frames_dir: str,
+    downscale_maps: np.ndarray,
+    block_size: int,
+    *,
+    model_name: str = "RealESRGAN_x4plus",
+    denoise_strength: float = 1.0,
+    tile: int = 0,
+    tile_pad: int = 10,
+    pre_pad: int = 0,
+    fp32: bool = False,
+    devices: Optional[Sequence[DeviceSpec]] = None,
+    parallel_chunk_length: Optional[int] = None,
+    per_device_workers: int = 1,
+    model_path: Optional[str] = None,
+    schedule: str = "staged",
+    png_writer: str = "pil",
+    png_reader: str = "pil",
+    _shard_fn: Optional[ShardFn] = None,
+) -> None:
+    """Adaptive Real-ESRGAN restoration over a directory of frames: the reference's function of this name
+    (elvis.py:2685-2769) with its own network, RRDBNet, in the model slot (`restore.restore_frames_realesrgan`, which
+    lists the departures: no fp32, no pre_pad, no denoise_strength, `tile` / `tile_pad` ignored).  `model_path` is the
+    checkpoint file (e.g. "RealESRGAN_x4plus.pth"); without it the weights are seeded and synthetic.
+    `parallel_chunk_length` / `per_device_workers` are accepted and ignored, as in the reference (elvis.py:2698-2699)."""
+    _ = (parallel_chunk_length, per_device_workers)
+    _check_png_writer(png_writer)
+    _check_png_reader(png_reader)
+    if _shard_fn is None:
+        from .restore import _check_realesrgan_args
+        from .weights import realesrgan_config
+        _check_realesrgan_args(denoise_strength, pre_pad, fp32)
+        realesrgan_config(model_name)
+    names, maps = _frames_and_maps(input_frames_dir, downscale_maps, "Downscale maps")
+    clear_directory(output_frames_dir)
+    os.makedirs(output_frames_dir, exist_ok=True)
+    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
+    kw = dict(model_name=model_name, denoise_strength=denoise_strength, tile=tile, tile_pad=tile_pad, pre_pad=pre_pad,
+              fp32=fp32, model_path=model_path, schedule=schedule)
+    _run_shards(_shard_fn or _realesrgan_shard, input_frames_dir, output_frames_dir, names,
+                chunk_for_devices(len(names), devs), maps, block_size, 0, kw if _shard_fn is None else {}, png_writer, png_reader)
+
+
 def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int, devices, halo: int, kw: dict,
                       what: str, allow_cpu: bool, png_writer: str = "pil", png_reader: str = "pil") -> None:
     _check_png_writer(png_writer)
@@ -474,7 +524,7 @@ def restore_shrunk_frames(
 
 
 # ----------------------------------------------------------------------------- clip files: decoder output in, encoder input out
-YUV_CLIP_KINDS = {"sinsr": "Downscale maps", "blur": "blur_maps", "dct": "strength_maps"}
+YUV_CLIP_KINDS = {"sinsr": "Downscale maps", "blur": "blur_maps", "dct": "strength_maps", "realesrgan": "Downscale maps"}
 # (clip, maps, block_size, device, first_frame_index, **kw) -> clip ; resident [n,H,W,3] u8 BGR in and out
 ClipShardFn = Callable[..., torch.Tensor]
 
@@ -494,7 +544,13 @@ def _dct_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
     return restore_frames_dct_device(clip, maps, block_size, **kw)
 
 
-_CLIP_SHARDS = {"sinsr": _sinsr_clip_shard, "blur": _blur_clip_shard, "dct": _dct_clip_shard}
+def _realesrgan_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
+    from .restore import restore_frames_realesrgan_device
+    return restore_frames_realesrgan_device(clip, maps, block_size, **kw)
+
+
+_CLIP_SHARDS = {"sinsr": _sinsr_clip_shard, "blur": _blur_clip_shard, "dct": _dct_clip_shard,
+                "realesrgan": _realesrgan_clip_shard}
 _FRAME_MARKER = b"FRAME\n"
 
 
@@ -555,8 +611,8 @@ def restore_yuv_clip(
     _shard_fn: Optional[ClipShardFn] = None,
     **kw,
 ) -> None:
-    """One of the three model slots - `kind` "sinsr" (`restore_frames_sinsr`), "blur" (`restore_frames_blur`) or "dct"
-    (`restore_frames_dct`) - from a clip file to a clip file: what a decoder emits (`ffmpeg -f yuv4mpegpipe`, or
+    """One of the model slots - `kind` "sinsr" (`restore_frames_sinsr`), "realesrgan" (`restore_frames_realesrgan`),
+    "blur" (`restore_frames_blur`) or "dct" (`restore_frames_dct`) - from a clip file to a clip file: what a decoder emits (`ffmpeg -f yuv4mpegpipe`, or
     `-f rawvideo -pix_fmt yuv420p`) in, what the encoders and VMAF take out, no directory of PNGs in between.
 
     `input_path` is a `.y4m` file, or a raw `.yuv` with `width` and `height`; `output_path` is a `.y4m` (`handoff.y4m_header`

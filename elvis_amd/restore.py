@@ -312,6 +312,166 @@ def restore_with_sinsr_naive(frames: List[np.ndarray], device="cuda", seed: int 
         return frames_to_host(out)
 
 
+# ----------------------------------------------------------------------------- Real-ESRGAN (RRDBNet) in the Downsample slot
+_REALESRGAN_CACHE: Dict[tuple, tuple] = {}
+
+
+def _check_realesrgan_args(denoise_strength, pre_pad, fp32) -> None:
+    """The departures from the reference call: each is refused, none is silently ignored."""
+    if fp32:
+        raise ValueError("Real-ESRGAN: fp32=True is not built; the network runs in f16 with fp32 accumulation "
+                         "(the reference's GPU precision, half=True)")
+    if int(pre_pad) != 0:
+        raise ValueError(f"Real-ESRGAN: pre_pad={pre_pad} is not built; only pre_pad=0")
+    if float(denoise_strength) != 1.0:
+        raise ValueError(f"Real-ESRGAN: denoise_strength={denoise_strength} applies to realesr-general-x4v3 only "
+                         "(an SRVGG model, not built); pass 1.0")
+
+
+def get_realesrgan_upsampler(device, *, model_name: str = "RealESRGAN_x4plus", denoise_strength: float = 1.0,
+                             tile: int = 0, tile_pad: int = 10, pre_pad: int = 0, fp32: bool = False,
+                             model_path=None, state_dict=None):
+    """Get or create the cached RRDBNet runtime for `device` (elvis.py:2611-2637: thread-safe, one per device, model
+    and weights, never freed).  `model_name` picks the architecture from the reference's table (`weights.realesrgan_config`);
+    the weights are `state_dict` (a state dict or checkpoint dict), else the checkpoint file `model_path`, else SEEDED
+    SYNTHETIC ones - nothing is downloaded.  `tile` and `tile_pad` are accepted and ignored: whole frames fit.
+    `fp32=True`, `pre_pad != 0` and `denoise_strength != 1` are a ValueError."""
+    from .realesrgan import RRDBNetModel
+    from .weights import realesrgan_config
+    _check_realesrgan_args(denoise_strength, pre_pad, fp32)
+    _ = (tile, tile_pad)
+    cfg = realesrgan_config(model_name)
+    dev = torch.device(device)
+    L.require_gpu(dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    source = state_dict if state_dict is not None else model_path
+    # the entry keeps a strong reference to a caller's dict, so its id cannot be reused by another object
+    key = (str(dev), cfg, id(state_dict) if state_dict is not None else (str(model_path) if model_path is not None else None))
+    with _MODEL_LOCK:
+        hit = _REALESRGAN_CACHE.get(key)
+        if hit is None:
+            try:
+                m = RRDBNetModel(cfg, source, dev)
+            except RuntimeError as exc:
+                raise RuntimeError(f"Real-ESRGAN failed on {dev}: {exc}") from exc
+            hit = _REALESRGAN_CACHE[key] = (m, state_dict)
+    return hit[0]
+
+
+def _realesrgan_up(model, cur: torch.Tensor, swap_rb: bool = True) -> torch.Tensor:
+    try:
+        return model.forward(cur, swap_rb=swap_rb)
+    except RuntimeError as exc:       # elvis.py:2517-2519
+        raise RuntimeError(f"Real-ESRGAN failed on {model.device}: {exc}") from exc
+
+
+def get_realesrgan_upsample_fn(device, *, model_name: str = "RealESRGAN_x4plus", scale: int = 2, **kw) -> Callable[[np.ndarray], np.ndarray]:
+    """P1: "a single 2x upscale" of a BGR uint8 HWC image (elvis.py:2528, 2575), what `enhance(img, outscale=scale)`
+    returns.  An x2 model at scale=2 and an x4 model at scale=4 return the network's output; an x4 model at scale=2
+    area-halves it, where `enhance` resizes with cv2.INTER_LANCZOS4 (PARITY UNPINNED vs cv2)."""
+    model = get_realesrgan_upsampler(device, model_name=model_name, **kw)
+    if scale not in (2, 4) or scale > model.scale:
+        raise ValueError(f"scale must be 2 or 4 and at most the model's {model.scale}, got {scale!r}")
+
+    def upsample_fn(img: np.ndarray) -> np.ndarray:
+        with torch.cuda.device(model.device):
+            out = _realesrgan_up(model, frames_to_device([img], model.device))
+            if scale != model.scale:
+                out = ops.area_downscale_u8(out, model.scale // scale)
+            return frames_to_host(out)[0]
+
+    return upsample_fn
+
+
+def restore_frames_realesrgan_device(frames_d: torch.Tensor, downscale_maps, block_size: int, *,
+                                     model_name: str = "RealESRGAN_x4plus", denoise_strength: float = 1.0, tile: int = 0,
+                                     tile_pad: int = 10, pre_pad: int = 0, fp32: bool = False, model_path=None,
+                                     state_dict=None, schedule: str = "staged", **_ignored) -> torch.Tensor:
+    """`restore_frames_realesrgan` on a resident clip: [n,H,W,3] u8 BGR on the device and the host maps in, the
+    restored resident clip out, on the clip's device; no pixel visits the host."""
+    model = get_realesrgan_upsampler(frames_d.device, model_name=model_name, denoise_strength=denoise_strength, tile=tile,
+                                     tile_pad=tile_pad, pre_pad=pre_pad, fp32=fp32, model_path=model_path, state_dict=state_dict)
+    if schedule not in ("staged", "single4x"):
+        raise ValueError(f"unknown schedule '{schedule}'")
+    if schedule == "single4x" and model.scale != 4:
+        raise ValueError(f"schedule='single4x' needs an x4 model, '{model_name}' is x{model.scale}")
+    with torch.cuda.device(model.device):
+        frames_d = frames_to_device(frames_d, model.device)
+        n, H, W, _ = frames_d.shape
+        maps_d = maps_to_device(downscale_maps, n, model.device)
+        maxlv = maps_d.flatten(1).max(dim=1).values.tolist() if n else []
+        out = torch.empty_like(frames_d)
+        if schedule == "single4x":
+            if H % 4 or W % 4 or H % block_size or W % block_size:
+                raise ValueError("Image dimensions must be divisible by block_size and by 4.")
+            idx = [i for i, v in enumerate(maxlv) if v > 0]
+            rest = [i for i, v in enumerate(maxlv) if v <= 0]
+            if rest:
+                out[rest] = frames_d[rest]
+            if idx:
+                it = torch.tensor(idx, device=model.device)
+                sub_f, sub_m = frames_d[it].contiguous(), maps_d[it].contiguous()
+                sr = _realesrgan_up(model, ops.area_downscale_u8(sub_f, 4))
+                out[it] = ops.recompose_u8(sub_f, sr, sub_m, block_size, 0)
+            return out
+        # the reference derives the stage schedule from each frame's own max level (elvis.py:2561): group frames by it
+        for lv in sorted(set(maxlv)):
+            idx = [i for i, v in enumerate(maxlv) if v == lv]
+            if lv <= 0:
+                out[idx] = frames_d[idx]
+                continue
+            it = torch.tensor(idx, device=model.device)
+            out[it] = upscale_adaptive_device(frames_d[it].contiguous(), maps_d[it].contiguous(), block_size,
+                                              lambda cur: _realesrgan_up(model, cur), sr_scale=model.scale)
+        return out
+
+
+def restore_frames_realesrgan(frames: List[np.ndarray], downscale_maps: np.ndarray, block_size: int, device, *,
+                              model_name: str = "RealESRGAN_x4plus", denoise_strength: float = 1.0, tile: int = 0,
+                              tile_pad: int = 10, pre_pad: int = 0, fp32: bool = False, model_path=None, state_dict=None,
+                              schedule: str = "staged", **_ignored) -> List[np.ndarray]:
+    """The reference's `restore_frames_realesrgan` (elvis.py:2640-2682) with the network it runs there, RRDBNet, on the
+    device: BGR uint8 frames + per-block log2 downscale maps -> restored frames.  Host to host around
+    `restore_frames_realesrgan_device`.
+
+    Everything goes through `upscale_adaptive_device`.  An x2 model (`RealESRGAN_x2plus`) runs it with `sr_scale=2`: the
+    reference's loop (elvis.py:2570-2598) line by line, no resize anywhere.  An x4 model runs it with `sr_scale=4`:
+    stages advance by 4x while the remaining factor allows, and a trailing 2x stage area-halves the x4 output where
+    `enhance(outscale=2)` resizes with cv2.INTER_LANCZOS4 (PARITY UNPINNED vs cv2).  `schedule="single4x"`: one x4 call
+    from the /4 level per frame, whatever the map's maximum (the benchmark path of the SinSR slot).
+
+    Weights: `state_dict`, else the checkpoint file `model_path` (e.g. "RealESRGAN_x4plus.pth"), else seeded synthetic
+    ones; nothing is downloaded.  `tile` / `tile_pad` are accepted and ignored (whole frames fit); `fp32=True`,
+    `pre_pad != 0` and `denoise_strength != 1` are a ValueError.  A runtime failure is
+    `RuntimeError("Real-ESRGAN failed on <device>: ...")` (elvis.py:2517-2519)."""
+    if not frames:
+        return []
+    model = get_realesrgan_upsampler(device, model_name=model_name, denoise_strength=denoise_strength, tile=tile,
+                                     tile_pad=tile_pad, pre_pad=pre_pad, fp32=fp32, model_path=model_path, state_dict=state_dict)
+    with torch.cuda.device(model.device):
+        return frames_to_host(restore_frames_realesrgan_device(
+            frames_to_device(frames, model.device), downscale_maps, block_size, model_name=model_name, model_path=model_path,
+            state_dict=state_dict, schedule=schedule))
+
+
+def restore_with_realesrgan_naive(frames: List[np.ndarray], device="cuda", model_name: str = "RealESRGAN_x4plus",
+                                  tile: int = 0, tile_pad: int = 10, pre_pad: int = 0, fp32: bool = False,
+                                  denoise_strength: float = 1.0, **kwargs) -> List[np.ndarray]:
+    """P3 restore_fn (utils.py:1428-1473): RGB uint8 frames, each upscaled by the network and brought back to its own
+    size - by an area downscale where the reference resizes with cv2.INTER_LANCZOS4 (PARITY UNPINNED vs cv2).
+    `model_path=` / `state_dict=` choose the weights; other unknown keywords are accepted and ignored."""
+    if not frames:
+        return []
+    dev = L.resolve_device(device)
+    model = get_realesrgan_upsampler(dev, model_name=model_name, denoise_strength=denoise_strength, tile=tile,
+                                     tile_pad=tile_pad, pre_pad=pre_pad, fp32=fp32, model_path=kwargs.get("model_path"),
+                                     state_dict=kwargs.get("state_dict"))
+    with torch.cuda.device(model.device):
+        d = frames_to_device(frames, model.device)
+        return frames_to_host(ops.area_downscale_u8(_realesrgan_up(model, d, swap_rb=False), model.scale))
+
+
 def restore_frames_rounds(frames: List[np.ndarray], maps: np.ndarray, block_size: int, device,
                           restore_dev: Callable[[torch.Tensor], torch.Tensor], batch_size: int = 4,
                           max_rounds: Optional[int] = None) -> List[np.ndarray]:

@@ -355,3 +355,130 @@ def make_lpips_weights(seed: int = 0) -> Dict[str, torch.Tensor]:
     for tap, c in enumerate(LPIPS_TAP_CHANNELS):
         I.sd[f"lin{tap}.model.1.weight"] = I.randn(1, c, 1, 1).abs() / math.sqrt(c)
     return I.sd
+
+
+# ----------------------------------------------------------------------------- Real-ESRGAN (RRDBNet)
+@dataclass(frozen=True)
+class RRDBNetConfig:
+    """`RRDBNet(3, 3, num_feat, num_block, num_grow_ch, scale)` as `_instantiate_realesrgan_upsampler` builds it
+    (elvis.py:2415-2430).  The kernels are written for 64 features and 32 growth channels; scale 2 feeds the network a
+    2x pixel-unshuffled image (12 channels) and scale 4 the image itself - the body and the two nearest-2x up-convs are
+    the same network either way."""
+    scale: int = 4
+    num_block: int = 23
+    num_feat: int = 64
+    num_grow_ch: int = 32
+
+    def __post_init__(self):
+        if self.scale not in (2, 4):
+            raise ValueError(f"RRDBNetConfig: scale must be 2 or 4, got {self.scale!r}")
+        if self.num_feat != 64 or self.num_grow_ch != 32:
+            raise ValueError(f"RRDBNetConfig: only num_feat=64, num_grow_ch=32 are built, got {self.num_feat}, {self.num_grow_ch}")
+        if not isinstance(self.num_block, int) or self.num_block < 1:
+            raise ValueError(f"RRDBNetConfig: num_block must be a positive integer, got {self.num_block!r}")
+
+    @property
+    def in_channels(self) -> int:
+        return 3 * (4 if self.scale == 2 else 1)
+
+
+# model_name -> (num_block, netscale): the RRDBNet rows of the reference's table (elvis.py:2415-2430)
+REALESRGAN_MODELS = {
+    "RealESRGAN_x4plus": (23, 4),
+    "RealESRNet_x4plus": (23, 4),
+    "RealESRGAN_x4plus_anime_6B": (6, 4),
+    "RealESRGAN_x2plus": (23, 2),
+}
+# the reference's SRVGGNetCompact rows: another network, not built here
+REALESRGAN_SRVGG_MODELS = ("realesr-animevideov3", "realesr-general-x4v3")
+
+
+def realesrgan_config(model_name: str) -> RRDBNetConfig:
+    """The RRDBNet configuration of a reference model name, cut at the first '.' as the reference does
+    (`model_name.split('.')[0]`).  The two SRVGG names and unknown names are a ValueError."""
+    name = str(model_name).split(".")[0]
+    if name in REALESRGAN_SRVGG_MODELS:
+        raise ValueError(f"Real-ESRGAN model '{name}' is an SRVGGNetCompact; only the RRDBNet models "
+                         f"{tuple(REALESRGAN_MODELS)} are built")
+    if name not in REALESRGAN_MODELS:
+        raise ValueError(f"Unknown Real-ESRGAN model: {name}")
+    num_block, scale = REALESRGAN_MODELS[name]
+    return RRDBNetConfig(scale=scale, num_block=num_block)
+
+
+def rrdbnet_layout(cfg: RRDBNetConfig):
+    """[(key, cout, cin)] of every conv of the network, in forward order; each has `key.weight` [cout,cin,3,3] and
+    `key.bias` [cout]."""
+    f, g = cfg.num_feat, cfg.num_grow_ch
+    out = [("conv_first", f, cfg.in_channels)]
+    for i in range(cfg.num_block):
+        for r in (1, 2, 3):
+            for c in range(1, 5):
+                out.append((f"body.{i}.rdb{r}.conv{c}", g, f + (c - 1) * g))
+            out.append((f"body.{i}.rdb{r}.conv5", f, f + 4 * g))
+    out += [("conv_body", f, f), ("conv_up1", f, f), ("conv_up2", f, f), ("conv_hr", f, f), ("conv_last", 3, f)]
+    return out
+
+
+def make_rrdbnet_weights(cfg: RRDBNetConfig = RRDBNetConfig(), seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded SYNTHETIC weights of the Real-ESRGAN slot: every conv normal with std 0.1 * sqrt(2 / fan_in) and a zero
+    bias, which is basicsr's `default_init_weights(scale=0.1)`.  They exercise the network, they restore nothing; the
+    trained checkpoints go through `load_realesrgan_state_dict`."""
+    g = torch.Generator().manual_seed(int(seed))
+    sd: Dict[str, torch.Tensor] = {}
+    for key, cout, cin in rrdbnet_layout(cfg):
+        sd[key + ".weight"] = torch.randn((cout, cin, 3, 3), generator=g, dtype=torch.float32) * (0.1 * math.sqrt(2.0 / (cin * 9)))
+        sd[key + ".bias"] = torch.zeros(cout, dtype=torch.float32)
+    return sd
+
+
+def _rrdbnet_config_of(sd) -> RRDBNetConfig:
+    blocks = {int(k.split(".")[1]) for k in sd if k.startswith("body.") and k.split(".")[1].isdigit()}
+    if not blocks:
+        raise ValueError("Real-ESRGAN state dict: no 'body.{i}...' key - not an RRDBNet checkpoint")
+    w = sd.get("conv_first.weight")
+    if w is None:
+        raise ValueError("Real-ESRGAN state dict: missing key 'conv_first.weight'")
+    cin = int(w.shape[1]) if getattr(w, "ndim", 0) == 4 else -1
+    if cin not in (3, 12):
+        raise ValueError(f"Real-ESRGAN state dict: 'conv_first.weight' has shape {tuple(w.shape)}; 3 (x4) or 12 (x2) input channels are built")
+    return RRDBNetConfig(scale=4 if cin == 3 else 2, num_block=max(blocks) + 1)
+
+
+def load_realesrgan_state_dict(path_or_dict, cfg: "RRDBNetConfig | None" = None) -> Dict[str, torch.Tensor]:
+    """A Real-ESRGAN RRDBNet checkpoint as a checked dict of fp32 CPU tensors.  A path is read with
+    `torch.load(path, map_location="cpu", weights_only=True)`; a checkpoint dict is unwrapped as RealESRGANer does
+    (`params_ema` if present, else `params`, else the dict itself).  Keys: `conv_first`, `body.{i}.rdb{1,2,3}.conv{1..5}`,
+    `conv_body`, `conv_up1`, `conv_up2`, `conv_hr`, `conv_last`, each with `.weight` and `.bias`.  Without `cfg` the block
+    count and the scale are read from the keys.  A missing key, an extra key or a wrong shape is a ValueError that names
+    the key.  Nothing is ever downloaded."""
+    import os
+    if isinstance(path_or_dict, (str, bytes, os.PathLike)):
+        sd = torch.load(os.fspath(path_or_dict), map_location="cpu", weights_only=True)
+    else:
+        sd = path_or_dict
+    if not isinstance(sd, dict):
+        raise ValueError(f"Real-ESRGAN checkpoint: expected a dict, got {type(sd).__name__}")
+    for wrap in ("params_ema", "params"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+            break
+    if cfg is None:
+        cfg = _rrdbnet_config_of(sd)
+    expect = {}
+    for key, cout, cin in rrdbnet_layout(cfg):
+        expect[key + ".weight"] = (cout, cin, 3, 3)
+        expect[key + ".bias"] = (cout,)
+    out: Dict[str, torch.Tensor] = {}
+    for key, shape in expect.items():
+        if key not in sd:
+            raise ValueError(f"Real-ESRGAN state dict: missing key '{key}'")
+        t = sd[key]
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"Real-ESRGAN state dict: '{key}' has shape {got}, expected {shape}")
+        out[key] = t.detach().to("cpu", torch.float32).contiguous()
+    for key in sd:
+        if key not in expect:
+            raise ValueError(f"Real-ESRGAN state dict: unexpected key '{key}'")
+    return out

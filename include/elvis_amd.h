@@ -687,6 +687,45 @@ int elvis_png_inflate(const uint8_t* streams, int64_t streams_bytes, const int64
 int elvis_png_unfilter(uint8_t* filtered, int64_t stride, uint8_t* frames, uint32_t* status, int n, int h, int w, int bpp,
                        int channels, int order, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ Real-ESRGAN / RRDBNet (rrdb.hip)
+ * The network behind RealESRGANer.enhance (elvis.py:2515): RRDBNet(3, 3, 64, num_block, 32, scale) on f16 NHWC tensors.
+ * Channel counts are the padded ones the kernel runs: cin in {32, 64, 96, 128, 160, 192}, cout in {32, 64}. */
+
+/* Bytes of the packed f16 weights of one conv (9 * cin * cout * 2); 0 for an unsupported cin or cout.  elvis.py:2515 */
+size_t elvis_rrdb_packed_weight_bytes(int cin, int cout);
+
+/* Host function, no GPU: fp32 OIHW [cout_real][cin_real][3][3] -> packed f16 [cin/32][tap = ky*3+kx][cout][32]
+ * (round to nearest even), element [kc][tap][co][k] = w[co][32 kc + k][ky][kx]; input channels past cin_real and output
+ * channels past cout_real are zero (conv_first: 3 or 12 real inputs in 32; conv_last: 3 real outputs in 32).
+ * elvis.py:2515 */
+int elvis_rrdb_pack_weights(const float* w_oihw_host, int cin_real, int cout_real, int cin, int cout, void* packed_host);
+
+/* 3x3 / stride 1 / pad 1 conv of a dense block (elvis.py:2515), f16 in, fp32 accumulate on v_mfma_f32_16x16x32_f16.
+ * x: f16 [n,h,w,x_pitch], channels [0, cin) are read.  upsample != 0: the conv sees the nearest-2x image (pixel (y, x)
+ * reads (y >> 1, x >> 1)), ho = 2h, wo = 2w; otherwise ho = h, wo = w.  w_packed: elvis_rrdb_pack_weights' layout on
+ * the device; bias: fp32 [cout].  out: f16 [n,ho,wo,out_pitch], channels [out_coff, out_coff + cout) are written and no
+ * other byte.  Epilogue in fp32: v = z + bias; lrelu != 0: v = v > 0 ? v : 0.2f * v; y = s0 * v + s1 * r1 + r2 with r1, r2
+ * f16 [n,ho,wo,r*_pitch] read at channels [0, cout), each optional (NULL); y is stored as f16, round to nearest even.
+ * out_u8 != 0 (conv_last; cout = 32, out_coff = 0): out is u8 [n,ho,wo,3], byte c = rint(clamp(y_c, 0, 1) * 255) (half
+ * to even) from the fp32 y of the three real channels, written at 2 - c with swap_rb.
+ * Aliasing: out may be x itself (same pointer and pitch, no upsample) when out_coff >= cin - the in-place concat of a
+ * dense block; r1 and r2 may alias x; a residual may be out itself (same pointer and pitch) when out_coff == 0 (each
+ * element is read, then written, by one lane) or out_coff >= cout.  Any other overlap of out with x or a residual is
+ * ELVIS_E_INVALID, as are an unsupported cin / cout, a pitch or offset that is no multiple of 8 (residuals: 4) or too
+ * small, out_u8 with cout != 32, a null or misaligned pointer (x, weights, bias 16 bytes; out, residuals 8).  Offsets
+ * are 64-bit.  n, h or w == 0 does nothing and succeeds.  elvis_last_launch: "rrdb_conv3x3_kernel<32>" or "<64>". */
+int elvis_rrdb_conv3x3(const void* x, int x_pitch, const void* w_packed, const float* bias, void* out, int out_pitch,
+                       int out_coff, const void* r1, int r1_pitch, const void* r2, int r2_pitch, int n, int h, int w,
+                       int cin, int cout, int upsample, int lrelu, float s0, float s1, int out_u8, int swap_rb,
+                       elvis_stream_t stream);
+
+/* The network's input stage (what RealESRGANer.pre_process and RRDBNet.forward do before conv_first, elvis.py:2515):
+ * src u8 [n,h,w,3] -> dst f16 [n,ceil(h/s),ceil(w/s),32], values f16(v / 255.0f), channel order reversed with swap_rb.
+ * s = 1: channels 0..2.  s = 2: pixel-unshuffle, input (c, 2y+sy, 2x+sx) at channel 4c + 2sy + sx
+ * (torch.nn.functional.pixel_unshuffle's order); an odd h or w is first extended by one reflected row or column
+ * (index h reads h - 2, F.pad(..., 'reflect')) and must then be at least 3.  Channels past 3*s*s are zero. */
+int elvis_rrdb_input_u8(const uint8_t* src, void* dst, int n, int h, int w, int s, int swap_rb, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
