@@ -26,175 +26,206 @@ from the directory, so results do not depend on the device count.
 
 Every driver that writes frames takes `png_writer="pil"` (the default: frameio.save_frame / save_mask, files as before)
 or `"device"`: the PNGs are then written by the GPU (png.py) - decodable by any PNG reader to the same pixels, bytes not
-PIL's or cv2's.  The v1 shards hand their resident stretched, inpainted frames and full-resolution masks to the writer
-directly (`png.save_frames_device`); a model worker's restored frames go up once more (`png.save_frames`).  Any other value is a ValueError; "device" without a
-GPU raises.
+PIL's or cv2's.  Every built-in shard function returns a resident clip, and the writer takes it as it is
+(`png.save_frames_device`: only finished files come down), as it takes a v1 shard's stretched frames and full-resolution
+masks; only the host frames of a replaced `_shard_fn` go up once more (`png.save_frames`).  Any other value is a
+ValueError; "device" without a GPU raises.
 
 Every driver also takes `png_reader="pil"` (the default: frameio.load_frame per file) or `"device"`: a worker's frame
-range is then decoded by the GPU (png.load_frames_device) into one resident clip.  The v1 shards take that clip as it
-is - with both options "device" a v1 shard's pixels never visit the host; the model restorers' `restore_frames_*` are
-host-to-host functions and get `frames_to_host` of it, as does a replaced `_shard_fn`.  Same errors as `png_writer`.
+range is then decoded by the GPU (png.load_frames_device) into one resident clip.  The built-in shard functions - v1
+and the model slots' `restore_frames_*_device` alike - take that clip as it is: with both options "device" a worker's
+pixels never visit the host.  A replaced `_shard_fn` gets `frames_to_host` of it.  Same errors as `png_writer`.
+
+One worker (`_shard_worker`) serves every driver, the clip-file one included: a `ShardJob` names the shard function, the
+source it loads its frame range from and the sink it saves it to (a PNG directory or a clip file), and whether the shard
+function works on a resident clip or on host frames.
 """
 from __future__ import annotations
 
 import multiprocessing
 import os
+from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
+from . import recompose   # frames_to_device / frames_to_host are looked up at the call, where tests replace them
 from .frameio import clear_directory, get_frame_paths, load_block_masks, load_frame, save_frame, save_mask
 from .sharding import ChunkSpec, chunk_for_devices, resolve_device_list
 
 DeviceSpec = Union[int, str, torch.device]
 # (frames, maps, block_size, device, first_frame_index, **kw) -> frames ; replaceable for host-only tests
 ShardFn = Callable[..., List[np.ndarray]]
+# (clip, maps, block_size, device, first_frame_index, **kw) -> clip ; resident [n,H,W,3] u8 BGR in and out
+ClipShardFn = Callable[..., torch.Tensor]
 
 
 PNG_WRITERS = ("pil", "device")
-
-
-def _check_png_writer(png_writer) -> str:
-    """`png_writer=` of the directory drivers: "pil" (frameio.save_frame / save_mask, the default) or "device" (png.py:
-    the files are written by the GPU - any PNG reader decodes them to the same pixels, the bytes are not PIL's)."""
-    if png_writer not in PNG_WRITERS:
-        raise ValueError(f"png_writer must be one of {PNG_WRITERS}, got {png_writer!r}")
-    return png_writer
-
-
 PNG_READERS = ("pil", "device")
 
 
-def _check_png_reader(png_reader) -> str:
-    """`png_reader=` of the directory drivers: "pil" (frameio.load_frame, the default) or "device" (png.py: the files are
-    decoded by the GPU into a resident clip - the same pixels)."""
+def _check_png_io(png_writer, png_reader) -> None:
+    """`png_writer=` of the directory drivers: "pil" (frameio.save_frame / save_mask, the default) or "device" (png.py:
+    the files are written by the GPU - any PNG reader decodes them to the same pixels, the bytes are not PIL's).
+    `png_reader=`: "pil" (frameio.load_frame, the default) or "device" (png.py: the files are decoded by the GPU into a
+    resident clip - the same pixels)."""
+    if png_writer not in PNG_WRITERS:
+        raise ValueError(f"png_writer must be one of {PNG_WRITERS}, got {png_writer!r}")
     if png_reader not in PNG_READERS:
         raise ValueError(f"png_reader must be one of {PNG_READERS}, got {png_reader!r}")
-    return png_reader
 
 
 def _device_str(dev: torch.device) -> str:
     return f"cuda:{dev.index or 0}" if dev.type == "cuda" else str(dev)
 
 
-def _sinsr_shard(frames, maps, block_size, device, first_frame_index, **kw):
-    from .restore import restore_frames_sinsr
-    return restore_frames_sinsr(frames, maps, block_size, device, first_frame_index=first_frame_index, **kw)
+# ----------------------------------------------------------------------------- where a worker's frames come from and go to
+@dataclass(frozen=True)
+class PngDirSource:
+    """Frames `names` of the directory `in_dir`: a host list (`reader` "pil") or a resident clip ("device")."""
+    in_dir: str
+    names: Sequence[str]
+    reader: str = "pil"
+
+    @property
+    def total(self) -> int:
+        return len(self.names)
+
+    def load(self, lo: int, hi: int, device):
+        paths = [os.path.join(self.in_dir, n) for n in self.names[lo:hi]]
+        if self.reader == "device":
+            from .png import load_frames_device
+            return load_frames_device(paths, device)
+        return [load_frame(p) for p in paths]
 
 
-def _blur_shard(frames, maps, block_size, device, first_frame_index, **kw):
-    from .restore import restore_frames_blur
-    return restore_frames_blur(frames, maps, block_size, device, **kw)
+@dataclass(frozen=True)
+class PngDirSink:
+    """Frames written to `out_dir` under `names`: host frames through the save_frame loop (`writer` "pil"; a resident
+    clip comes down first), or a resident clip through png.save_frames_device ("device": only finished files come down;
+    host frames, what a replaced `_shard_fn` returns, go up once through png.save_frames)."""
+    out_dir: str
+    names: Sequence[str]
+    writer: str = "pil"
 
-
-def _dct_shard(frames, maps, block_size, device, first_frame_index, **kw):
-    from .restore import restore_frames_dct
-    return restore_frames_dct(frames, maps, block_size, device, **kw)
-
-
-def _stretch_shard(frames, maps, block_size, device, first_frame_index, fullres_masks_dir=None, png_writer="pil", **kw):
-    """Stretch a run of decoded shrunk frames in one launch pair; the inpainter's full-resolution masks come out of
-    the same gather and are written here under the global frame numbers."""
-    from .recompose import frames_to_device, frames_to_host
-    from .shrink import stretch_device
-    with torch.cuda.device(device):
-        fd = frames_to_device(frames, device)
-        md = torch.from_numpy(np.ascontiguousarray(np.asarray(maps) != 0).view(np.uint8)).to(device)
-        out, full = stretch_device(fd, md, block_size, "flat", fullres_mask=True)
-        if fullres_masks_dir is not None:
-            names = [f"{first_frame_index + i + 1:05d}.png" for i in range(len(frames))]
-            if png_writer == "device":
-                from .png import save_frames_device
-                save_frames_device(full.contiguous(), [os.path.join(fullres_masks_dir, name) for name in names])
+    def save(self, frames, start: int, device) -> None:
+        paths = [os.path.join(self.out_dir, n) for n in self.names[start:start + len(frames)]]
+        if self.writer == "device":
+            from .png import save_frames, save_frames_device
+            if isinstance(frames, torch.Tensor):
+                save_frames_device(frames.contiguous(), paths)
             else:
-                full_h = full.cpu().numpy()
-                for i, name in enumerate(names):
-                    save_mask(full_h[i], os.path.join(fullres_masks_dir, name))
-        # the device writer takes the resident clip from the worker: the stretched frames do not come down
-        return out if png_writer == "device" else frames_to_host(out)
+                save_frames(frames, paths, device)
+            return
+        for f, p in zip(recompose.frames_to_host(frames) if isinstance(frames, torch.Tensor) else frames, paths):
+            save_frame(f, p)
 
 
-def _restore_shard(frames, maps, block_size, device, first_frame_index, stretched_dir=None, fullres_masks_dir=None,
-                   png_writer="pil", **kw):
-    """Stretch a run of decoded shrunk frames and inpaint their holes without leaving the device: the hole mask goes
-    from the gather to the inpainter as a resident tensor.  The stretched frames and the masks come down only where a
-    directory asks for them, under the global frame numbers."""
-    from .inpaint import inpaint_device
-    from .recompose import frames_to_device, frames_to_host
-    from .shrink import stretch_device
-    with torch.cuda.device(device):
-        fd = frames_to_device(frames, device)
-        md = torch.from_numpy(np.ascontiguousarray(np.asarray(maps) != 0).view(np.uint8)).to(device)
-        out, full = stretch_device(fd, md, block_size, "flat", fullres_mask=True)
-        names = [f"{first_frame_index + i + 1:05d}.png" for i in range(len(frames))]
-        if png_writer == "device":
-            # the resident clip and its masks go to the PNG writer as they are: only finished files come down
-            from .png import save_frames_device
-            if stretched_dir is not None:
-                save_frames_device(out.contiguous(), [os.path.join(stretched_dir, name) for name in names])
-            if fullres_masks_dir is not None:
-                save_frames_device(full.contiguous(), [os.path.join(fullres_masks_dir, name) for name in names])
-        else:
-            if stretched_dir is not None:
-                for name, f in zip(names, frames_to_host(out)):
-                    save_frame(f, os.path.join(stretched_dir, name))
-            if fullres_masks_dir is not None:
-                full_h = full.cpu().numpy()
-                for i, name in enumerate(names):
-                    save_mask(full_h[i], os.path.join(fullres_masks_dir, name))
-        done = inpaint_device(out, full, out=out)
-        return done if png_writer == "device" else frames_to_host(done)
+_FRAME_MARKER = b"FRAME\n"
 
 
-def _shard_worker(shard_fn: ShardFn, in_dir: str, out_dir: str, names: Sequence[str], start: int, end: int,
-                  maps: np.ndarray, block_size: int, device_str: str, halo: int, kw: dict, png_writer: str = "pil",
-                  png_reader: str = "pil") -> None:
-    """Restore frames [start, end) of the sorted file list `names` on one device and write them to
-    `out_dir` under the same names.  `halo` extra frames on each side are read (never written) for
-    restorers with a temporal window; their maps are taken as given.  `png_writer="device"` writes the frame range
-    through png.save_frames_device where the shard function returned its resident clip (the v1 shards), else through
-    png.save_frames (one more upload, no host pass over the pixels), in place of the save_frame loop;
-    `png_reader="device"` decodes the range with png.load_frames_device in place of the load_frame loop - the v1 shards
-    take the resident clip, every other shard function its frames_to_host."""
-    device = torch.device(device_str)
+@dataclass(frozen=True)
+class ClipFileSource:
+    """The `total` frames of the clip file `path` ("y4m" | "yuv", `width` x `height`): the pixels go up as I420, 1.5
+    bytes per pixel, and are a resident BGR clip from the conversion on."""
+    path: str
+    format: str
+    width: int
+    height: int
+    total: int
+
+    def load(self, lo: int, hi: int, device) -> torch.Tensor:
+        from .handoff import load_y4m_device, load_yuv420p_device
+        if self.format == "y4m":
+            return load_y4m_device(self.path, device, "bgr", start=lo, count=hi - lo)
+        return load_yuv420p_device(self.path, self.width, self.height, device, "bgr", start=lo, count=hi - lo)
+
+
+@dataclass(frozen=True)
+class ClipFileSink:
+    """The clip file `path` ("y4m" | "yuv", `head` header bytes, `width` x `height` frames), which exists at full
+    length: a resident BGR clip is converted back, comes down once as I420 and is written at its frames' own offsets."""
+    path: str
+    format: str
+    head: int
+    width: int
+    height: int
+
+    def save(self, clip: torch.Tensor, start: int, device) -> None:
+        from .handoff import rgb_to_i420_device
+        if tuple(clip.shape[1:]) != (self.height, self.width, 3):
+            raise RuntimeError(f"restorer returned {tuple(clip.shape[1:])} frames for the {self.width}x{self.height} clip {self.path}")
+        planes = rgb_to_i420_device(clip.contiguous(), "bgr")
+        host = torch.empty(planes.shape, dtype=torch.uint8).pin_memory()
+        host.copy_(planes, non_blocking=True)
+        torch.cuda.current_stream(device).synchronize()
+        rows = host.numpy()
+        frame_bytes = self.width * self.height * 3 // 2
+        with open(self.path, "r+b") as f:
+            if self.format == "yuv":
+                f.seek(start * frame_bytes)
+                f.write(memoryview(rows).cast("B"))
+            else:
+                f.seek(self.head + start * (len(_FRAME_MARKER) + frame_bytes))
+                for i in range(len(rows)):
+                    f.write(_FRAME_MARKER)
+                    f.write(memoryview(rows[i]).cast("B"))
+
+
+# ----------------------------------------------------------------------------- jobs and workers
+@dataclass(frozen=True, eq=False)
+class ShardJob:
+    """One worker's share of a driver call: frames [start, end) of `source` through `shard_fn` on `device` into `sink`.
+    `resident`: the shard function takes and returns a resident [n,H,W,3] u8 clip (every built-in one, and a replaced
+    `_shard_fn` of the clip driver), else a list of host frames (a replaced `_shard_fn` of a directory driver)."""
+    shard_fn: Callable
+    source: Union[PngDirSource, ClipFileSource]
+    sink: Union[PngDirSink, ClipFileSink]
+    resident: bool
+    start: int
+    end: int
+    halo: int
+    maps: np.ndarray
+    block_size: int
+    device: str
+    kw: dict
+
+
+def _shard_worker(job: ShardJob) -> None:
+    """Restore frames [start, end) of the job's source on one device and hand them to its sink.  `halo` extra frames on
+    each side are read (never written) for restorers with a temporal window; their maps are taken as given.  The frames
+    reach the shard function in the form the job declares: whatever the source loaded is uploaded or downloaded once
+    where it is in the other form, and passed through where it is not."""
+    device = torch.device(job.device)
     if device.type == "cuda":
         torch.cuda.set_device(device)
-    lo, hi = max(0, start - halo), min(len(names), end + halo)
-    if png_reader == "device":
-        from .png import load_frames_device
-        from .recompose import frames_to_host
-        frames = load_frames_device([os.path.join(in_dir, names[i]) for i in range(lo, hi)], device)
-        if shard_fn not in (_stretch_shard, _restore_shard):
-            frames = frames_to_host(frames)
-    else:
-        frames = [load_frame(os.path.join(in_dir, names[i])) for i in range(lo, hi)]
-    restored = shard_fn(frames, np.asarray(maps[lo:hi]), block_size, device, lo, **kw)
+    start, end = job.start, job.end
+    lo, hi = max(0, start - job.halo), min(job.source.total, end + job.halo)
+    frames = job.source.load(lo, hi, device)
+    if job.resident and not isinstance(frames, torch.Tensor):
+        frames = recompose.frames_to_device(frames, device)
+    elif not job.resident and isinstance(frames, torch.Tensor):
+        frames = recompose.frames_to_host(frames)
+    restored = job.shard_fn(frames, np.asarray(job.maps[lo:hi]), job.block_size, device, lo, **job.kw)
     if len(restored) != hi - lo:
-        raise RuntimeError(f"restorer returned {len(restored)} frames for {hi - lo} inputs on {device_str}")
-    if png_writer == "device":
-        from .png import save_frames, save_frames_device
-        paths = [os.path.join(out_dir, names[i]) for i in range(start, end)]
-        if isinstance(restored, torch.Tensor):     # a v1 shard's resident clip: only finished files come down
-            save_frames_device(restored[start - lo:end - lo].contiguous(), paths)
-        else:
-            save_frames([restored[i - lo] for i in range(start, end)], paths, device)
-        return
-    for i in range(start, end):
-        save_frame(restored[i - lo], os.path.join(out_dir, names[i]))
+        raise RuntimeError(f"restorer returned {len(restored)} frames for {hi - lo} inputs on {job.device}")
+    # a resident result has the clip's layout; its frame size is the sink's to judge (the v1 shards stretch theirs)
+    if job.resident and (not isinstance(restored, torch.Tensor) or restored.dtype != torch.uint8
+                         or restored.dim() != 4 or restored.shape[3] != frames.shape[3]):
+        raise RuntimeError(f"restorer did not return the resident uint8 clip {tuple(frames.shape)} it was given on {job.device}")
+    job.sink.save(restored[start - lo:end - lo], start, device)
 
 
-def _shard_process(err_path: str, job: tuple, worker: Optional[Callable[..., None]] = None) -> None:
-    """Entry point of a spawned per-GPU worker (`worker`, by default `_shard_worker`; every worker's job holds its frame
-    range at [4], [5] and its device at [8]): a failure is written to stderr and to `err_path` as
+def _shard_process(err_path: str, job: ShardJob) -> None:
+    """Entry point of a spawned per-GPU worker: a failure is written to stderr and to `err_path` as
     `device / [start, end) / traceback`, so the parent can say WHICH shard failed and why."""
     import sys
     import traceback
     try:
-        (worker or _shard_worker)(*job)
+        _shard_worker(job)
     except BaseException:
-        start, end, device_str = job[4], job[5], job[8]
-        msg = f"shard on {device_str}, frames [{start}, {end}):\n{traceback.format_exc()}"
+        msg = f"shard on {job.device}, frames [{job.start}, {job.end}):\n{traceback.format_exc()}"
         sys.stderr.write(msg)
         try:
             with open(err_path, "w") as f:
@@ -203,29 +234,17 @@ def _shard_process(err_path: str, job: tuple, worker: Optional[Callable[..., Non
             raise SystemExit(1)
 
 
-def _run_shards(shard_fn: ShardFn, in_dir: str, out_dir: str, names: List[str], chunks: List[ChunkSpec],
-                maps: np.ndarray, block_size: int, halo: int, kw: dict, png_writer: str = "pil", png_reader: str = "pil") -> None:
-    for what, value in (("png_writer", png_writer), ("png_reader", png_reader)):
-        if value == "device":
-            for c in chunks:
-                if c.device.type != "cuda":
-                    raise RuntimeError(f"{what}='device' needs a GPU (got device '{c.device}'); there is no CPU path")
-    jobs = [(shard_fn, in_dir, out_dir, names, c.start, c.end, maps, block_size, _device_str(c.device), halo, kw, png_writer, png_reader)
-            for c in chunks]
-    _run_jobs(_shard_worker, jobs)
-
-
-def _run_jobs(worker: Callable[..., None], jobs: List[tuple]) -> None:
-    """One job: `worker(*job)` in-process.  Several: one spawned process per job, failures gathered and reported by
-    device and frame range (`_shard_process`)."""
+def _run_jobs(jobs: List[ShardJob]) -> None:
+    """One job: in-process.  Several: one spawned process per job, failures gathered and reported by device and frame
+    range (`_shard_process`)."""
     if len(jobs) == 1:
-        worker(*jobs[0])
+        _shard_worker(jobs[0])
         return
     import tempfile
     ctx = multiprocessing.get_context("spawn")   # never fork a process that may hold a GPU context
     with tempfile.TemporaryDirectory(prefix="elvis_shards_") as errdir:
         errs = [os.path.join(errdir, f"shard{i}.err") for i in range(len(jobs))]
-        procs = [ctx.Process(target=_shard_process, args=(e, job, worker)) for e, job in zip(errs, jobs)]
+        procs = [ctx.Process(target=_shard_process, args=(e, job)) for e, job in zip(errs, jobs)]
         for p in procs:
             p.start()
         failed = []
@@ -233,10 +252,85 @@ def _run_jobs(worker: Callable[..., None], jobs: List[tuple]) -> None:
             p.join()
             if p.exitcode not in (0, None):
                 detail = open(e).read() if os.path.exists(e) else \
-                    f"shard on {job[8]}, frames [{job[4]}, {job[5]}): exit code {p.exitcode} (no traceback: killed?)"
+                    f"shard on {job.device}, frames [{job.start}, {job.end}): exit code {p.exitcode} (no traceback: killed?)"
                 failed.append(detail)
     if failed:
         raise RuntimeError("restoration worker(s) failed:\n" + "\n".join(failed))
+
+
+def _png_jobs(builtin: Callable, _shard_fn: Optional[ShardFn], in_dir: str, out_dir: str, names: List[str],
+              chunks: List[ChunkSpec], maps: np.ndarray, block_size: int, halo: int, kw: dict, png_writer: str,
+              png_reader: str) -> List[ShardJob]:
+    """The jobs of a directory driver, one per chunk: the resident `builtin` shard function, or the caller's `_shard_fn`
+    on host frames.  `png_writer` / `png_reader` "device" need a GPU on every chunk."""
+    for what, value in (("png_writer", png_writer), ("png_reader", png_reader)):
+        if value == "device":
+            for c in chunks:
+                if c.device.type != "cuda":
+                    raise RuntimeError(f"{what}='device' needs a GPU (got device '{c.device}'); there is no CPU path")
+    source, sink = PngDirSource(in_dir, names, png_reader), PngDirSink(out_dir, names, png_writer)
+    return [ShardJob(_shard_fn or builtin, source, sink, _shard_fn is None, c.start, c.end, halo, maps, block_size,
+                     _device_str(c.device), kw) for c in chunks]
+
+
+# ----------------------------------------------------------------------------- the shard functions
+def _sinsr_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
+    from .restore import restore_frames_sinsr_device
+    return restore_frames_sinsr_device(clip, maps, block_size, first_frame_index=first_frame_index, **kw)
+
+
+def _blur_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
+    from .restore import restore_frames_blur_device
+    return restore_frames_blur_device(clip, maps, block_size, **kw)
+
+
+def _dct_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
+    from .restore import restore_frames_dct_device
+    return restore_frames_dct_device(clip, maps, block_size, **kw)
+
+
+def _realesrgan_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
+    from .restore import restore_frames_realesrgan_device
+    return restore_frames_realesrgan_device(clip, maps, block_size, **kw)
+
+
+_CLIP_SHARDS = {"sinsr": _sinsr_clip_shard, "blur": _blur_clip_shard, "dct": _dct_clip_shard,
+                "realesrgan": _realesrgan_clip_shard}
+
+
+def _write_clip(clip: torch.Tensor, directory: str, names: Sequence[str], png_writer: str) -> None:
+    """A resident clip of frames [n,H,W,3] or of masks [n,H,W] as PNGs `names` of `directory`, with either writer: the
+    device writer takes the clip as it is and only finished files come down."""
+    paths = [os.path.join(directory, name) for name in names]
+    if png_writer == "device":
+        from .png import save_frames_device
+        save_frames_device(clip.contiguous(), paths)
+    elif clip.dim() == 4:
+        for f, p in zip(recompose.frames_to_host(clip), paths):
+            save_frame(f, p)
+    else:
+        for m, p in zip(clip.cpu().numpy(), paths):
+            save_mask(m, p)
+
+
+def _v1_shard(clip, maps, block_size, device, first_frame_index, inpaint=False, stretched_dir=None,
+              fullres_masks_dir=None, png_writer="pil", **kw):
+    """Stretch a run of decoded shrunk frames in one launch pair and, with `inpaint`, fill their holes without leaving
+    the device: the hole mask goes from the gather to the inpainter as a resident tensor.  The stretched frames and the
+    full-resolution masks are written only where a directory asks for them, under the global frame numbers."""
+    from .shrink import stretch_device
+    with torch.cuda.device(device):
+        md = torch.from_numpy(np.ascontiguousarray(np.asarray(maps) != 0).view(np.uint8)).to(device)
+        out, full = stretch_device(clip, md, block_size, "flat", fullres_mask=True)
+        names = [f"{first_frame_index + i + 1:05d}.png" for i in range(len(clip))]
+        if stretched_dir is not None:
+            _write_clip(out, stretched_dir, names, png_writer)
+        if fullres_masks_dir is not None:
+            _write_clip(full, fullres_masks_dir, names, png_writer)
+        if inpaint:
+            from .inpaint import inpaint_device
+            return inpaint_device(out, full, out=out)
+        return out
 
 
 def _frames_and_maps(frames_dir: str, maps, what: str):
@@ -247,6 +341,18 @@ def _frames_and_maps(frames_dir: str, maps, what: str):
     if maps.ndim != 3 or maps.shape[0] != len(paths):
         raise ValueError(f"{what} length ({maps.shape[0] if maps.ndim else 0}) does not match frame count ({len(paths)}).")
     return [p.name for p in paths], maps
+
+
+def _restore_downsampled(builtin: Callable, kw: dict, input_frames_dir: str, output_frames_dir: str, downscale_maps,
+                         block_size: int, devices, png_writer: str, png_reader: str, _shard_fn: Optional[ShardFn]) -> None:
+    """What the two Downsample drivers share once their own arguments are checked: `output_frames_dir` is cleared and
+    every frame of `input_frames_dir` is written to it under the same name."""
+    names, maps = _frames_and_maps(input_frames_dir, downscale_maps, "Downscale maps")
+    clear_directory(output_frames_dir)
+    os.makedirs(output_frames_dir, exist_ok=True)
+    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
+    _run_jobs(_png_jobs(builtin, _shard_fn, input_frames_dir, output_frames_dir, names, chunk_for_devices(len(names), devs),
+                        maps, block_size, 0, kw if _shard_fn is None else {}, png_writer, png_reader))
 
 
 def restore_downsampled_with_sinsr(
@@ -274,21 +380,11 @@ def restore_downsampled_with_sinsr(
     are accepted and ignored, as are `parallel_chunk_length` / `per_device_workers` (the reference ignores
     them too, elvis.py:2698-2699)."""
     _ = (parallel_chunk_length, per_device_workers)
-    _check_png_writer(png_writer)
-    _check_png_reader(png_reader)
-    names, maps = _frames_and_maps(input_frames_dir, downscale_maps, "Downscale maps")
-    clear_directory(output_frames_dir)
-    os.makedirs(output_frames_dir, exist_ok=True)
-    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
+    _check_png_io(png_writer, png_reader)
     kw = dict(fp32=fp32, seed=seed, schedule=schedule)
     kw.update({k: v for k, v in model_kwargs.items() if k in ("cfg",)})
-    _run_shards(_shard_fn or _sinsr_shard, input_frames_dir, output_frames_dir, names,
-                chunk_for_devices(len(names), devs), maps, block_size, 0, kw if _shard_fn is None else {}, png_writer, png_reader)
-
-
-def _realesrgan_shard(frames, maps, block_size, device, first_frame_index, **kw):
-    from .restore import restore_frames_realesrgan
-    return restore_frames_realesrgan(frames, maps, block_size, device, **kw)
+    _restore_downsampled(_sinsr_clip_shard, kw, input_frames_dir, output_frames_dir, downscale_maps, block_size, devices,
+                         png_writer, png_reader, _shard_fn)
 
 
 def restore_downsampled_with_realesrgan(
@@ -318,31 +414,25 @@ def restore_downsampled_with_realesrgan(
     checkpoint file (e.g. "RealESRGAN_x4plus.pth"); without it the weights are seeded and synthetic.
     `parallel_chunk_length` / `per_device_workers` are accepted and ignored, as in the reference (elvis.py:2698-2699)."""
     _ = (parallel_chunk_length, per_device_workers)
-    _check_png_writer(png_writer)
-    _check_png_reader(png_reader)
+    _check_png_io(png_writer, png_reader)
     if _shard_fn is None:
         from .restore import _check_realesrgan_args
         from .weights import realesrgan_config
         _check_realesrgan_args(denoise_strength, pre_pad, fp32)
         realesrgan_config(model_name)
-    names, maps = _frames_and_maps(input_frames_dir, downscale_maps, "Downscale maps")
-    clear_directory(output_frames_dir)
-    os.makedirs(output_frames_dir, exist_ok=True)
-    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
     kw = dict(model_name=model_name, denoise_strength=denoise_strength, tile=tile, tile_pad=tile_pad, pre_pad=pre_pad,
               fp32=fp32, model_path=model_path, schedule=schedule)
-    _run_shards(_shard_fn or _realesrgan_shard, input_frames_dir, output_frames_dir, names,
-                chunk_for_devices(len(names), devs), maps, block_size, 0, kw if _shard_fn is None else {}, png_writer, png_reader)
+    _restore_downsampled(_realesrgan_clip_shard, kw, input_frames_dir, output_frames_dir, downscale_maps, block_size, devices,
+                         png_writer, png_reader, _shard_fn)
 
 
-def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int, devices, halo: int, kw: dict,
-                      what: str, allow_cpu: bool, png_writer: str = "pil", png_reader: str = "pil") -> None:
-    _check_png_writer(png_writer)
-    _check_png_reader(png_reader)
+def _restore_in_place(builtin: Callable, _shard_fn: Optional[ShardFn], frames_dir: str, maps, block_size: int, devices,
+                      halo: int, kw: dict, what: str, png_writer: str, png_reader: str) -> None:
+    _check_png_io(png_writer, png_reader)
     names, maps = _frames_and_maps(frames_dir, maps, what)
     if maps.size == 0 or int(np.max(maps)) <= 0:
         return   # nothing degraded: the frames stay as decoded (elvis.py:3042-3044)
-    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=allow_cpu)
+    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
     gpus = [d for d in devs if d.type == "cuda"]
     workers = gpus or devs[:1]            # the reference uses every GPU, else the first device (elvis.py:3030-3031)
     chunks = chunk_for_devices(len(names), workers)
@@ -352,7 +442,8 @@ def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int,
         scratch = os.path.join(frames_dir, ".elvis_restore_tmp")
         os.makedirs(scratch, exist_ok=True)
         try:
-            _run_shards(shard_fn, frames_dir, scratch, names, chunks, maps, block_size, halo, kw, png_writer, png_reader)
+            _run_jobs(_png_jobs(builtin, _shard_fn, frames_dir, scratch, names, chunks, maps, block_size, halo, kw,
+                                png_writer, png_reader))
             for n in names:
                 os.replace(os.path.join(scratch, n), os.path.join(frames_dir, n))
         finally:
@@ -360,7 +451,8 @@ def _restore_in_place(shard_fn: ShardFn, frames_dir: str, maps, block_size: int,
                 os.unlink(os.path.join(scratch, n))
             os.rmdir(scratch)
     else:
-        _run_shards(shard_fn, frames_dir, frames_dir, names, chunks, maps, block_size, halo, kw, png_writer, png_reader)
+        _run_jobs(_png_jobs(builtin, _shard_fn, frames_dir, frames_dir, names, chunks, maps, block_size, halo, kw,
+                            png_writer, png_reader))
 
 
 def restore_blur_adaptive(
@@ -387,13 +479,12 @@ def restore_blur_adaptive(
     (cfg, creative_start, preview_start) and the seed have no meaning for a deterministic forward pass
     and are ignored; `parallel_chunk_length` is ignored like in the reference (elvis.py:3015)."""
     _ = (cfg, creative_start, preview_start, seed, parallel_chunk_length)
-    _check_png_writer(png_writer)
-    _check_png_reader(png_reader)
+    _check_png_io(png_writer, png_reader)
     if batch_size < 1:
         raise ValueError("`batch_size` must be at least 1.")
     kw = {} if _shard_fn is not None else dict(batch_size=batch_size, fp32=fp32)
-    _restore_in_place(_shard_fn or _blur_shard, input_frames_dir, blur_maps, block_size, devices, 0, kw,
-                      "blur_maps", _shard_fn is not None, png_writer, png_reader)
+    _restore_in_place(_blur_clip_shard, _shard_fn, input_frames_dir, blur_maps, block_size, devices, 0, kw, "blur_maps",
+                      png_writer, png_reader)
 
 
 def restore_dct_adaptive(
@@ -413,8 +504,8 @@ def restore_dct_adaptive(
     Each worker also reads `temporal_radius` decoded frames on either side of its range (read-only
     overlap, the expand-then-trim pattern of elvis.py:1550-1566, 1650-1657)."""
     kw = {} if _shard_fn is not None else dict(fp32=fp32)
-    _restore_in_place(_shard_fn or _dct_shard, input_frames_dir, strength_maps, block_size, devices,
-                      max(0, int(temporal_radius)), kw, "strength_maps", _shard_fn is not None, png_writer, png_reader)
+    _restore_in_place(_dct_clip_shard, _shard_fn, input_frames_dir, strength_maps, block_size, devices,
+                      max(0, int(temporal_radius)), kw, "strength_maps", png_writer, png_reader)
 
 
 def _v1_clip(frames_dir: str, masks_npz: str, block_size: int):
@@ -443,6 +534,27 @@ def _v1_kw(png_writer: str, **dirs) -> dict:
     return dict(dirs, png_writer=png_writer) if png_writer != "pil" else dirs
 
 
+def _run_v1(inpaint: bool, frames_dir: str, masks_npz: str, block_size: int, out_dir: str, block_masks_dir: Optional[str],
+            devices, png_writer: str, png_reader: str, _shard_fn: Optional[ShardFn], **dirs) -> np.ndarray:
+    """What the two v1 drivers share: the checks, the directories (`dirs`: the ones the shard step writes, by keyword),
+    the block-resolution masks, and the stretch (and `inpaint`) of every frame of `frames_dir` into `out_dir`."""
+    _check_png_io(png_writer, png_reader)
+    masks, names = _v1_clip(frames_dir, masks_npz, block_size)
+    for d in (out_dir, *dirs.values(), block_masks_dir):
+        if d is not None:
+            os.makedirs(d, exist_ok=True)
+    if block_masks_dir is not None:
+        for i, n in enumerate(names):
+            save_mask((masks[i] * 255).astype(np.uint8), os.path.join(block_masks_dir, n))
+    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
+    gpus = [d for d in devs if d.type == "cuda"]
+    workers = gpus or (devs if _shard_fn is not None else devs[:1])
+    kw = _v1_kw(png_writer, **dirs)
+    _run_jobs(_png_jobs(_v1_shard, _shard_fn, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
+                        block_size, 0, kw if _shard_fn is not None else dict(kw, inpaint=inpaint), png_writer, png_reader))
+    return masks
+
+
 def stretch_shrunk_frames(
     frames_dir: str,
     masks_npz: str,
@@ -464,21 +576,8 @@ def stretch_shrunk_frames(
 
     Every frame must hold exactly as many blocks as its mask keeps (`stretch_frame`'s rule): ValueError otherwise,
     before anything is written."""
-    _check_png_writer(png_writer)
-    _check_png_reader(png_reader)
-    masks, names = _v1_clip(frames_dir, masks_npz, block_size)
-    for d in (out_dir, fullres_masks_dir, block_masks_dir):
-        if d is not None:
-            os.makedirs(d, exist_ok=True)
-    if block_masks_dir is not None:
-        for i, n in enumerate(names):
-            save_mask((masks[i] * 255).astype(np.uint8), os.path.join(block_masks_dir, n))
-    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
-    gpus = [d for d in devs if d.type == "cuda"]
-    workers = gpus or (devs if _shard_fn is not None else devs[:1])
-    _run_shards(_shard_fn or _stretch_shard, frames_dir, out_dir or frames_dir, names, chunk_for_devices(len(names), workers),
-                masks, block_size, 0, _v1_kw(png_writer, fullres_masks_dir=fullres_masks_dir), png_writer, png_reader)
-    return masks
+    return _run_v1(False, frames_dir, masks_npz, block_size, out_dir or frames_dir, block_masks_dir, devices, png_writer,
+                   png_reader, _shard_fn, fullres_masks_dir=fullres_masks_dir)
 
 
 def restore_shrunk_frames(
@@ -506,52 +605,12 @@ def restore_shrunk_frames(
     one worker per GPU.  Returns the unpacked masks."""
     if out_dir is None:
         raise ValueError("restore_shrunk_frames: out_dir is required")
-    _check_png_writer(png_writer)
-    _check_png_reader(png_reader)
-    masks, names = _v1_clip(frames_dir, masks_npz, block_size)
-    for d in (out_dir, stretched_dir, fullres_masks_dir, block_masks_dir):
-        if d is not None:
-            os.makedirs(d, exist_ok=True)
-    if block_masks_dir is not None:
-        for i, n in enumerate(names):
-            save_mask((masks[i] * 255).astype(np.uint8), os.path.join(block_masks_dir, n))
-    devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
-    gpus = [d for d in devs if d.type == "cuda"]
-    workers = gpus or (devs if _shard_fn is not None else devs[:1])
-    _run_shards(_shard_fn or _restore_shard, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
-                block_size, 0, _v1_kw(png_writer, stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir), png_writer, png_reader)
-    return masks
+    return _run_v1(True, frames_dir, masks_npz, block_size, out_dir, block_masks_dir, devices, png_writer, png_reader,
+                   _shard_fn, stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir)
 
 
 # ----------------------------------------------------------------------------- clip files: decoder output in, encoder input out
 YUV_CLIP_KINDS = {"sinsr": "Downscale maps", "blur": "blur_maps", "dct": "strength_maps", "realesrgan": "Downscale maps"}
-# (clip, maps, block_size, device, first_frame_index, **kw) -> clip ; resident [n,H,W,3] u8 BGR in and out
-ClipShardFn = Callable[..., torch.Tensor]
-
-
-def _sinsr_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
-    from .restore import restore_frames_sinsr_device
-    return restore_frames_sinsr_device(clip, maps, block_size, first_frame_index=first_frame_index, **kw)
-
-
-def _blur_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
-    from .restore import restore_frames_blur_device
-    return restore_frames_blur_device(clip, maps, block_size, **kw)
-
-
-def _dct_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
-    from .restore import restore_frames_dct_device
-    return restore_frames_dct_device(clip, maps, block_size, **kw)
-
-
-def _realesrgan_clip_shard(clip, maps, block_size, device, first_frame_index, **kw):
-    from .restore import restore_frames_realesrgan_device
-    return restore_frames_realesrgan_device(clip, maps, block_size, **kw)
-
-
-_CLIP_SHARDS = {"sinsr": _sinsr_clip_shard, "blur": _blur_clip_shard, "dct": _dct_clip_shard,
-                "realesrgan": _realesrgan_clip_shard}
-_FRAME_MARKER = b"FRAME\n"
 
 
 def _clip_format(path: str, what: str) -> str:
@@ -559,42 +618,6 @@ def _clip_format(path: str, what: str) -> str:
     if ext not in (".y4m", ".yuv"):
         raise ValueError(f"restore_yuv_clip: {what} must be a .y4m or a .yuv file, got {os.fspath(path)!r}")
     return ext[1:]
-
-
-def _yuv_clip_worker(shard_fn: ClipShardFn, src: tuple, dst: tuple, total: int, start: int, end: int, maps: np.ndarray,
-                     block_size: int, device_str: str, halo: int, kw: dict) -> None:
-    """Restore frames [start, end) of the clip file `src` = (path, "y4m" | "yuv", width, height) on one device and write
-    their I420 planes into `dst` = (path, "y4m" | "yuv", header length) at the frames' own offsets; the file exists at
-    full length.  `halo` extra frames on each side are read from the input (never written) for restorers with a
-    temporal window.  The pixels go up as I420, stay resident as RGB from the conversion through the restorer to the
-    conversion back, and come down once as I420: 1.5 bytes per pixel each way."""
-    from .handoff import load_y4m_device, load_yuv420p_device, rgb_to_i420_device
-    device = torch.device(device_str)
-    torch.cuda.set_device(device)
-    (in_path, in_format, width, height), (out_path, out_format, head) = src, dst
-    lo, hi = max(0, start - halo), min(total, end + halo)
-    if in_format == "y4m":
-        clip = load_y4m_device(in_path, device, "bgr", start=lo, count=hi - lo)
-    else:
-        clip = load_yuv420p_device(in_path, width, height, device, "bgr", start=lo, count=hi - lo)
-    restored = shard_fn(clip, np.asarray(maps[lo:hi]), block_size, device, lo, **kw)
-    if not isinstance(restored, torch.Tensor) or tuple(restored.shape) != tuple(clip.shape) or restored.dtype != torch.uint8:
-        raise RuntimeError(f"restorer did not return the resident uint8 clip {tuple(clip.shape)} it was given on {device_str}")
-    planes = rgb_to_i420_device(restored[start - lo:end - lo].contiguous(), "bgr")
-    host = torch.empty(planes.shape, dtype=torch.uint8).pin_memory()
-    host.copy_(planes, non_blocking=True)
-    torch.cuda.current_stream(device).synchronize()
-    rows = host.numpy()
-    frame_bytes = width * height * 3 // 2
-    with open(out_path, "r+b") as f:
-        if out_format == "yuv":
-            f.seek(start * frame_bytes)
-            f.write(memoryview(rows).cast("B"))
-        else:
-            f.seek(head + start * (len(_FRAME_MARKER) + frame_bytes))
-            for i in range(end - start):
-                f.write(_FRAME_MARKER)
-                f.write(memoryview(rows[i]).cast("B"))
 
 
 def restore_yuv_clip(
@@ -668,10 +691,10 @@ def restore_yuv_clip(
     with open(output_path, "wb") as f:
         f.write(head)
         f.truncate(len(head) + total * (frame_bytes + (len(_FRAME_MARKER) if out_format == "y4m" else 0)))
-    src, dst = (input_path, in_format, width, height), (output_path, out_format, len(head))
-    jobs = [(_shard_fn or _CLIP_SHARDS[kind], src, dst, total, c.start, c.end, maps, block_size, _device_str(c.device), halo,
-             {} if _shard_fn is not None else kw) for c in chunk_for_devices(total, devs)]
-    _run_jobs(_yuv_clip_worker, jobs)
+    source = ClipFileSource(input_path, in_format, width, height, total)
+    sink = ClipFileSink(output_path, out_format, len(head), width, height)
+    _run_jobs([ShardJob(_shard_fn or _CLIP_SHARDS[kind], source, sink, True, c.start, c.end, halo, maps, block_size,
+                        _device_str(c.device), {} if _shard_fn is not None else kw) for c in chunk_for_devices(total, devs)])
 
 
 def calculate_removability_scores_from_frames(frames, foreground_masks, block_size: int, alpha: float = 0.5,

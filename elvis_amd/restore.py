@@ -30,28 +30,46 @@ _MODEL_LOCK = threading.Lock()
 DEFAULT_SEED = 42  # the reference's default sampler seed (elvis.py:89, utils.py:103)
 
 
-def get_sinsr_model(device, *, cfg: Optional[SinSRConfig] = None, fp32: bool = False, weight_seed: int = 0,
-                    state_dict=None, fuse_gn: bool = True, precision: Optional[str] = None) -> SinSRModel:
-    """Get or create the cached SinSR runtime for `device` (thread-safe, never freed - the
-    reference's cache policy, elvis.py:2611-2637)."""
+def _cached_model(label: str, device, key: tuple, state_dict, make: Callable[[torch.device], object]):
+    """The process-global model cache behind the three getters (thread-safe, never freed - the reference's cache
+    policy, elvis.py:2611-2637): `make(dev)` runs once per (`label`, device, `key`, identity of the caller's
+    `state_dict`).  The entry keeps a strong reference to that dict, so its id cannot be reused by another object.  A
+    RuntimeError of `make` becomes "<label> failed on <dev>: ..."."""
     dev = torch.device(device)
     L.require_gpu(dev)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
-    cfg = cfg or SinSRConfig()
-    # the key holds `cfg` itself (a frozen dataclass) and the identity of the caller's state_dict; the
-    # cache entry keeps a strong reference to that dict, so its id cannot be reused by another object
-    key = (str(dev), cfg, bool(fp32), precision, int(weight_seed), id(state_dict) if state_dict is not None else 0, bool(fuse_gn))
+    key = (label, str(dev), id(state_dict) if state_dict is not None else 0) + key
     with _MODEL_LOCK:
         hit = _MODEL_CACHE.get(key)
         if hit is None:
             try:
-                m = SinSRModel(cfg, state_dict, dev, torch.float32 if fp32 else torch.float16, weight_seed, fuse_gn,
-                               precision=precision)
+                model = make(dev)
             except RuntimeError as exc:
-                raise RuntimeError(f"SinSR failed on {dev}: {exc}") from exc
-            hit = _MODEL_CACHE[key] = (m, state_dict)
+                raise RuntimeError(f"{label} failed on {dev}: {exc}") from exc
+            hit = _MODEL_CACHE[key] = (model, state_dict)
     return hit[0]
+
+
+def _host_to_host(frames, model_device: Callable[[], torch.device], device_form, maps, block_size: int, **kw) -> List[np.ndarray]:
+    """The host-to-host form of a `*_device` restorer: no frames give `[]`; else `model_device()` resolves the model
+    (its errors come first) and names its device, the frames go up once, `device_form` runs, the result comes down once."""
+    if not frames:
+        return []
+    dev = model_device()
+    with torch.cuda.device(dev):
+        return frames_to_host(device_form(frames_to_device(frames, dev), maps, block_size, **kw))
+
+
+def get_sinsr_model(device, *, cfg: Optional[SinSRConfig] = None, fp32: bool = False, weight_seed: int = 0,
+                    state_dict=None, fuse_gn: bool = True, precision: Optional[str] = None) -> SinSRModel:
+    """Get or create the cached SinSR runtime for `device` (thread-safe, never freed - the
+    reference's cache policy, elvis.py:2611-2637)."""
+    cfg = cfg or SinSRConfig()
+    # the key holds `cfg` itself (a frozen dataclass)
+    return _cached_model("SinSR", device, (cfg, bool(fp32), precision, int(weight_seed), bool(fuse_gn)), state_dict,
+                         lambda dev: SinSRModel(cfg, state_dict, dev, torch.float32 if fp32 else torch.float16, weight_seed,
+                                                fuse_gn, precision=precision))
 
 
 def sr4x_device(model: SinSRModel, lr_d: torch.Tensor, frame_indices: Sequence[int], seed: int = DEFAULT_SEED,
@@ -281,14 +299,9 @@ def restore_frames_sinsr(frames: List[np.ndarray], downscale_maps: np.ndarray, b
     Unknown model kwargs of the reference call (model_name, tile, ...) are accepted and ignored
     (the `**kwargs` convention of the P3 surface, utils.py:1428).
     """
-    if not frames:
-        return []
-    dev = torch.device(device)
-    model = get_sinsr_model(dev, cfg=cfg, fp32=fp32, precision=precision)
-    with torch.cuda.device(model.device):
-        return frames_to_host(restore_frames_sinsr_device(
-            frames_to_device(frames, model.device), downscale_maps, block_size, seed=seed, first_frame_index=first_frame_index,
-            fp32=fp32, schedule=schedule, staged_2x=staged_2x, cfg=cfg, precision=precision))
+    return _host_to_host(frames, lambda: get_sinsr_model(device, cfg=cfg, fp32=fp32, precision=precision).device,
+                         restore_frames_sinsr_device, downscale_maps, block_size, seed=seed, first_frame_index=first_frame_index,
+                         fp32=fp32, schedule=schedule, staged_2x=staged_2x, cfg=cfg, precision=precision)
 
 
 def restore_with_sinsr_naive(frames: List[np.ndarray], device="cuda", seed: int = DEFAULT_SEED,
@@ -313,9 +326,6 @@ def restore_with_sinsr_naive(frames: List[np.ndarray], device="cuda", seed: int 
 
 
 # ----------------------------------------------------------------------------- Real-ESRGAN (RRDBNet) in the Downsample slot
-_REALESRGAN_CACHE: Dict[tuple, tuple] = {}
-
-
 def _check_realesrgan_args(denoise_strength, pre_pad, fp32) -> None:
     """The departures from the reference call: each is refused, none is silently ignored."""
     if fp32:
@@ -341,22 +351,10 @@ def get_realesrgan_upsampler(device, *, model_name: str = "RealESRGAN_x4plus", d
     _check_realesrgan_args(denoise_strength, pre_pad, fp32)
     _ = (tile, tile_pad)
     cfg = realesrgan_config(model_name)
-    dev = torch.device(device)
-    L.require_gpu(dev)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
     source = state_dict if state_dict is not None else model_path
-    # the entry keeps a strong reference to a caller's dict, so its id cannot be reused by another object
-    key = (str(dev), cfg, id(state_dict) if state_dict is not None else (str(model_path) if model_path is not None else None))
-    with _MODEL_LOCK:
-        hit = _REALESRGAN_CACHE.get(key)
-        if hit is None:
-            try:
-                m = RRDBNetModel(cfg, source, dev)
-            except RuntimeError as exc:
-                raise RuntimeError(f"Real-ESRGAN failed on {dev}: {exc}") from exc
-            hit = _REALESRGAN_CACHE[key] = (m, state_dict)
-    return hit[0]
+    # a caller's dict is keyed by its identity, a checkpoint file by its path
+    path = str(model_path) if state_dict is None and model_path is not None else None
+    return _cached_model("Real-ESRGAN", device, (cfg, path), state_dict, lambda dev: RRDBNetModel(cfg, source, dev))
 
 
 def _realesrgan_up(model, cur: torch.Tensor, swap_rb: bool = True) -> torch.Tensor:
@@ -445,14 +443,10 @@ def restore_frames_realesrgan(frames: List[np.ndarray], downscale_maps: np.ndarr
     ones; nothing is downloaded.  `tile` / `tile_pad` are accepted and ignored (whole frames fit); `fp32=True`,
     `pre_pad != 0` and `denoise_strength != 1` are a ValueError.  A runtime failure is
     `RuntimeError("Real-ESRGAN failed on <device>: ...")` (elvis.py:2517-2519)."""
-    if not frames:
-        return []
-    model = get_realesrgan_upsampler(device, model_name=model_name, denoise_strength=denoise_strength, tile=tile,
-                                     tile_pad=tile_pad, pre_pad=pre_pad, fp32=fp32, model_path=model_path, state_dict=state_dict)
-    with torch.cuda.device(model.device):
-        return frames_to_host(restore_frames_realesrgan_device(
-            frames_to_device(frames, model.device), downscale_maps, block_size, model_name=model_name, model_path=model_path,
-            state_dict=state_dict, schedule=schedule))
+    kw = dict(model_name=model_name, denoise_strength=denoise_strength, tile=tile, tile_pad=tile_pad, pre_pad=pre_pad,
+              fp32=fp32, model_path=model_path, state_dict=state_dict)
+    return _host_to_host(frames, lambda: get_realesrgan_upsampler(device, **kw).device, restore_frames_realesrgan_device,
+                         downscale_maps, block_size, schedule=schedule, **kw)
 
 
 def restore_with_realesrgan_naive(frames: List[np.ndarray], device="cuda", model_name: str = "RealESRGAN_x4plus",
@@ -477,39 +471,20 @@ def restore_frames_rounds(frames: List[np.ndarray], maps: np.ndarray, block_size
                           max_rounds: Optional[int] = None) -> List[np.ndarray]:
     """Frames-level form of the iterative round loop (elvis.py:2947-2981) for any on-device
     restorer (`restore_dev`: [n,H,W,3] u8 -> same) - the slot the Blur / DCT restorers fill."""
-    if not frames:
-        return []
-    dev = torch.device(device)
-    L.require_gpu(dev)
-    with torch.cuda.device(dev):
-        frames_d = frames_to_device(frames, dev)
-        maps_d = maps_to_device(maps, frames_d.shape[0], dev)
-        return frames_to_host(rounds_recompose_device(frames_d, maps_d, block_size, restore_dev, batch_size, max_rounds))
+    def rounds(frames_d, maps, block_size):
+        maps_d = maps_to_device(maps, frames_d.shape[0], frames_d.device)
+        return rounds_recompose_device(frames_d, maps_d, block_size, restore_dev, batch_size, max_rounds)
+
+    return _host_to_host(frames, lambda: L.require_gpu(device) or torch.device(device), rounds, maps, block_size)
 
 
 # ----------------------------------------------------------------------------- Blur / DCT slots
-_RESTORER_CACHE: Dict[tuple, tuple] = {}
-
-
 def _get_restorer(kind: str, device, fp32: bool, cfg=None, state_dict=None):
     from .restorers import DCNRestorer, SwinDeblur
-    dev = torch.device(device)
-    L.require_gpu(dev)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (kind, str(dev), bool(fp32), cfg, id(state_dict) if state_dict is not None else 0)
-    with _MODEL_LOCK:
-        hit = _RESTORER_CACHE.get(key)
-        m = hit[0] if hit is not None else None
-        if m is None:
-            cls = SwinDeblur if kind == "blur" else DCNRestorer
-            args = (cfg,) if cfg is not None else ()
-            try:
-                m = cls(*args, state_dict=state_dict, device=dev, dtype=torch.float32 if fp32 else torch.float16)
-            except RuntimeError as exc:
-                raise RuntimeError(f"{cls.__name__} failed on {dev}: {exc}") from exc
-            _RESTORER_CACHE[key] = (m, state_dict)   # the strong reference keeps id(state_dict) unique
-    return m
+    cls = SwinDeblur if kind == "blur" else DCNRestorer
+    args = (cfg,) if cfg is not None else ()
+    return _cached_model(cls.__name__, device, (kind, bool(fp32), cfg), state_dict, lambda dev: cls(
+        *args, state_dict=state_dict, device=dev, dtype=torch.float32 if fp32 else torch.float16))
 
 
 def restore_frames_blur_device(frames_d: torch.Tensor, blur_maps, block_size: int, *, batch_size: int = 4,
@@ -533,13 +508,9 @@ def restore_frames_blur(frames: List[np.ndarray], blur_maps: np.ndarray, block_s
     still has map > 0, re-paste the ORIGINAL decoded blocks whose remaining level is <= 0,
     decrement.  BGR uint8 frames in and out; `batch_size` as in the reference (elvis.py:91).
     Host to host around `restore_frames_blur_device`."""
-    if not frames:
-        return []
-    model = _get_restorer("blur", device, fp32, cfg, state_dict)
-    with torch.cuda.device(model.device):
-        return frames_to_host(restore_frames_blur_device(
-            frames_to_device(frames, model.device), blur_maps, block_size, batch_size=batch_size, max_rounds=max_rounds,
-            fp32=fp32, cfg=cfg, state_dict=state_dict))
+    return _host_to_host(frames, lambda: _get_restorer("blur", device, fp32, cfg, state_dict).device, restore_frames_blur_device,
+                         blur_maps, block_size, batch_size=batch_size, max_rounds=max_rounds, fp32=fp32, cfg=cfg,
+                         state_dict=state_dict)
 
 
 def restore_frames_dct_device(frames_d: torch.Tensor, strength_maps, block_size: int, *, fp32: bool = False, cfg=None,
@@ -561,12 +532,8 @@ def restore_frames_dct(frames: List[np.ndarray], strength_maps: np.ndarray, bloc
     defines it with the round loop's signature and ONE pass: the LaplacianVCAR-style DCN restorer
     sees the whole chunk (its temporal window crosses frames), then `level > 0 ? restored : decoded`.
     Host to host around `restore_frames_dct_device`."""
-    if not frames:
-        return []
-    model = _get_restorer("dct", device, fp32, cfg, state_dict)
-    with torch.cuda.device(model.device):
-        return frames_to_host(restore_frames_dct_device(
-            frames_to_device(frames, model.device), strength_maps, block_size, fp32=fp32, cfg=cfg, state_dict=state_dict))
+    return _host_to_host(frames, lambda: _get_restorer("dct", device, fp32, cfg, state_dict).device, restore_frames_dct_device,
+                         strength_maps, block_size, fp32=fp32, cfg=cfg, state_dict=state_dict)
 
 
 # ----------------------------------------------------------------------------- Blur / DCT slots, host to host

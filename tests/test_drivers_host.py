@@ -144,3 +144,37 @@ def test_dct_driver_halo_is_independent_of_worker_count(tmp_path):
         assert sorted(os.listdir(d)) == [f"{i + 1:05d}.png" for i in range(6)]      # scratch directory removed
         outs.append(frameio.load_frames(d))
     assert all(np.array_equal(a, b) for a, b in zip(*outs))
+
+
+def test_clip_file_jobs_report_their_own_device_and_range(tmp_path, monkeypatch):
+    """The clip-file driver's jobs go through the same spawned workers as a directory driver's: two failing jobs are
+    reported with each one's own device and frame range.  The workers fail in the stand-in, or before it where the
+    device they are told to use does not exist; either way no output is written."""
+    raw, out = tmp_path / "in.yuv", tmp_path / "out.yuv"
+    raw.write_bytes(bytes(i % 251 for i in range(5 * 18 * 6 * 3 // 2)))           # 5 frames of 18x6 I420
+    monkeypatch.setattr(drivers, "resolve_device_list", lambda *a, **k: [torch.device("cuda:0"), torch.device("cuda:1")])
+    with pytest.raises(RuntimeError, match="restoration worker") as ei:
+        drivers.restore_yuv_clip("blur", str(raw), str(out), np.ones((5, 3, 9), np.int32), 2, width=18, height=6,
+                                 _shard_fn=_hooks.failing)
+    for report in ("shard on cuda:0, frames [0, 3):\nTraceback", "shard on cuda:1, frames [3, 5):\nTraceback"):
+        assert report in str(ei.value)
+    assert out.read_bytes() == bytes(out.stat().st_size)                           # created at full length, never written
+
+
+def test_shard_job_pickles_with_each_source_and_sink():
+    import dataclasses
+    import itertools
+    import pickle
+    names, maps = ["00001.png", "00002.png"], np.arange(12, dtype=np.int32).reshape(2, 2, 3)
+    sources = [drivers.PngDirSource("in", names, "device"), drivers.ClipFileSource("a.y4m", "y4m", 18, 6, 2)]
+    sinks = [drivers.PngDirSink("out", names, "pil"), drivers.ClipFileSink("b.yuv", "yuv", 0, 18, 6)]
+    for source, sink in itertools.product(sources, sinks):
+        job = drivers.ShardJob(shard_fn=_hooks.plus_device_tag, source=source, sink=sink, resident=False, start=0, end=2,
+                               halo=1, maps=maps, block_size=8, device="cuda:1", kw={"fp32": True})
+        back = pickle.loads(pickle.dumps(job))
+        assert back.shard_fn is _hooks.plus_device_tag and back.source == source and back.sink == sink
+        assert np.array_equal(back.maps, maps) and back.maps.dtype == maps.dtype
+        for field in ("resident", "start", "end", "halo", "block_size", "device", "kw"):
+            assert getattr(back, field) == getattr(job, field), field
+        with pytest.raises(dataclasses.FrozenInstanceError):
+            job.start = 1

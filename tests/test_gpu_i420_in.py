@@ -269,9 +269,10 @@ def test_restore_yuv_clip_ranges_land_at_their_own_offsets(gpu_device, clip, tmp
         out = str(tmp_path / name)
         with open(out, "wb") as f:
             f.write(want[:head] + b"\xee" * (len(want) - head))
+        source, sink = drivers.ClipFileSource(clip["raw"], "yuv", 18, 6, 5), drivers.ClipFileSink(out, name[-3:], head, 18, 6)
         for start, end in ((3, 5), (0, 3)):
-            drivers._yuv_clip_worker(_plus_global_index, (clip["raw"], "yuv", 18, 6), (out, name[-3:], head), 5, start, end, maps, 2,
-                                     "cuda:0", 1, {})
+            drivers._shard_worker(drivers.ShardJob(_plus_global_index, source, sink, resident=True, start=start, end=end, halo=1, maps=maps,
+                                                   block_size=2, device="cuda:0", kw={}))
         assert open(out, "rb").read() == want, name
 
 
@@ -307,14 +308,17 @@ def test_restore_yuv_clip_dct_and_its_halo(gpu_device, tmp_path):
     split = str(tmp_path / "split.yuv")
     with open(split, "wb") as f:
         f.truncate(want.size)
+    source, sink = drivers.ClipFileSource(path, "y4m", 96, 64, 4), drivers.ClipFileSink(split, "yuv", 0, 96, 64)
     for start, end in ((0, 2), (2, 4)):
-        drivers._yuv_clip_worker(drivers._dct_clip_shard, (path, "y4m", 96, 64), (split, "yuv", 0), 4, start, end, rounds, 8, "cuda:0", 3, {})
+        drivers._shard_worker(drivers.ShardJob(drivers._dct_clip_shard, source, sink, resident=True, start=start, end=end, halo=3,
+                                               maps=rounds, block_size=8, device="cuda:0", kw={}))
     assert open(split, "rb").read() == want.tobytes()
     # and without the halo the ranges' edge frames miss their neighbours
     with open(split, "wb") as f:
         f.truncate(want.size)
     for start, end in ((0, 2), (2, 4)):
-        drivers._yuv_clip_worker(drivers._dct_clip_shard, (path, "y4m", 96, 64), (split, "yuv", 0), 4, start, end, rounds, 8, "cuda:0", 0, {})
+        drivers._shard_worker(drivers.ShardJob(drivers._dct_clip_shard, source, sink, resident=True, start=start, end=end, halo=0,
+                                               maps=rounds, block_size=8, device="cuda:0", kw={}))
     assert open(split, "rb").read() != want.tobytes()
 
 

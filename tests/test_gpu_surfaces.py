@@ -139,6 +139,48 @@ def test_directory_drivers_match_frames_level(gpu_device, tmp_path):
     assert all(np.array_equal(a, b) for a, b in zip(frameio.load_frames(src), want_d))
 
 
+def test_model_drivers_with_device_png_io_match_pil(gpu_device, tmp_path, monkeypatch):
+    """`png_reader="device", png_writer="device"` on the model drivers: the files decode to exactly the frames of the
+    ("pil", "pil") run, and the worker's pixels stay resident from the PNG reader through the restorer to the PNG
+    writer - the Blur driver runs with `frames_to_host` and the host branch of `frames_to_device` refusing."""
+    from elvis_amd import drivers, frameio, handoff, recompose, restore
+    frames = _frames(3, 64, 96, 11)
+    rounds = np.random.default_rng(12).integers(0, 3, size=(3, 8, 12)).astype(np.int32)
+
+    def run(driver, name, **kw):
+        d = tmp_path / name
+        for i, f in enumerate(frames):
+            frameio.save_frame(f, d / f"{i + 1:05d}.png")
+        driver(str(d), rounds, 8, devices=["cuda:0"], **kw)
+        return frameio.load_frames(d)
+
+    device_io = dict(png_reader="device", png_writer="device")
+    want_b = run(drivers.restore_blur_adaptive, "blur_pil", batch_size=2)
+    want_d = run(drivers.restore_dct_adaptive, "dct_pil", temporal_radius=1)
+    assert not all(np.array_equal(a, b) for a, b in zip(want_b, frames))           # the restorers did run
+    assert not all(np.array_equal(a, b) for a, b in zip(want_d, frames))
+    got_d = run(drivers.restore_dct_adaptive, "dct_device", temporal_radius=1, **device_io)
+    assert len(got_d) == 3 and all(np.array_equal(a, b) for a, b in zip(got_d, want_d))
+
+    def refuse(*args, **kw):
+        raise AssertionError("pixels went through the host")
+
+    real_to_device = recompose.frames_to_device
+
+    def resident_only(frames, device):
+        return real_to_device(frames, device) if isinstance(frames, torch.Tensor) else refuse()
+
+    for module in (recompose, restore, drivers, handoff):
+        for name, fn in (("frames_to_host", refuse), ("frames_to_device", resident_only)):
+            if hasattr(module, name):
+                monkeypatch.setattr(module, name, fn)
+    with pytest.raises(AssertionError, match="through the host"):
+        run(drivers.restore_blur_adaptive, "blur_caught", batch_size=2)              # the ("pil", "pil") run is caught
+    got_b = run(drivers.restore_blur_adaptive, "blur_device", batch_size=2, **device_io)
+    monkeypatch.undo()
+    assert len(got_b) == 3 and all(np.array_equal(a, b) for a, b in zip(got_b, want_b))
+
+
 def test_convert_act_and_mixed_sections(gpu_device):
     from elvis_amd import ops
     from elvis_amd.sinsr import SinSRModel
