@@ -36,6 +36,8 @@ from .complexity import (BlockComplexity, EVCAConfig, analyze_frames, block_comp
                          removability_from_complexity, resize_masks_nearest)
 from .lpips import (LpipsAlex, calculate_lpips, calculate_lpips_per_frame, get_lpips_model,  # noqa: F401
                     load_lpips_state_dict, lpips_device)
+from .vmaf import (VmafModel, calculate_vmaf, calculate_vmaf_frames, get_vmaf_model, load_vmaf_model, luma_device,  # noqa: F401
+                   make_vmaf_model, vmaf_device, vmaf_features_device, vmaf_stats)
 from .png import decode_png_device, encode_png_device, load_frames_device, save_frames, save_frames_device  # noqa: F401
 from .drivers import (calculate_removability_scores_from_frames, restore_blur_adaptive, restore_dct_adaptive,  # noqa: F401
                       restore_downsampled_with_sinsr, restore_shrunk_frames, restore_yuv_clip, stretch_shrunk_frames)

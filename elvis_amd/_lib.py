@@ -103,6 +103,10 @@ SIGNATURES = {
     "elvis_lpips_maxpool_f32": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_lpips_distance_workspace_bytes": [i32, i32, i32],
     "elvis_lpips_distance_f64": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_vmaf_luma_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_vmaf_workspace_bytes": [i32, i32, i32],
+    "elvis_vmaf_features_f64": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "elvis_vmaf_predict_f64": [vp, vp, vp, i32, i32, i32, vp],
     "elvis_png_stats": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_png_pack": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp],
     "elvis_png_gather": [vp, i64, vp, i32, vp, i64, vp, vp],
@@ -150,6 +154,7 @@ def lib() -> C.CDLL:
         handle.elvis_inpaint_workspace_bytes.restype = C.c_size_t
         handle.elvis_lpips_distance_workspace_bytes.restype = C.c_size_t
         handle.elvis_rrdb_packed_weight_bytes.restype = C.c_size_t
+        handle.elvis_vmaf_workspace_bytes.restype = C.c_size_t
         if handle.elvis_abi_version() != 1:
             raise RuntimeError("libelvis_amd.so ABI version mismatch")
         _lib = handle

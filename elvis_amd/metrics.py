@@ -327,14 +327,19 @@ def metric_frame_indices(frame_count: int, metric_stride: int) -> List[int]:
 
 def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frames: Sequence[np.ndarray],
                            fg_masks: Sequence[np.ndarray], metric_stride: int = 1, device="cuda:0",
-                           lpips_model=None) -> Dict[str, Dict[str, float]]:
+                           lpips_model=None, vmaf_model=None) -> Dict[str, Dict[str, float]]:
     """The numeric core of _evaluate_single_video_metrics (elvis.py:3799-3878): masked PSNR, SSIM and MSE of the
     sampled frames, foreground (inside fg_masks) and background (outside), each as _mean and _std.  Bitrate, VMAF and
     FVMD keys are not produced.  Per-frame MSE is a float32 number, as the reference's is (see below).
     With `lpips_model` (an `elvis_amd.lpips.LpipsAlex` on `device`) both regions gain `lpips_mean` / `lpips_std` as
     elvis.py:3853-3893 forms them, on the tensors already uploaded: the foreground from the fg-masked frames cropped to
     the ROI around the union of all foreground masks (elvis.py:3639-3646), the background from the bg-masked whole
-    frames.  An ROI under 31 x 31 raises ValueError.  Without it (None) the result is what it was."""
+    frames.  An ROI under 31 x 31 raises ValueError.  Without it (None) the result is what it was.
+    With `vmaf_model` (an `elvis_amd.vmaf.VmafModel`) both regions gain `vmaf_mean` / `vmaf_std`, on the same tensors and
+    the same two regions: the luma (`vmaf.luma_device`, order "bgr") of the fg-masked frames cropped to that ROI, and of
+    the bg-masked whole frames; motion runs between consecutive sampled frames.  The reference squeezes these masked
+    clips through a lossy x264 encode before it scores them (elvis.py:3895-3929); that encode is NOT reproduced.  An ROI
+    under 64 x 64 raises ValueError.  Without it (None) the result is what it was."""
     if metric_stride < 1:
         raise ValueError("metric_stride must be at least 1")
     count = min(len(reference_frames), len(decoded_frames))
@@ -361,6 +366,9 @@ def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frame
         roi = None
         if lpips_model is not None:
             from .lpips import lpips_device
+        if vmaf_model is not None:
+            from .vmaf import luma_device, vmaf_device
+        if lpips_model is not None or vmaf_model is not None:
             h, w = refs[0].shape[:2]
             bx, by, bw, bh = compute_mask_union_bbox(list(fg_masks[:count]), w, h, device=dev)
             roi = (by, min(h, by + max(1, bh)), bx, min(w, bx + max(1, bw)))
@@ -378,4 +386,9 @@ def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frame
             if lpips_model is not None:
                 scores = lpips_device(a, b, lpips_model, masks=m, rect=roi if region == "foreground" else None, order="bgr").cpu().numpy()
                 result[region]["lpips_mean"], result[region]["lpips_std"] = float(np.mean(scores)), float(np.std(scores))
+            if vmaf_model is not None:
+                rect = roi if region == "foreground" else None
+                scores = vmaf_device(luma_device(a, "bgr", masks=m, rect=rect), luma_device(b, "bgr", masks=m, rect=rect),
+                                     vmaf_model).cpu().numpy()
+                result[region]["vmaf_mean"], result[region]["vmaf_std"] = float(np.mean(scores)), float(np.std(scores))
         return result

@@ -622,6 +622,43 @@ size_t elvis_lpips_distance_workspace_bytes(int n, int h, int w);
 int elvis_lpips_distance_f64(const float* x, const float* y, const float* weight, void* workspace, double* out, int n,
                              int h, int w, int c, int pitch, int accumulate, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ VMAF (vmaf.hip)
+ * The third per-frame metric of the evaluation report.  The reference writes both clips to disk as I420 and starts the
+ * vmaf binary in a subprocess (elvis.py:3197-3356, presley.py:262-326); neither libvmaf nor its model file is available
+ * to this build, so this is a BUILD-DEFINED restatement of the published float feature extractors - VIF on four
+ * scales, ADM2 on four scales, motion2 - and of the nu-SVR over them.  The contract is stated in numpy float64 in
+ * tests/_vmaf_ref.py (and in words in DESIGN.md 7); the kernels agree with it to 1e-9 * max(1, |value|).  It does not
+ * claim libvmaf's numbers.  All arithmetic is float64 on luma less 128, every per-pixel quantity in one stated order
+ * (a filter is ((f0 x0 + f1 x1) + f2 x2) + ..., vertical pass first, mirror border without repeating the edge), no FMA
+ * contraction, no atomics, fixed summation orders: the same input gives the same bytes, whatever n it is given with.
+ *
+ * elvis_vmaf_luma_u8: frames u8 [n, h, w, 3] (order 0 rgb, 1 bgr) -> out u8 [n, y1 - y0, x1 - x0], the Y of
+ *   elvis_rgb_to_i420_u8 over the rectangle [y0, y1) x [x0, x1), any h and w.  masks NULL, or u8 [n, h, w]: where
+ *   (mask != 0) == invert the pixel's three bytes count as 0 (elvis.py:615-624).  n == 0 is a no-op. */
+int elvis_vmaf_luma_u8(const uint8_t* frames, const uint8_t* masks, uint8_t* out, int n, int h, int w, int order,
+                       int invert, int y0, int y1, int x0, int x1, elvis_stream_t stream);
+/* Bytes of the workspace elvis_vmaf_features_f64 needs for n frame pairs of h x w: the pyramids of four frames at a
+ * time and every frame's tile partials; 0 for a bad shape (h or w under 64 included). */
+size_t elvis_vmaf_workspace_bytes(int n, int h, int w);
+/* ref, dis u8 [n, h, w] luma, h, w >= 64 -> out f64 [n, 6] = adm2, motion2, vif_scale0..3.  prev NULL, or u8 [h, w]:
+ * the reference frame before ref[0] (without it motion of frame 0 is 0); next NULL, or u8 [h, w]: the one after
+ * ref[n - 1] (without it motion2 of the last frame is its motion) - with both, a clip cut into calls gives the bytes
+ * of one call.  tables f64 [56]: the filters and constants, built on the host (elvis_amd/vmaf.py vmaf_tables):
+ * the normalised Gaussians of 17, 9, 5 and 3 taps, the 5-tap motion blur, the db2 low and high pass, cos^2(1 degree)
+ * and per scale 1 / Q for the h, v bands and for the d band.  workspace: elvis_vmaf_workspace_bytes(n, h, w) bytes,
+ * 8-byte aligned, written before it is read.  ELVIS_E_INVALID: h or w under 64, n < 0 or n >= 65535, a null ref / dis
+ * / tables / workspace / out.  n == 0 is a no-op. */
+int elvis_vmaf_features_f64(const uint8_t* ref, const uint8_t* dis, const uint8_t* prev, const uint8_t* next,
+                            const double* tables, double* workspace, double* out, int n, int h, int w,
+                            elvis_stream_t stream);
+/* feats f64 [n, 6] -> out f64 [n], the score.  model f64 [21 + 7 nsv]: slopes[7], intercepts[7], rho, gamma, the clip's
+ * two ends, the transform's p0, p1, p2, then the support vectors [nsv, 6] and their coefficients [nsv].
+ * x_i = slopes[i + 1] f_i + intercepts[i + 1]; p = sum_j coef_j exp(-gamma |sv_j - x|^2) - rho;
+ * s = (p - intercepts[0]) / slopes[0]; flags bit 0: s = p0 + p1 s + p2 s^2, bit 1: no less than the s it came from;
+ * bit 2: clipped.  One wave per frame, a fixed summation order. */
+int elvis_vmaf_predict_f64(const double* feats, const double* model, double* out, int n, int nsv, int flags,
+                           elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ PNG writer (png.hip)
  * Lossless PNG files written by the device in place of the cv2.imwrite(...png) that ends every client-side entry point
  * of the reference (elvis.py:131-135, 4566-4579).  Decodable by any PNG reader; the bytes are this build's own, not
