@@ -38,6 +38,8 @@ from .lpips import (LpipsAlex, calculate_lpips, calculate_lpips_per_frame, get_l
                     load_lpips_state_dict, lpips_device)
 from .vmaf import (VmafModel, calculate_vmaf, calculate_vmaf_frames, get_vmaf_model, load_vmaf_model, luma_device,  # noqa: F401
                    make_vmaf_model, vmaf_device, vmaf_features_device, vmaf_stats)
+from .fvmd import (FvmdConfig, FvmdNoTrajectories, calculate_fvmd, calculate_fvmd_device, frechet_distance_device,  # noqa: F401
+                   fvmd_device, motion_features_device, track_keypoints_device)
 from .png import decode_png_device, encode_png_device, load_frames_device, save_frames, save_frames_device  # noqa: F401
 from .drivers import (calculate_removability_scores_from_frames, restore_blur_adaptive, restore_dct_adaptive,  # noqa: F401
                       restore_downsampled_with_sinsr, restore_shrunk_frames, restore_yuv_clip, stretch_shrunk_frames)

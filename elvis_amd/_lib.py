@@ -107,6 +107,14 @@ SIGNATURES = {
     "elvis_vmaf_workspace_bytes": [i32, i32, i32],
     "elvis_vmaf_features_f64": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "elvis_vmaf_predict_f64": [vp, vp, vp, i32, i32, i32, vp],
+    "elvis_fvmd_pyramid_bytes": [i32, i32, i32],
+    "elvis_fvmd_pyramid_f64": [vp, vp, i32, i32, i32, vp],
+    "elvis_fvmd_track_f64": [vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "elvis_fvmd_features_f64": [vp, vp, i32, i32, vp],
+    "elvis_fvmd_gram_workspace_bytes": [i32, i32, i32],
+    "elvis_fvmd_gram_f64": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "elvis_fvmd_singular_values_f64": [vp, vp, i32, i32, vp],
+    "elvis_fvmd_finish_f64": [vp, vp, vp, i32, i32, i32, vp],
     "elvis_png_stats": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_png_pack": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp],
     "elvis_png_gather": [vp, i64, vp, i32, vp, i64, vp, vp],
@@ -155,6 +163,8 @@ def lib() -> C.CDLL:
         handle.elvis_lpips_distance_workspace_bytes.restype = C.c_size_t
         handle.elvis_rrdb_packed_weight_bytes.restype = C.c_size_t
         handle.elvis_vmaf_workspace_bytes.restype = C.c_size_t
+        handle.elvis_fvmd_pyramid_bytes.restype = C.c_size_t
+        handle.elvis_fvmd_gram_workspace_bytes.restype = C.c_size_t
         if handle.elvis_abi_version() != 1:
             raise RuntimeError("libelvis_amd.so ABI version mismatch")
         _lib = handle

@@ -327,10 +327,10 @@ def metric_frame_indices(frame_count: int, metric_stride: int) -> List[int]:
 
 def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frames: Sequence[np.ndarray],
                            fg_masks: Sequence[np.ndarray], metric_stride: int = 1, device="cuda:0",
-                           lpips_model=None, vmaf_model=None) -> Dict[str, Dict[str, float]]:
+                           lpips_model=None, vmaf_model=None, fvmd=None) -> Dict[str, Dict[str, float]]:
     """The numeric core of _evaluate_single_video_metrics (elvis.py:3799-3878): masked PSNR, SSIM and MSE of the
-    sampled frames, foreground (inside fg_masks) and background (outside), each as _mean and _std.  Bitrate, VMAF and
-    FVMD keys are not produced.  Per-frame MSE is a float32 number, as the reference's is (see below).
+    sampled frames, foreground (inside fg_masks) and background (outside), each as _mean and _std.  Bitrate keys are not
+    produced; LPIPS, VMAF and FVMD keys only on request (below).  Per-frame MSE is a float32 number, as the reference's is.
     With `lpips_model` (an `elvis_amd.lpips.LpipsAlex` on `device`) both regions gain `lpips_mean` / `lpips_std` as
     elvis.py:3853-3893 forms them, on the tensors already uploaded: the foreground from the fg-masked frames cropped to
     the ROI around the union of all foreground masks (elvis.py:3639-3646), the background from the bg-masked whole
@@ -339,7 +339,14 @@ def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frame
     the same two regions: the luma (`vmaf.luma_device`, order "bgr") of the fg-masked frames cropped to that ROI, and of
     the bg-masked whole frames; motion runs between consecutive sampled frames.  The reference squeezes these masked
     clips through a lossy x264 encode before it scores them (elvis.py:3895-3929); that encode is NOT reproduced.  An ROI
-    under 64 x 64 raises ValueError.  Without it (None) the result is what it was."""
+    under 64 x 64 raises ValueError.  Without it (None) the result is what it was.
+    With `fvmd` (an `elvis_amd.fvmd.FvmdConfig`, or True for the default one) both regions gain `fvmd` / `fvmd_std`, the
+    reference's key names (elvis.py:4035-4038), from `fvmd.calculate_fvmd_device` on the luma of the same masked tensors
+    and the same two regions.  The reference's frame sampling is kept (elvis.py:3954-3981): the config's `stride` is
+    lowered until ten frames are sampled, `max_frames` cuts the list, and with fewer than ten sampled frames both keys
+    are NaN (elvis.py:3882-3885).  BUILD-DEFINED: the score is this build's KLT restatement and does NOT claim parity with
+    the `fvmd` package (elvis_amd/fvmd.py).  An ROI under 64 x 64 raises ValueError.  Without it (None) the result is
+    what it was."""
     if metric_stride < 1:
         raise ValueError("metric_stride must be at least 1")
     count = min(len(reference_frames), len(decoded_frames))
@@ -368,7 +375,15 @@ def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frame
             from .lpips import lpips_device
         if vmaf_model is not None:
             from .vmaf import luma_device, vmaf_device
-        if lpips_model is not None or vmaf_model is not None:
+        fvmd_idx = None
+        if fvmd is not None and fvmd is not False:
+            from . import fvmd as _fvmd
+            from .vmaf import luma_device
+            fvmd_cfg = _fvmd.FvmdConfig() if fvmd is True else fvmd
+            if not isinstance(fvmd_cfg, _fvmd.FvmdConfig):
+                raise ValueError("fvmd must be None, True or an elvis_amd.fvmd.FvmdConfig")
+            fvmd_idx = _fvmd_sample_indices(len(idx), fvmd_cfg.stride, fvmd_cfg.max_frames)
+        if lpips_model is not None or vmaf_model is not None or fvmd_idx is not None:
             h, w = refs[0].shape[:2]
             bx, by, bw, bh = compute_mask_union_bbox(list(fg_masks[:count]), w, h, device=dev)
             roi = (by, min(h, by + max(1, bh)), bx, min(w, bx + max(1, bw)))
@@ -391,4 +406,34 @@ def evaluate_fg_bg_metrics(reference_frames: Sequence[np.ndarray], decoded_frame
                 scores = vmaf_device(luma_device(a, "bgr", masks=m, rect=rect), luma_device(b, "bgr", masks=m, rect=rect),
                                      vmaf_model).cpu().numpy()
                 result[region]["vmaf_mean"], result[region]["vmaf_std"] = float(np.mean(scores)), float(np.std(scores))
+            if fvmd_idx is not None:
+                value, std = float("nan"), float("nan")                     # elvis.py:3882-3885
+                if len(fvmd_idx) >= 10:
+                    rect = roi if region == "foreground" else None
+                    planes = [luma_device(t, "bgr", masks=m, rect=rect) for t in (a, b)]
+                    if fvmd_idx != list(range(len(idx))):
+                        at = torch.as_tensor(fvmd_idx, dtype=torch.long, device=dev)
+                        planes = [p.index_select(0, at) for p in planes]
+                    value, std = _fvmd.calculate_fvmd_device(planes[0], planes[1], fvmd_cfg, stride=1, max_frames=None,
+                                                             early_stop_delta=fvmd_cfg.early_stop_delta,
+                                                             early_stop_window=fvmd_cfg.early_stop_window)
+                result[region]["fvmd"], result[region]["fvmd_std"] = value, std
         return result
+
+
+def _fvmd_sample_indices(frame_count: int, fvmd_stride: int, fvmd_max_frames: Optional[int]) -> List[int]:
+    """elvis.py:3954-3976: the frames FVMD is given - the stride lowered so that ten frames are sampled where the clip
+    has them, then `max_frames`."""
+    min_fvmd_samples = 10
+    total_available_frames = frame_count
+    if fvmd_max_frames is not None and fvmd_max_frames > 0:
+        total_available_frames = min(total_available_frames, fvmd_max_frames)
+    effective_stride = max(1, fvmd_stride)
+    if total_available_frames >= min_fvmd_samples:
+        effective_stride = min(effective_stride, max(1, total_available_frames // min_fvmd_samples))
+    else:
+        effective_stride = 1
+    fvmd_indices = list(range(0, frame_count, effective_stride)) or [0]
+    if fvmd_max_frames is not None and fvmd_max_frames > 0:
+        fvmd_indices = fvmd_indices[:fvmd_max_frames]
+    return fvmd_indices

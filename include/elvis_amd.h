@@ -659,6 +659,84 @@ int elvis_vmaf_features_f64(const uint8_t* ref, const uint8_t* dis, const uint8_
 int elvis_vmaf_predict_f64(const double* feats, const double* model, double* out, int n, int nsv, int flags,
                            elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ FVMD (fvmd.hip)
+ * The sixth quality number of the evaluation report.  The reference hands two clips to the `fvmd` package
+ * (track_keypoints, calc_hist, calculate_fd_given_vectors: elvis.py:3476-3505, inside calculate_fvmd,
+ * elvis.py:3358-3597).  BUILD-DEFINED: the package is available neither to the reference tree nor to this build; its
+ * tracker (PIPs++, a network), its calc_hist and its VideoDataset semantics cannot be read.  This is a restatement of
+ * the published form - tracks -> velocity / acceleration -> cell orientation histograms -> Frechet distance - with a
+ * pyramidal Lucas-Kanade (KLT) tracker in the network's place.  It does NOT claim parity with the `fvmd` package and its
+ * values are not comparable with published FVMD numbers.  It is pinned against its own numpy float64 statement,
+ * tests/_fvmd_ref.py (1e-9 * max(1, |value|) per stage), and - for the control flow of calculate_fvmd only - against
+ * the reference's own code (tests/golden/fvmd.npz).
+ *
+ * THE CONTRACT.  All arithmetic is float64, no FMA, every reduction in a fixed order, no float atomics; nothing branches
+ * on data except the singular test below.
+ *   input      8-bit luma [F, h, w], h, w >= 64, taken as float64 unscaled (a masked pixel is luma 16).
+ *   segments   sliding windows of S frames (10 <= S <= 16, the reference's clip_seq_len, elvis.py:3452) starting every
+ *              segment_step frames: B = (F - S) / segment_step + 1; each is tracked on its own from a fresh grid.
+ *              segment_step is this build's reading of VideoDataset(..., stride=1).
+ *   keypoints  20 x 20, x_j = ((j + 0.5) w) / 20 - 0.5, y_i = ((i + 0.5) h) / 20 - 0.5; index i * 20 + j.
+ *   pyramid    3 levels; level l + 1 = level l filtered with [1,4,6,4,1] / 16, vertical pass first, taps ascending
+ *              (((c0 x0 + c1 x1) + c2 x2) + ...), mirror border without repeating the edge, kept at even indices: size
+ *              (n + 1) / 2.
+ *   frame step t -> t + 1, per point, levels 2, 1, 0: d = 0 at level 2 and is doubled on the way down; p = position /
+ *              2^level; window = the 225 integer offsets |ox|, |oy| <= 7, offset o = (oy + 7) 15 + (ox + 7).  A sample is
+ *              bilinear, (1 - ay) ((1 - ax) v00 + ax v01) + ay ((1 - ax) v10 + ax v11), its coordinate clamped to
+ *              [0, n - 1] first.  T(o) = I_t(p + o); gx(o) = (I_t(p + o + (1,0)) - I_t(p + o - (1,0))) / 2, gy likewise;
+ *              G = sum [gx gx, gx gy; gx gy, gy gy] once per level.  Then exactly 8 iterations, no early exit:
+ *              b = sum (T(o) - I_{t+1}((p + o) + d)) (gx, gy); d += G^-1 b by the closed form
+ *              ((gyy bx - gxy by) / det, (gxx by - gxy bx) / det).  THE ONE DATA BRANCH: with lambda_min(G) =
+ *              ((gxx + gyy) - sqrt((gxx - gyy)^2 + 4 gxy^2)) / 2, a level with lambda_min / 225 < 1e-3 adds no update.
+ *              After level 0 the position is p + d clamped to the frame; a point is never dropped.  A sum over the
+ *              window is: lane L of 64 adds offsets L, L + 64, L + 128, L + 192 (< 225) in that order, then the
+ *              butterfly v += v[lane ^ 32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.  Exact consequences: a black (masked) region has
+ *              G = 0 and does not move; a static clip has d = 0.
+ *   fields     v_t = p_{t+1} - p_t (S - 1 of them), a_t = v_{t+1} - v_t (S - 2), in input pixels.
+ *   histograms 4 x 4 cells of 5 x 5 points, 8 bins centred at k pi / 4: for a vector of magnitude m,
+ *              u = atan2(y, x) / (pi / 4) (+ 8 where negative), k = floor(u), f = u - k; (1 - f) m goes to bin k mod 8,
+ *              f m to bin (k + 1) mod 8 - a soft vote, continuous across a pure horizontal pan where vy is +-1e-17.
+ *              A cell's bin is summed over its points in point order.  Row of a segment: velocity fields, then
+ *              acceleration fields, each [cell][bin], unnormalised: d = (2 S - 3) 128.
+ *   distance   rows A [n, d] (reference) and Bm [m, d] (decoded), each centred by its own column means, n, m >= 2:
+ *              FD = |mu_A - mu_B|^2 + |A|_F^2 / (n - 1) + |Bm|_F^2 / (m - 1) - 2 |A Bm^T|_* / sqrt((n - 1)(m - 1)),
+ *              |.|_* the sum of singular values.  In exact arithmetic this is tr S1 + tr S2 - 2 tr (S1 S2)^(1/2) with
+ *              np.cov covariances: the non-zero eigenvalues of S1 S2 are those of (A Bm^T)(A Bm^T)^T / ((n-1)(m-1)).
+ *              The form needs no d x d matrix and no square root of a singular product (n, m << d = 3712 here).
+ * n == 0 / no segment is a no-op; ELVIS_E_INVALID before any launch for a bad shape or a null pointer. */
+
+/* elvis.py:3476-3505 (what track_keypoints first does with a clip).  Bytes of the pyramid of `frames` planes of h x w:
+ * levels 1 and 2 as float64 (level 0 is the luma itself); 0 for a bad shape (h or w under 64, frames > 65535). */
+size_t elvis_fvmd_pyramid_bytes(int frames, int h, int w);
+/* elvis.py:3476-3505.  luma u8 [frames, h, w] -> pyramid: level 1 f64 [frames, h1, w1], then level 2 f64
+ * [frames, h2, w2], h1 = (h + 1) / 2, h2 = (h1 + 1) / 2 (fvmd_pyr_down_kernel, a lane per output pixel). */
+int elvis_fvmd_pyramid_f64(const uint8_t* luma, double* pyramid, int frames, int h, int w, elvis_stream_t stream);
+/* elvis.py:3476-3505 (track_keypoints).  luma and its pyramid -> tracks f64 [B, seq_len, 400, 2] = (x, y), B =
+ * (frames - seq_len) / segment_step + 1 (nothing is written when frames < seq_len).  One wave per (segment, point),
+ * template and gradients in registers across a level's 8 iterations (fvmd_track_kernel).  10 <= seq_len <= 16. */
+int elvis_fvmd_track_f64(const uint8_t* luma, const double* pyramid, double* tracks, int frames, int h, int w, int seq_len,
+                         int segment_step, elvis_stream_t stream);
+/* elvis.py:3476-3505 (calc_hist on velocities and accelerations, concatenated).  tracks f64 [segments, seq_len, 400, 2]
+ * -> rows f64 [segments, (2 seq_len - 3) 128] (fvmd_hist_kernel, a workgroup per (segment, field)). */
+int elvis_fvmd_features_f64(const double* tracks, double* rows, int segments, int seq_len, elvis_stream_t stream);
+/* elvis.py:3476-3505 (calculate_fd_given_vectors).  Bytes of elvis_fvmd_gram_f64's workspace: (2 d + n + m) doubles;
+ * 0 for a bad shape (n or m under 2 or over 1024). */
+size_t elvis_fvmd_gram_workspace_bytes(int n, int m, int d);
+/* elvis.py:3476-3505 (calculate_fd_given_vectors).  a f64 [n, d], b f64 [m, d] -> gram f64 [n, m] = the centred
+ * A Bm^T (k ascending), scalars f64 [3] = |mu_A - mu_B|^2, |A|_F^2, |Bm|_F^2.  2 <= n, m <= 1024. */
+int elvis_fvmd_gram_f64(const double* a, const double* b, double* workspace, double* gram, double* scalars, int n, int m,
+                        int d, elvis_stream_t stream);
+/* elvis.py:3476-3505 (the matrix square root inside calculate_fd_given_vectors, here a nuclear norm).  vectors f64
+ * [k, len], k, len <= 1024, OVERWRITTEN -> sv f64 [k], unsorted: the singular values of the matrix (those past
+ * min(k, len) are 0 to rounding).  One-sided (Hestenes) Jacobi on the k vectors: round-robin pairing, 16 sweeps, a
+ * rotation skipped where |x.y| <= 1e-15 |x| |y|.  k * len <= 16384: one workgroup, the matrix in LDS
+ * (fvmd_jacobi_lds_kernel); above: one launch per pairing round, a workgroup per pair (fvmd_jacobi_round_kernel).  No
+ * kernel waits on another workgroup.  Give it the orientation with k <= len. */
+int elvis_fvmd_singular_values_f64(double* vectors, double* sv, int k, int len, elvis_stream_t stream);
+/* elvis.py:3476-3505 (calculate_fd_given_vectors' last line).  sv f64 [k], scalars f64 [3] of elvis_fvmd_gram_f64 ->
+ * out f64 [1] = ((scalars[0] + scalars[1] / (n - 1)) + scalars[2] / (m - 1)) - 2 (sum sv) / sqrt((n - 1)(m - 1)). */
+int elvis_fvmd_finish_f64(const double* sv, const double* scalars, double* out, int k, int n, int m, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ PNG writer (png.hip)
  * Lossless PNG files written by the device in place of the cv2.imwrite(...png) that ends every client-side entry point
  * of the reference (elvis.py:131-135, 4566-4579).  Decodable by any PNG reader; the bytes are this build's own, not
