@@ -163,9 +163,25 @@ def cell_point(c: int, a: int) -> int:
     return ((c // CELLS) * CELL_SIDE + a // CELL_SIDE) * GRID + (c % CELLS) * CELL_SIDE + a % CELL_SIDE
 
 
-def field_hist(vx: np.ndarray, vy: np.ndarray) -> np.ndarray:
-    """[..., 400] vectors -> [..., 128] = [cell][bin], the soft orientation vote, a cell summed in point order."""
+# One clause of the statement changed, selected by `mutant=`; the kernels are never changed.  tests/_fvmdcases.py names
+# the case each must move by a thousand bars.
+MUTANTS = ("vote_previous_bin", "cell_transposed", "acceleration_one_sided", "mean_over_n_minus_1", "centre_by_a")
+
+
+def field_hist(vx: np.ndarray, vy: np.ndarray, mutant=None, counts=None) -> np.ndarray:
+    """[..., 400] vectors -> [..., 128] = [cell][bin], the soft orientation vote, a cell summed in point order.  `counts`,
+    a dict, collects what the vectors reach: `boundary` (per bin k, vectors with u == k exactly), `wrapped` (u < 0 took
+    the + 8), `to_eight` (that sum rounded to 8.0, bin 8 & 7), `zero` (magnitude 0), `negative_zero` (a -0.0 component)."""
     m = np.sqrt(vx * vx + vy * vy)
+    if counts is not None:
+        u0 = np.arctan2(vy, vx) / QUARTER_PI
+        u1 = np.where(u0 < 0.0, u0 + 8.0, u0)
+        for k in range(BINS):
+            counts["boundary"][k] += int(((u1 == float(k)) & (m > 0.0)).sum())
+        counts["wrapped"] += int(((u0 < 0.0) & (m > 0.0)).sum())
+        counts["to_eight"] += int(((u1 == 8.0) & (m > 0.0)).sum())
+        counts["zero"] += int((m == 0.0).sum())
+        counts["negative_zero"] += int((((vx == 0.0) & np.signbit(vx)) | ((vy == 0.0) & np.signbit(vy))).sum())
     u = np.arctan2(vy, vx) / QUARTER_PI
     u = np.where(u < 0.0, u + 8.0, u)
     k = np.floor(u)
@@ -178,22 +194,35 @@ def field_hist(vx: np.ndarray, vy: np.ndarray) -> np.ndarray:
         acc = np.zeros(vx.shape[:-1] + (BINS,))
         for a in range(CELL_SIDE * CELL_SIDE):
             pt = cell_point(c, a)
+            if mutant == "cell_transposed":                                  # the point's row and column change places
+                pt = (pt % GRID) * GRID + pt // GRID
             kk = kb[..., pt, None]
-            acc = (acc + np.where(kk == bins, w0[..., pt, None], 0.0)) + np.where(((kk + 1) & (BINS - 1)) == bins, w1[..., pt, None], 0.0)
+            second = (kk - 1) if mutant == "vote_previous_bin" else (kk + 1)
+            acc = (acc + np.where(kk == bins, w0[..., pt, None], 0.0)) + np.where((second & (BINS - 1)) == bins, w1[..., pt, None], 0.0)
         out[..., c, :] = acc
     return out.reshape(vx.shape[:-1] + (CELLS * CELLS * BINS,))
 
 
-def features(tracks: np.ndarray) -> np.ndarray:
+def new_counts():
+    """What `field_hist` records of its vectors (see there)."""
+    return dict(boundary=[0] * BINS, wrapped=0, to_eight=0, zero=0, negative_zero=0)
+
+
+def features(tracks: np.ndarray, mutant=None, counts=None) -> np.ndarray:
     """[B,S,400,2] -> [B, (2 S - 3) 128]: velocity histograms, then acceleration histograms."""
+    if mutant is not None and mutant not in MUTANTS:
+        raise ValueError(f"fvmd: unknown mutant {mutant!r}")
     b = tracks.shape[0]
     v = tracks[:, 1:] - tracks[:, :-1]
-    a = v[:, 1:] - v[:, :-1]
-    return np.concatenate([field_hist(v[..., 0], v[..., 1]).reshape(b, -1), field_hist(a[..., 0], a[..., 1]).reshape(b, -1)], axis=1)
+    a = v[:, 1:] if mutant == "acceleration_one_sided" else v[:, 1:] - v[:, :-1]
+    return np.concatenate([field_hist(v[..., 0], v[..., 1], mutant, counts).reshape(b, -1),
+                           field_hist(a[..., 0], a[..., 1], mutant, counts).reshape(b, -1)], axis=1)
 
 
-def gram_parts(a: np.ndarray, b: np.ndarray):
+def gram_parts(a: np.ndarray, b: np.ndarray, mutant=None):
     """(centred A Bm^T [n,m], (|mu_A - mu_B|^2, |A|_F^2, |Bm|_F^2)); the means add the rows in order."""
+    if mutant is not None and mutant not in MUTANTS:
+        raise ValueError(f"fvmd: unknown mutant {mutant!r}")
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
         raise ValueError("fvmd: the two sets of rows must be [n, d] and [m, d]")
@@ -204,7 +233,9 @@ def gram_parts(a: np.ndarray, b: np.ndarray):
         s = np.zeros(rows.shape[1])
         for r in rows:
             s = s + r
-        mu.append(s / float(rows.shape[0]))
+        mu.append(s / float(rows.shape[0] - 1 if mutant == "mean_over_n_minus_1" else rows.shape[0]))
+    if mutant == "centre_by_a":
+        mu[1] = mu[0]
     ac, bc = a - mu[0], b - mu[1]
     dm = mu[0] - mu[1]
     return ac @ bc.T, np.asarray([(dm * dm).sum(), (ac * ac).sum(), (bc * bc).sum()])

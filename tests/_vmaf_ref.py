@@ -15,6 +15,11 @@ FEATURES = ("adm2", "motion2", "vif_scale0", "vif_scale1", "vif_scale2", "vif_sc
 BAR = 1e-9                                        # |device - statement| <= BAR * max(1, |statement|)
 SHAPES = ((64, 64), (66, 70), (71, 93), (270, 480))
 FRAMES = 3
+PASS_FRAMES, TILE_H = 4, 16                       # VMAF_PASS_FRAMES and VMAF_TH of csrc/vmaf.hip, for the mutants below
+# One clause of the statement changed, selected by `mutant=`; the kernels are never changed.  tests/_vmafcases.py names
+# the case each must move by a thousand bars.
+MUTANTS = ("mirror_repeats_edge", "decimate_odd", "adm_window_floor", "adm_threshold_no_centre", "motion2_before",
+           "vif_tile_row_more", "pass2_from_0", "adm_hw_swapped")
 
 CSF_A = ((0.62171, 0.67234, 0.72709, 0.67234), (0.34537, 0.41317, 0.49428, 0.41317), (0.18004, 0.22727, 0.28688, 0.22727),
          (0.091401, 0.11792, 0.15214, 0.11792))
@@ -57,31 +62,34 @@ def tables() -> np.ndarray:
 
 
 # ----------------------------------------------------------------------------- filters
-def reflect(idx: np.ndarray, n: int) -> np.ndarray:
+def reflect(idx: np.ndarray, n: int, mutant=None) -> np.ndarray:
+    if mutant == "mirror_repeats_edge":
+        idx = np.where(idx < 0, -idx - 1, idx)
+        return np.where(idx >= n, 2 * n - 1 - idx, idx)
     idx = np.abs(idx)
     return np.where(idx >= n, 2 * n - 2 - idx, idx)
 
 
-def filt(x: np.ndarray, f: np.ndarray, axis: int) -> np.ndarray:
+def filt(x: np.ndarray, f: np.ndarray, axis: int, mutant=None) -> np.ndarray:
     """Same-size filter along one axis, centred, mirror border."""
     n, r = x.shape[axis], len(f) // 2
     acc = None
     for k in range(len(f)):
-        term = f[k] * np.take(x, reflect(np.arange(n) + k - r, n), axis=axis)
+        term = f[k] * np.take(x, reflect(np.arange(n) + k - r, n, mutant), axis=axis)
         acc = term if acc is None else acc + term
     return acc
 
 
-def filt2(x: np.ndarray, f: np.ndarray) -> np.ndarray:
-    return filt(filt(x, f, -2), f, -1)
+def filt2(x: np.ndarray, f: np.ndarray, mutant=None) -> np.ndarray:
+    return filt(filt(x, f, -2, mutant), f, -1, mutant)
 
 
-def dwt_axis(x: np.ndarray, f: np.ndarray, axis: int) -> np.ndarray:
+def dwt_axis(x: np.ndarray, f: np.ndarray, axis: int, mutant=None) -> np.ndarray:
     n = x.shape[axis]
     m = (n + 1) // 2
     acc = None
     for k in range(4):
-        term = f[k] * np.take(x, reflect(2 * np.arange(m) + k - 1, n), axis=axis)
+        term = f[k] * np.take(x, reflect(2 * np.arange(m) + k - 1, n, mutant), axis=axis)
         acc = term if acc is None else acc + term
     return acc
 
@@ -96,19 +104,21 @@ def planes(y: np.ndarray) -> np.ndarray:
 
 
 # ----------------------------------------------------------------------------- VIF
-def vif(ref: np.ndarray, dis: np.ndarray, counts=None) -> np.ndarray:
+def vif(ref: np.ndarray, dis: np.ndarray, counts=None, mutant=None) -> np.ndarray:
     """[F,H,W] u8 x2 -> [F,4]."""
+    first = 1 if mutant == "decimate_odd" else 0
     x, y = planes(ref), planes(dis)
     out = np.empty((x.shape[0], 4), np.float64)
     for s, taps in enumerate(VIF_TAPS):
         g = gaussian(taps)
         if s:
             h, w = x.shape[1] // 2, x.shape[2] // 2
-            x, y = filt2(x, g)[:, 0::2, 0::2][:, :h, :w], filt2(y, g)[:, 0::2, 0::2][:, :h, :w]
-        mu1, mu2 = filt2(x, g), filt2(y, g)
-        s1 = np.maximum(filt2(x * x, g) - mu1 * mu1, 0.0)
-        s2 = np.maximum(filt2(y * y, g) - mu2 * mu2, 0.0)
-        s12 = filt2(x * y, g) - mu1 * mu2
+            x, y = filt2(x, g, mutant)[:, first::2, first::2][:, :h, :w], filt2(y, g, mutant)[:, first::2, first::2][:, :h, :w]
+        mu1, mu2 = filt2(x, g, mutant), filt2(y, g, mutant)
+        s1 = np.maximum(filt2(x * x, g, mutant) - mu1 * mu1, 0.0)
+        s2 = np.maximum(filt2(y * y, g, mutant) - mu2 * mu2, 0.0)
+        s12 = filt2(x * y, g, mutant) - mu1 * mu2
+        raw1 = s1
         gain = s12 / (s1 + EPS)
         sv = s2 - gain * s12
         c1 = s1 < EPS
@@ -118,6 +128,7 @@ def vif(ref: np.ndarray, dis: np.ndarray, counts=None) -> np.ndarray:
         c3 = gain < 0.0
         sv, gain = np.where(c3, s2, sv), np.where(c3, 0.0, gain)
         sv = np.maximum(sv, EPS)
+        unclamped = gain
         gain = np.minimum(gain, GAIN_LIMIT)
         big = s1 >= NSQ
         safe = np.where(big, s1, NSQ)
@@ -127,34 +138,43 @@ def vif(ref: np.ndarray, dis: np.ndarray, counts=None) -> np.ndarray:
             for name, c in (("s1_below_eps", c1), ("s2_below_eps", c2), ("gain_negative", c3), ("log_term", big), ("flat_term", ~big),
                             ("low_term", ~big & ~c1)):
                 counts[name][s] += int(c.sum())
+            counts["sv_floored"][s] += int((sv == EPS).sum())
+            counts["nsq_margin"][s] = min(counts["nsq_margin"][s], float((np.abs(raw1 - NSQ) / NSQ).min()))
+            counts["max_gain_log"][s] = max(counts["max_gain_log"][s], float(np.where(big, unclamped, 0.0).max()))
+        if mutant == "vif_tile_row_more" and x.shape[1] % TILE_H:           # the ragged tile's guard one row late: row h is the mirror's
+            rows = reflect(np.arange(x.shape[1] + 1), x.shape[1])
+            num, den = num[:, rows], den[:, rows]
         n, d = num.sum(axis=(1, 2)), den.sum(axis=(1, 2))
         out[:, s] = np.where(d == 0.0, 1.0, n / np.where(d == 0.0, 1.0, d))
     return out
 
 
 # ----------------------------------------------------------------------------- motion
-def motion(ref: np.ndarray, prev=None, nxt=None):
+def motion(ref: np.ndarray, prev=None, nxt=None, mutant=None):
     """-> (motion [F], motion2 [F]).  prev / nxt: the u8 [H,W] plane before the first / after the last frame."""
     x = planes(ref)
-    b = filt2(x, blur5())
+    b = filt2(x, blur5(), mutant)
     m = np.zeros(x.shape[0], np.float64)
     m[1:] = np.abs(b[1:] - b[:-1]).mean(axis=(1, 2))
     if prev is not None:
-        m[0] = np.abs(b[0] - filt2(planes(prev[None]), blur5())[0]).mean()
+        m[0] = np.abs(b[0] - filt2(planes(prev[None]), blur5(), mutant)[0]).mean()
     after = m[1:].tolist()
     if nxt is not None:
-        after.append(float(np.abs(filt2(planes(nxt[None]), blur5())[0] - b[-1]).mean()))
+        after.append(float(np.abs(filt2(planes(nxt[None]), blur5(), mutant)[0] - b[-1]).mean()))
     m2 = m.copy()
     m2[:len(after)] = np.minimum(m[:len(after)], np.asarray(after))
+    if mutant == "motion2_before":
+        m2 = m.copy()
+        m2[1:] = np.minimum(m[1:], m[:-1])
     return m, m2
 
 
 # ----------------------------------------------------------------------------- ADM
-def dwt(x: np.ndarray):
+def dwt(x: np.ndarray, mutant=None):
     """One db2 step: (a, h, v, d), (vertical, horizontal) = (lo, lo), (hi, lo), (lo, hi), (hi, hi)."""
     lo, hi = db2()
-    vl, vh = dwt_axis(x, lo, -2), dwt_axis(x, hi, -2)
-    return dwt_axis(vl, lo, -1), dwt_axis(vh, lo, -1), dwt_axis(vl, hi, -1), dwt_axis(vh, hi, -1)
+    vl, vh = dwt_axis(x, lo, -2, mutant), dwt_axis(x, hi, -2, mutant)
+    return dwt_axis(vl, lo, -1, mutant), dwt_axis(vh, lo, -1, mutant), dwt_axis(vl, hi, -1, mutant), dwt_axis(vh, hi, -1, mutant)
 
 
 def clamp_shift(x: np.ndarray, dy: int, dx: int) -> np.ndarray:
@@ -162,20 +182,22 @@ def clamp_shift(x: np.ndarray, dy: int, dx: int) -> np.ndarray:
     return x[..., np.clip(np.arange(h) + dy, 0, h - 1), :][..., np.clip(np.arange(w) + dx, 0, w - 1)]
 
 
-def adm(ref: np.ndarray, dis: np.ndarray, counts=None) -> np.ndarray:
+def adm(ref: np.ndarray, dis: np.ndarray, counts=None, mutant=None) -> np.ndarray:
     """[F,H,W] u8 x2 -> adm2 [F]."""
     x, y = planes(ref), planes(dis)
     num = np.zeros(x.shape[0], np.float64)
     den = np.zeros(x.shape[0], np.float64)
     for s in range(4):
-        x, oh, ov, od = dwt(x)
-        y, th, tv, td = dwt(y)
+        x, oh, ov, od = dwt(x, mutant)
+        y, th, tv, td = dwt(y, mutant)
         dp = oh * th + ov * tv
         om, tm = oh * oh + ov * ov, th * th + tv * tv
         flag = (dp >= 0.0) & (dp * dp >= COS2 * om * tm)
         if counts is not None:
             counts["adm_flag_set"][s] += int(flag.sum())
             counts["adm_flag_clear"][s] += int((~flag).sum())
+            counts["adm_dp_negative"][s] += int((dp < 0.0).sum())
+            counts["adm_o_zero"][s] += int(sum(((o == 0.0) & (t != 0.0)).sum() for o, t in ((oh, th), (ov, tv), (od, td))))
         rf = (1.0 / csf_q(s + 1, 1), 1.0 / csf_q(s + 1, 1), 1.0 / csf_q(s + 1, 2))
         rest, art = [], []
         for o, t in ((oh, th), (ov, tv), (od, td)):
@@ -191,11 +213,16 @@ def adm(ref: np.ndarray, dis: np.ndarray, counts=None) -> np.ndarray:
                 for dx in (-1, 0, 1):
                     term = clamp_shift(a, dy, dx)
                     acc = term if acc is None else acc + term
-            acc = acc + a
+            if mutant != "adm_threshold_no_centre":
+                acc = acc + a
             thr = acc if thr is None else thr + acc
         thr = thr / 30.0
         h, w = oh.shape[-2:]
         left, top = max(0, int(w * 0.1 - 0.5)), max(0, int(h * 0.1 - 0.5))
+        if mutant == "adm_window_floor":
+            left, top = int(w * 0.1), int(h * 0.1)
+        if mutant == "adm_hw_swapped":
+            left, top = max(0, int(h * 0.1 - 0.5)), max(0, int(w * 0.1 - 0.5))
         win = (slice(None), slice(top, h - top), slice(left, w - left))
         floor_term = np.cbrt((w - 2 * left) * (h - 2 * top) / 32.0)
         for b, o in enumerate((oh, ov, od)):
@@ -210,9 +237,16 @@ def adm(ref: np.ndarray, dis: np.ndarray, counts=None) -> np.ndarray:
 def new_counts():
     """Per scale, how many pixels took each way: the three VIF pixel classes - `s1_below_eps` (a flat reference window),
     `low_term` (eps <= s1 < nsq) and `log_term` (s1 >= nsq) - the corrections `s2_below_eps` and `gain_negative`,
-    `flat_term` (= s1_below_eps + low_term), and the two values of the ADM flag."""
-    return {k: [0, 0, 0, 0] for k in ("s1_below_eps", "s2_below_eps", "gain_negative", "log_term", "flat_term", "low_term",
-                                      "adm_flag_set", "adm_flag_clear")}
+    `flat_term` (= s1_below_eps + low_term), and the two values of the ADM flag.  For the edge matrix: `sv_floored` (the
+    `sw` floor held), `adm_dp_negative` (dp < 0), `adm_o_zero` (a reference coefficient exactly 0 under a non-zero
+    distorted one: the 1e-30 quotient is evaluated and clamps), and two figures that are no counts - `nsq_margin`,
+    the smallest |s1 - nsq| / nsq (the one discontinuous branch), and `max_gain_log`, the largest gain in the log term before
+    the clamp to 100."""
+    counts = {k: [0, 0, 0, 0] for k in ("s1_below_eps", "s2_below_eps", "gain_negative", "log_term", "flat_term", "low_term",
+                                        "adm_flag_set", "adm_flag_clear", "sv_floored", "adm_dp_negative", "adm_o_zero")}
+    counts["nsq_margin"] = [math.inf] * 4
+    counts["max_gain_log"] = [0.0] * 4
+    return counts
 
 
 def luma(frames: np.ndarray, order: str = "bgr", masks=None, invert: bool = False, rect=None) -> np.ndarray:
@@ -238,16 +272,22 @@ def branch_pair(h: int = 64, w: int = 64):
     return ref, dis
 
 
-def features(ref: np.ndarray, dis: np.ndarray, prev=None, nxt=None, counts=None) -> np.ndarray:
+def features(ref: np.ndarray, dis: np.ndarray, prev=None, nxt=None, counts=None, mutant=None) -> np.ndarray:
     """[F,H,W] u8 x2 -> [F,6] = adm2, motion2, vif_scale0..3."""
+    if mutant is not None and mutant not in MUTANTS:
+        raise ValueError(f"vmaf: unknown mutant {mutant!r}")
     ref, dis = np.asarray(ref), np.asarray(dis)
     if ref.shape != dis.shape:
         raise ValueError("vmaf: the two clips differ in shape")
     planes(ref), planes(dis)
     out = np.empty((ref.shape[0], 6), np.float64)
-    out[:, 0] = adm(ref, dis, counts)
-    out[:, 1] = motion(ref, prev, nxt)[1]
-    out[:, 2:] = vif(ref, dis, counts)
+    pr, pd = ref, dis
+    if mutant == "pass2_from_0":                  # a later pass reads the frames of the first: ref + f0 * size lost its f0
+        at = np.arange(ref.shape[0]) % PASS_FRAMES
+        pr, pd = ref[at], dis[at]
+    out[:, 0] = adm(pr, pd, counts, mutant)
+    out[:, 1] = motion(ref, prev, nxt, mutant)[1]
+    out[:, 2:] = vif(pr, pd, counts, mutant)
     return out
 
 
