@@ -50,5 +50,6 @@ from .restore import (get_realesrgan_upsample_fn, get_realesrgan_upsampler, rest
                       restore_frames_realesrgan_device, restore_with_realesrgan_naive)
 from .drivers import restore_downsampled_with_realesrgan  # noqa: F401
 from .weights import RRDBNetConfig, load_realesrgan_state_dict  # noqa: F401
+from .weights import SRVGGConfig, dni_state_dicts, load_srvgg_state_dict  # noqa: F401
 
 __version__ = "0.1.0"

@@ -124,6 +124,10 @@ SIGNATURES = {
     "elvis_rrdb_pack_weights": [vp, i32, i32, i32, i32, vp],
     "elvis_rrdb_conv3x3": [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, i32, vp],
     "elvis_rrdb_input_u8": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "elvis_srvgg_packed_weight_bytes": [i32, i32],
+    "elvis_srvgg_pack_weights": [vp, i32, i32, i32, i32, vp],
+    "elvis_srvgg_conv3x3": [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "elvis_srvgg_tail": [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
@@ -162,6 +166,7 @@ def lib() -> C.CDLL:
         handle.elvis_inpaint_workspace_bytes.restype = C.c_size_t
         handle.elvis_lpips_distance_workspace_bytes.restype = C.c_size_t
         handle.elvis_rrdb_packed_weight_bytes.restype = C.c_size_t
+        handle.elvis_srvgg_packed_weight_bytes.restype = C.c_size_t
         handle.elvis_vmaf_workspace_bytes.restype = C.c_size_t
         handle.elvis_fvmd_pyramid_bytes.restype = C.c_size_t
         handle.elvis_fvmd_gram_workspace_bytes.restype = C.c_size_t

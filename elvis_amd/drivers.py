@@ -2,7 +2,7 @@
 (elvis.py:4722, 4794) with the MI355X restorers in the model slots.
 
   restore_downsampled_with_sinsr   <- restore_downsampled_with_realesrgan  (elvis.py:2685-2769)
-  restore_downsampled_with_realesrgan  <- the same function, with the network the reference runs there (RRDBNet)
+  restore_downsampled_with_realesrgan  <- the same function, with the networks the reference runs there (RRDBNet, SRVGGNetCompact)
   restore_blur_adaptive            <- restore_with_instantir_adaptive      (elvis.py:3000-3160)
   restore_dct_adaptive             -  the DCT slot the reference never wrote, given the
                                       Blur driver's shape
@@ -409,17 +409,17 @@ def restore_downsampled_with_realesrgan(
     _shard_fn: Optional[ShardFn] = None,
 ) -> None:
     """Adaptive Real-ESRGAN restoration over a directory of frames: the reference's function of this name
-    (elvis.py:2685-2769) with its own network, RRDBNet, in the model slot (`restore.restore_frames_realesrgan`, which
-    lists the departures: no fp32, no pre_pad, no denoise_strength, `tile` / `tile_pad` ignored).  `model_path` is the
-    checkpoint file (e.g. "RealESRGAN_x4plus.pth"); without it the weights are seeded and synthetic.
+    (elvis.py:2685-2769) with its own networks, RRDBNet or SRVGGNetCompact by `model_name`, in the model slot
+    (`restore.restore_frames_realesrgan`, which lists the departures: no fp32, no pre_pad, `tile` / `tile_pad` ignored;
+    `denoise_strength` is honoured for `realesr-general-x4v3` and refused elsewhere).  `model_path` is the checkpoint
+    file (e.g. "RealESRGAN_x4plus.pth"; for `denoise_strength != 1` a pair of files, or one with
+    `realesr-general-wdn-x4v3.pth` beside it); without it the weights are seeded and synthetic.
     `parallel_chunk_length` / `per_device_workers` are accepted and ignored, as in the reference (elvis.py:2698-2699)."""
     _ = (parallel_chunk_length, per_device_workers)
     _check_png_io(png_writer, png_reader)
     if _shard_fn is None:
         from .restore import _check_realesrgan_args
-        from .weights import realesrgan_config
-        _check_realesrgan_args(denoise_strength, pre_pad, fp32)
-        realesrgan_config(model_name)
+        _check_realesrgan_args(denoise_strength, pre_pad, fp32, model_name)
     kw = dict(model_name=model_name, denoise_strength=denoise_strength, tile=tile, tile_pad=tile_pad, pre_pad=pre_pad,
               fp32=fp32, model_path=model_path, schedule=schedule)
     _restore_downsampled(_realesrgan_clip_shard, kw, input_frames_dir, output_frames_dir, downscale_maps, block_size, devices,

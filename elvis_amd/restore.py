@@ -12,6 +12,7 @@ Model handles are process-global, cached per (device, params) under a lock like
 """
 from __future__ import annotations
 
+import math
 import threading
 from typing import Callable, Dict, List, Optional, Sequence
 
@@ -325,36 +326,112 @@ def restore_with_sinsr_naive(frames: List[np.ndarray], device="cuda", seed: int 
         return frames_to_host(out)
 
 
-# ----------------------------------------------------------------------------- Real-ESRGAN (RRDBNet) in the Downsample slot
-def _check_realesrgan_args(denoise_strength, pre_pad, fp32) -> None:
-    """The departures from the reference call: each is refused, none is silently ignored."""
+# ----------------------------------------------------------------------------- Real-ESRGAN in the Downsample slot
+def _check_realesrgan_args(denoise_strength, pre_pad, fp32, model_name=None):
+    """The departures from the reference call: each is refused, none is silently ignored.  With `model_name` the name is
+    checked too and its configuration returned (`weights.RRDBNetConfig` or `weights.SRVGGConfig`); `denoise_strength`
+    other than 1 (`math.isclose`, as elvis.py:2472) is taken for `realesr-general-x4v3` alone, the one model the
+    reference applies it to."""
+    from .weights import REALESRGAN_SRVGG_MODELS, SRVGG_DNI_MODEL, realesrgan_config, srvgg_config
     if fp32:
         raise ValueError("Real-ESRGAN: fp32=True is not built; the network runs in f16 with fp32 accumulation "
                          "(the reference's GPU precision, half=True)")
     if int(pre_pad) != 0:
         raise ValueError(f"Real-ESRGAN: pre_pad={pre_pad} is not built; only pre_pad=0")
-    if float(denoise_strength) != 1.0:
-        raise ValueError(f"Real-ESRGAN: denoise_strength={denoise_strength} applies to realesr-general-x4v3 only "
-                         "(an SRVGG model, not built); pass 1.0")
+    name = None if model_name is None else str(model_name).split(".")[0]
+    s = float(denoise_strength)
+    if not math.isclose(s, 1.0):
+        if name != SRVGG_DNI_MODEL:
+            raise ValueError(f"Real-ESRGAN: denoise_strength={denoise_strength} applies to {SRVGG_DNI_MODEL} only "
+                             f"(elvis.py:2472-2478); pass 1.0 for '{name or 'this model'}'")
+        if not 0.0 <= s <= 1.0:
+            raise ValueError(f"Real-ESRGAN: denoise_strength={denoise_strength} is outside [0, 1]")
+    if name is None:
+        return None
+    return srvgg_config(name) if name in REALESRGAN_SRVGG_MODELS else realesrgan_config(name)
+
+
+def _pair(v):
+    """`v` as a (first, second) pair if it is a list or tuple of two, else None."""
+    return tuple(v) if isinstance(v, (list, tuple)) and len(v) == 2 else None
+
+
+def _srvgg_dni_sources(model_path, state_dict):
+    """The two weight sets `denoise_strength` blends (elvis.py:2472-2478), as (a, b) of state dicts or paths: a pair
+    given as `state_dict` or as `model_path`, or one path with `realesr-general-wdn-x4v3.pth` looked up beside it;
+    (None, None) without weights.  Runs before any GPU is needed."""
+    import os
+    from .weights import SRVGG_DNI_PARTNER
+    if state_dict is not None:
+        pair = _pair(state_dict)
+        if pair is None:
+            raise ValueError("Real-ESRGAN: denoise_strength != 1 blends two weight sets; pass `state_dict` as a pair "
+                             "(realesr-general-x4v3, realesr-general-wdn-x4v3)")
+        return pair
+    if model_path is None:
+        return None, None
+    pair = _pair(model_path)
+    if pair is not None:
+        return os.fspath(pair[0]), os.fspath(pair[1])
+    first = os.fspath(model_path)
+    second = os.path.join(os.path.dirname(first), SRVGG_DNI_PARTNER + ".pth")
+    if not os.path.isfile(second):
+        raise RuntimeError("Unable to locate realesr-general-wdn-x4v3 weights for DNI upsampling.")   # elvis.py:2476
+    return first, second
 
 
 def get_realesrgan_upsampler(device, *, model_name: str = "RealESRGAN_x4plus", denoise_strength: float = 1.0,
                              tile: int = 0, tile_pad: int = 10, pre_pad: int = 0, fp32: bool = False,
                              model_path=None, state_dict=None):
-    """Get or create the cached RRDBNet runtime for `device` (elvis.py:2611-2637: thread-safe, one per device, model
-    and weights, never freed).  `model_name` picks the architecture from the reference's table (`weights.realesrgan_config`);
-    the weights are `state_dict` (a state dict or checkpoint dict), else the checkpoint file `model_path`, else SEEDED
-    SYNTHETIC ones - nothing is downloaded.  `tile` and `tile_pad` are accepted and ignored: whole frames fit.
-    `fp32=True`, `pre_pad != 0` and `denoise_strength != 1` are a ValueError."""
-    from .realesrgan import RRDBNetModel
-    from .weights import realesrgan_config
-    _check_realesrgan_args(denoise_strength, pre_pad, fp32)
+    """Get or create the cached Real-ESRGAN runtime for `device` (elvis.py:2611-2637: thread-safe, one per device,
+    model, denoise strength and weights, never freed).  `model_name` picks the architecture from the reference's table
+    (elvis.py:2415-2441): the four RRDBNet names give a `realesrgan.RRDBNetModel`, `realesr-animevideov3` and
+    `realesr-general-x4v3` a `srvgg.SRVGGModel`.  The weights are `state_dict` (a state dict or checkpoint dict), else
+    the checkpoint file `model_path`, else SEEDED SYNTHETIC ones - nothing is downloaded.
+
+    `denoise_strength` is honoured for `realesr-general-x4v3`, as in the reference (elvis.py:2472-2478): unless it is
+    1.0 the weights are `weights.dni_state_dicts(a, b, denoise_strength)` of two sets - `state_dict` as a pair of dicts,
+    `model_path` as a pair of paths, or one path with `realesr-general-wdn-x4v3.pth` beside it (absent: the reference's
+    RuntimeError); without weights, the synthetic sets of seeds 0 and 1.  For every other model a value other than 1 is
+    a ValueError.  `tile` and `tile_pad` are accepted and ignored: whole frames fit.  `fp32=True` and `pre_pad != 0`
+    are a ValueError."""
+    from .weights import SRVGGConfig
+    cfg = _check_realesrgan_args(denoise_strength, pre_pad, fp32, model_name)
     _ = (tile, tile_pad)
-    cfg = realesrgan_config(model_name)
-    source = state_dict if state_dict is not None else model_path
-    # a caller's dict is keyed by its identity, a checkpoint file by its path
-    path = str(model_path) if state_dict is None and model_path is not None else None
-    return _cached_model("Real-ESRGAN", device, (cfg, path), state_dict, lambda dev: RRDBNetModel(cfg, source, dev))
+    if not isinstance(cfg, SRVGGConfig):
+        from .realesrgan import RRDBNetModel
+        source = state_dict if state_dict is not None else model_path
+        # a caller's dict is keyed by its identity, a checkpoint file by its path
+        path = str(model_path) if state_dict is None and model_path is not None else None
+        return _cached_model("Real-ESRGAN", device, (cfg, path), state_dict, lambda dev: RRDBNetModel(cfg, source, dev))
+    from .srvgg import SRVGGModel
+    s = float(denoise_strength)
+    if math.isclose(s, 1.0):
+        # no blend: of a pair, the named model's own set is the first
+        if _pair(state_dict) is not None:
+            state_dict = state_dict[0]
+        if _pair(model_path) is not None:
+            model_path = model_path[0]
+        source = state_dict if state_dict is not None else model_path
+        path = str(model_path) if state_dict is None and model_path is not None else None
+        return _cached_model("Real-ESRGAN", device, (cfg, 1.0, path), state_dict, lambda dev: SRVGGModel(cfg, source, dev))
+    a, b = _srvgg_dni_sources(model_path, state_dict)
+
+    def make(dev):
+        from .weights import dni_state_dicts, load_srvgg_state_dict, make_srvgg_weights
+        if a is None:
+            sa, sb = make_srvgg_weights(cfg, 0), make_srvgg_weights(cfg, 1)
+        else:
+            sa, sb = load_srvgg_state_dict(a, cfg), load_srvgg_state_dict(b, cfg)
+        model = SRVGGModel(cfg, dni_state_dicts(sa, sb, s), dev)
+        model.dni_sources = (a, b)     # callers' dicts are keyed by identity: the cached model keeps them alive
+        return model
+
+    if state_dict is not None:
+        ident = (id(a), id(b))
+    else:
+        ident = None if a is None else (str(a), str(b))
+    return _cached_model("Real-ESRGAN", device, (cfg, s, ident), None, make)
 
 
 def _realesrgan_up(model, cur: torch.Tensor, swap_rb: bool = True) -> torch.Tensor:
@@ -429,9 +506,9 @@ def restore_frames_realesrgan(frames: List[np.ndarray], downscale_maps: np.ndarr
                               model_name: str = "RealESRGAN_x4plus", denoise_strength: float = 1.0, tile: int = 0,
                               tile_pad: int = 10, pre_pad: int = 0, fp32: bool = False, model_path=None, state_dict=None,
                               schedule: str = "staged", **_ignored) -> List[np.ndarray]:
-    """The reference's `restore_frames_realesrgan` (elvis.py:2640-2682) with the network it runs there, RRDBNet, on the
-    device: BGR uint8 frames + per-block log2 downscale maps -> restored frames.  Host to host around
-    `restore_frames_realesrgan_device`.
+    """The reference's `restore_frames_realesrgan` (elvis.py:2640-2682) with the networks it runs there - RRDBNet, or
+    SRVGGNetCompact for `realesr-animevideov3` / `realesr-general-x4v3` (x4 models) - on the device: BGR uint8 frames +
+    per-block log2 downscale maps -> restored frames.  Host to host around `restore_frames_realesrgan_device`.
 
     Everything goes through `upscale_adaptive_device`.  An x2 model (`RealESRGAN_x2plus`) runs it with `sr_scale=2`: the
     reference's loop (elvis.py:2570-2598) line by line, no resize anywhere.  An x4 model runs it with `sr_scale=4`:
@@ -440,8 +517,9 @@ def restore_frames_realesrgan(frames: List[np.ndarray], downscale_maps: np.ndarr
     from the /4 level per frame, whatever the map's maximum (the benchmark path of the SinSR slot).
 
     Weights: `state_dict`, else the checkpoint file `model_path` (e.g. "RealESRGAN_x4plus.pth"), else seeded synthetic
-    ones; nothing is downloaded.  `tile` / `tile_pad` are accepted and ignored (whole frames fit); `fp32=True`,
-    `pre_pad != 0` and `denoise_strength != 1` are a ValueError.  A runtime failure is
+    ones; nothing is downloaded.  `tile` / `tile_pad` are accepted and ignored (whole frames fit); `fp32=True` and
+    `pre_pad != 0` are a ValueError.  `denoise_strength != 1` blends two weight sets for `realesr-general-x4v3`
+    (`get_realesrgan_upsampler`) and is a ValueError for every other model.  A runtime failure is
     `RuntimeError("Real-ESRGAN failed on <device>: ...")` (elvis.py:2517-2519)."""
     kw = dict(model_name=model_name, denoise_strength=denoise_strength, tile=tile, tile_pad=tile_pad, pre_pad=pre_pad,
               fp32=fp32, model_path=model_path, state_dict=state_dict)

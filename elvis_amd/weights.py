@@ -389,7 +389,7 @@ REALESRGAN_MODELS = {
     "RealESRGAN_x4plus_anime_6B": (6, 4),
     "RealESRGAN_x2plus": (23, 2),
 }
-# the reference's SRVGGNetCompact rows: another network, not built here
+# the reference's SRVGGNetCompact rows (elvis.py:2431-2441): another network, `srvgg_config` and elvis_amd/srvgg.py
 REALESRGAN_SRVGG_MODELS = ("realesr-animevideov3", "realesr-general-x4v3")
 
 
@@ -398,8 +398,8 @@ def realesrgan_config(model_name: str) -> RRDBNetConfig:
     (`model_name.split('.')[0]`).  The two SRVGG names and unknown names are a ValueError."""
     name = str(model_name).split(".")[0]
     if name in REALESRGAN_SRVGG_MODELS:
-        raise ValueError(f"Real-ESRGAN model '{name}' is an SRVGGNetCompact; only the RRDBNet models "
-                         f"{tuple(REALESRGAN_MODELS)} are built")
+        raise ValueError(f"Real-ESRGAN model '{name}' is an SRVGGNetCompact, not an RRDBNet: its configuration is "
+                         f"`srvgg_config('{name}')`; the RRDBNet models are {tuple(REALESRGAN_MODELS)}")
     if name not in REALESRGAN_MODELS:
         raise ValueError(f"Unknown Real-ESRGAN model: {name}")
     num_block, scale = REALESRGAN_MODELS[name]
@@ -445,13 +445,9 @@ def _rrdbnet_config_of(sd) -> RRDBNetConfig:
     return RRDBNetConfig(scale=4 if cin == 3 else 2, num_block=max(blocks) + 1)
 
 
-def load_realesrgan_state_dict(path_or_dict, cfg: "RRDBNetConfig | None" = None) -> Dict[str, torch.Tensor]:
-    """A Real-ESRGAN RRDBNet checkpoint as a checked dict of fp32 CPU tensors.  A path is read with
-    `torch.load(path, map_location="cpu", weights_only=True)`; a checkpoint dict is unwrapped as RealESRGANer does
-    (`params_ema` if present, else `params`, else the dict itself).  Keys: `conv_first`, `body.{i}.rdb{1,2,3}.conv{1..5}`,
-    `conv_body`, `conv_up1`, `conv_up2`, `conv_hr`, `conv_last`, each with `.weight` and `.bias`.  Without `cfg` the block
-    count and the scale are read from the keys.  A missing key, an extra key or a wrong shape is a ValueError that names
-    the key.  Nothing is ever downloaded."""
+def _unwrap_checkpoint(path_or_dict) -> dict:
+    """A checkpoint path or dict as the bare state dict: `torch.load(path, map_location="cpu", weights_only=True)`, then
+    unwrapped as RealESRGANer does (`params_ema` if present, else `params`, else the dict itself)."""
     import os
     if isinstance(path_or_dict, (str, bytes, os.PathLike)):
         sd = torch.load(os.fspath(path_or_dict), map_location="cpu", weights_only=True)
@@ -461,14 +457,12 @@ def load_realesrgan_state_dict(path_or_dict, cfg: "RRDBNetConfig | None" = None)
         raise ValueError(f"Real-ESRGAN checkpoint: expected a dict, got {type(sd).__name__}")
     for wrap in ("params_ema", "params"):
         if wrap in sd and isinstance(sd[wrap], dict):
-            sd = sd[wrap]
-            break
-    if cfg is None:
-        cfg = _rrdbnet_config_of(sd)
-    expect = {}
-    for key, cout, cin in rrdbnet_layout(cfg):
-        expect[key + ".weight"] = (cout, cin, 3, 3)
-        expect[key + ".bias"] = (cout,)
+            return sd[wrap]
+    return sd
+
+
+def _checked_state_dict(sd: dict, expect: Dict[str, tuple]) -> Dict[str, torch.Tensor]:
+    """`sd` as fp32 CPU tensors, with exactly the keys and shapes of `expect`; anything else is a named ValueError."""
     out: Dict[str, torch.Tensor] = {}
     for key, shape in expect.items():
         if key not in sd:
@@ -482,3 +476,126 @@ def load_realesrgan_state_dict(path_or_dict, cfg: "RRDBNetConfig | None" = None)
         if key not in expect:
             raise ValueError(f"Real-ESRGAN state dict: unexpected key '{key}'")
     return out
+
+
+def load_realesrgan_state_dict(path_or_dict, cfg: "RRDBNetConfig | None" = None) -> Dict[str, torch.Tensor]:
+    """A Real-ESRGAN RRDBNet checkpoint as a checked dict of fp32 CPU tensors.  A path is read with
+    `torch.load(path, map_location="cpu", weights_only=True)`; a checkpoint dict is unwrapped as RealESRGANer does
+    (`params_ema` if present, else `params`, else the dict itself).  Keys: `conv_first`, `body.{i}.rdb{1,2,3}.conv{1..5}`,
+    `conv_body`, `conv_up1`, `conv_up2`, `conv_hr`, `conv_last`, each with `.weight` and `.bias`.  Without `cfg` the block
+    count and the scale are read from the keys.  A missing key, an extra key or a wrong shape is a ValueError that names
+    the key.  Nothing is ever downloaded."""
+    sd = _unwrap_checkpoint(path_or_dict)
+    if cfg is None:
+        cfg = _rrdbnet_config_of(sd)
+    expect = {}
+    for key, cout, cin in rrdbnet_layout(cfg):
+        expect[key + ".weight"] = (cout, cin, 3, 3)
+        expect[key + ".bias"] = (cout,)
+    return _checked_state_dict(sd, expect)
+
+
+# ----------------------------------------------------------------------------- Real-ESRGAN (SRVGGNetCompact)
+@dataclass(frozen=True)
+class SRVGGConfig:
+    """`SRVGGNetCompact(3, 3, num_feat, num_conv, upscale, act_type='prelu')` as `_instantiate_realesrgan_upsampler`
+    builds it (elvis.py:2431-2441).  The kernels are written for 64 features and upscale 4 (a 48-channel tail)."""
+    num_conv: int = 32
+    num_feat: int = 64
+    upscale: int = 4
+
+    def __post_init__(self):
+        if self.num_feat != 64 or self.upscale != 4:
+            raise ValueError(f"SRVGGConfig: only num_feat=64, upscale=4 are built, got {self.num_feat}, {self.upscale}")
+        if not isinstance(self.num_conv, int) or self.num_conv < 1:
+            raise ValueError(f"SRVGGConfig: num_conv must be a positive integer, got {self.num_conv!r}")
+
+    @property
+    def scale(self) -> int:
+        return self.upscale
+
+
+# model_name -> num_conv: the SRVGGNetCompact rows of the reference's table (elvis.py:2431-2441)
+SRVGG_MODELS = {"realesr-animevideov3": 16, "realesr-general-x4v3": 32}
+# the only model `denoise_strength` applies to, and the checkpoint it is blended with (elvis.py:2472-2478)
+SRVGG_DNI_MODEL = "realesr-general-x4v3"
+SRVGG_DNI_PARTNER = "realesr-general-wdn-x4v3"
+
+
+def srvgg_config(model_name: str) -> SRVGGConfig:
+    """The SRVGGNetCompact configuration of a reference model name, cut at the first '.' as the reference does."""
+    name = str(model_name).split(".")[0]
+    if name not in SRVGG_MODELS:
+        raise ValueError(f"Unknown Real-ESRGAN SRVGG model: {name} (the SRVGGNetCompact models are {tuple(SRVGG_MODELS)})")
+    return SRVGGConfig(num_conv=SRVGG_MODELS[name])
+
+
+def srvgg_layout(cfg: SRVGGConfig):
+    """[(state-dict key, shape)] of every tensor of the network, in forward order: `body.{2i}.weight` [cout,cin,3,3] and
+    `body.{2i}.bias` [cout] for the convs i = 0..num_conv+1 (3 -> 64, num_conv times 64 -> 64, 64 -> 3 * upscale^2) and
+    `body.{2i+1}.weight` [64], the PReLU slopes, after every conv but the last."""
+    f, last = cfg.num_feat, cfg.num_conv + 1
+    out = []
+    for i in range(last + 1):
+        cout, cin = (3 * cfg.upscale ** 2 if i == last else f), (3 if i == 0 else f)
+        out.append((f"body.{2 * i}.weight", (cout, cin, 3, 3)))
+        out.append((f"body.{2 * i}.bias", (cout,)))
+        if i != last:
+            out.append((f"body.{2 * i + 1}.weight", (f,)))
+    return out
+
+
+def make_srvgg_weights(cfg: SRVGGConfig = SRVGGConfig(), seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded SYNTHETIC weights of the SRVGG models: they exercise the network, they restore nothing; the trained
+    checkpoints go through `load_srvgg_state_dict`.  PReLU slopes are 0.2 + 0.1 N(0, 1) per channel with every 16th
+    channel from 7 at -0.25 and every 16th from 11 at 1.25, so negative slopes and slopes above 1 occur in every layer.
+    A conv is normal with std sqrt(1 / (9 cin m)), m the mean square its input keeps of a unit-variance pre-activation
+    (1/3 for the image in [0, 1]; mean((1 + a^2) / 2) after a PReLU with slopes a), so the second moment is carried
+    through all 33 layers; the last conv has a tenth of that (a residual on the nearest-4x base).  Biases are
+    0.05 N(0, 1), the last 0.02 N(0, 1)."""
+    g = torch.Generator().manual_seed(int(seed) + 404)
+    sd: Dict[str, torch.Tensor] = {}
+    m, last = 1.0 / 3.0, cfg.num_conv + 1
+    for key, shape in srvgg_layout(cfg):
+        idx, kind = int(key.split(".")[1]), key.split(".")[2]
+        if len(shape) == 4:
+            std = math.sqrt(1.0 / (9 * shape[1] * m)) * (0.1 if idx == 2 * last else 1.0)
+            sd[key] = torch.randn(shape, generator=g, dtype=torch.float32) * std
+        elif kind == "bias":
+            sd[key] = torch.randn(shape, generator=g, dtype=torch.float32) * (0.02 if idx == 2 * last else 0.05)
+        else:
+            a = 0.2 + 0.1 * torch.randn(shape, generator=g, dtype=torch.float32)
+            a[7::16], a[11::16] = -0.25, 1.25
+            sd[key] = a
+            m = float(((1.0 + a.double() ** 2) / 2.0).mean())
+    return sd
+
+
+def _srvgg_config_of(sd) -> SRVGGConfig:
+    idx = {int(k.split(".")[1]) for k in sd if k.startswith("body.") and k.split(".")[1].isdigit()}
+    if not idx or max(idx) < 4 or max(idx) % 2:
+        raise ValueError("Real-ESRGAN state dict: no 'body.{2i}.weight' keys up to an even index - not an SRVGGNetCompact checkpoint")
+    return SRVGGConfig(num_conv=(max(idx) - 2) // 2)
+
+
+def load_srvgg_state_dict(path_or_dict, cfg: "SRVGGConfig | None" = None) -> Dict[str, torch.Tensor]:
+    """A Real-ESRGAN SRVGGNetCompact checkpoint as a checked dict of fp32 CPU tensors: read and unwrapped as
+    `load_realesrgan_state_dict` does, keys and shapes as `srvgg_layout` lists them.  Without `cfg`, `num_conv` is read
+    from the keys (the last conv is `body.{2 num_conv + 2}`).  A missing key, an extra key or a wrong shape is a
+    ValueError that names the key.  Nothing is ever downloaded."""
+    sd = _unwrap_checkpoint(path_or_dict)
+    if cfg is None:
+        cfg = _srvgg_config_of(sd)
+    return _checked_state_dict(sd, dict(srvgg_layout(cfg)))
+
+
+def dni_state_dicts(a: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor], denoise_strength: float) -> Dict[str, torch.Tensor]:
+    """Deep network interpolation as RealESRGANer.dni does it for `dni_weight = [s, 1 - s]` (elvis.py:2472-2478): key by
+    key over two unwrapped state dicts, `s * a[k] + (1 - s) * b[k]` in fp32.  `a` is the named model, `b` the wdn one."""
+    s = float(denoise_strength)
+    if not 0.0 <= s <= 1.0:
+        raise ValueError(f"dni_state_dicts: denoise_strength={denoise_strength} is outside [0, 1]")
+    if set(a) != set(b):
+        odd = sorted(set(a) ^ set(b))
+        raise ValueError(f"dni_state_dicts: the two state dicts differ in their keys: {odd[:4]}")
+    return {k: s * a[k].to(torch.float32) + (1 - s) * b[k].to(torch.float32) for k in a}

@@ -841,6 +841,45 @@ int elvis_rrdb_conv3x3(const void* x, int x_pitch, const void* w_packed, const f
  * (index h reads h - 2, F.pad(..., 'reflect')) and must then be at least 3.  Channels past 3*s*s are zero. */
 int elvis_rrdb_input_u8(const uint8_t* src, void* dst, int n, int h, int w, int s, int swap_rb, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ Real-ESRGAN / SRVGGNetCompact (srvgg.hip)
+ * The network of `realesr-animevideov3` and `realesr-general-x4v3` (elvis.py:2431-2441), run by RealESRGANer.enhance
+ * (elvis.py:2515): SRVGGNetCompact(3, 3, 64, num_conv, upscale=4, 'prelu') on f16 NHWC tensors.  The first layer reads
+ * the 32-channel buffer elvis_rrdb_input_u8 writes with s = 1. */
+
+/* Bytes of the packed f16 weights of one conv (9 * cin * cout * 2); 0 unless cin is 32 or 64 and cout 48 or 64.
+ * elvis.py:2431-2441 / 2515 */
+size_t elvis_srvgg_packed_weight_bytes(int cin, int cout);
+
+/* Host function, no GPU: fp32 OIHW [cout_real][cin_real][3][3] -> packed f16 [cin/32][tap = ky*3+kx][cout][32]
+ * (round to nearest even), element [kc][tap][co][k] = w[co][32 kc + k][ky][kx]; input channels past cin_real and output
+ * channels past cout_real are zero (the first layer: 3 real inputs in 32).  elvis_rrdb_pack_weights' layout with the
+ * tail's cout = 48 admitted.  elvis.py:2431-2441 / 2515 */
+int elvis_srvgg_pack_weights(const float* w_oihw_host, int cin_real, int cout_real, int cin, int cout, void* packed_host);
+
+/* One body layer (elvis.py:2431-2441 / 2515): 3x3 / stride 1 / pad 1 conv to 64 channels and a per-channel PReLU, f16
+ * in, fp32 accumulate on v_mfma_f32_16x16x32_f16.  x: f16 [n,h,w,x_pitch], channels [0, cin) are read, cin 32 or 64.
+ * w_packed: elvis_srvgg_pack_weights' layout (cout = 64) on the device; bias, slope: fp32 [64].  out: f16
+ * [n,h,w,out_pitch], channels [0, 64) are written and no other byte.  Epilogue in fp32: z = sum + bias;
+ * y = z > 0 ? z : slope[c] * z, stored as f16, round to nearest even.  out may not overlap x.  ELVIS_E_INVALID, before
+ * any launch: an unsupported cin, a pitch that is no multiple of 8 or too small, a null or misaligned pointer (x,
+ * weights, bias, slope 16 bytes; out 8), an out that overlaps x.  Offsets are 64-bit.  n, h or w == 0 does nothing and
+ * succeeds.  elvis_last_launch: "srvgg_conv3x3_kernel<64,prelu>". */
+int elvis_srvgg_conv3x3(const void* x, int x_pitch, const void* w_packed, const float* bias, const float* slope, void* out,
+                        int out_pitch, int n, int h, int w, int cin, elvis_stream_t stream);
+
+/* The last conv with everything after it (elvis.py:2431-2441 / 2515): 3x3 conv 64 -> 48, pixel shuffle by 4 (channel
+ * 16c + 4dy + dx is colour c at (4y + dy, 4x + dx), torch's order), plus the nearest-4x base, then `enhance`'s
+ * quantisation.  x: f16 [n,h,w,x_pitch], channels [0, 64) read; w_packed: elvis_srvgg_pack_weights' layout with
+ * cin = 64, cout = 48; bias: fp32 [48]; base: f16 [n,h,w,base_pitch], channels 0..2 of pixel (y, x) are added to its
+ * 16 output pixels.  y = (sum + bias) + base in fp32.  out_u8 != 0: out is u8 [n,4h,4w,3], byte
+ * c = rint(clamp(y_c, 0, 1) * 255) (half to even); otherwise out is f16 [n,4h,4w,3], y before the clamp.  swap_rb != 0
+ * reverses the channel order on the way out (either mode).  The 48-channel tensor is never stored.  ELVIS_E_INVALID,
+ * before any launch: x_pitch no multiple of 8 or under 64, base_pitch under 3, a null or misaligned pointer (x, weights,
+ * bias 16 bytes; base 2; out 4 for u8, 8 for f16), an out that overlaps x or base.  n, h or w == 0 does nothing and
+ * succeeds.  elvis_last_launch: "srvgg_conv3x3_kernel<48,shuffle_u8>" or "<48,shuffle_f16>". */
+int elvis_srvgg_tail(const void* x, int x_pitch, const void* w_packed, const float* bias, const void* base, int base_pitch,
+                     void* out, int n, int h, int w, int out_u8, int swap_rb, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
