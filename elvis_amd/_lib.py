@@ -120,6 +120,9 @@ SIGNATURES = {
     "elvis_png_gather": [vp, i64, vp, i32, vp, i64, vp, vp],
     "elvis_png_inflate": [vp, i64, vp, vp, i64, vp, vp, i32, vp],
     "elvis_png_unfilter": [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_jpeg_entropy": [vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp, vp],
+    "elvis_jpeg_idct": [vp, i64, vp, i32, vp, vp],
+    "elvis_jpeg_colour": [vp, i64, vp, vp, i32, i32, i32, i32, i32, vp],
     "elvis_rrdb_packed_weight_bytes": [i32, i32],
     "elvis_rrdb_pack_weights": [vp, i32, i32, i32, i32, vp],
     "elvis_rrdb_conv3x3": [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, i32, vp],

@@ -32,7 +32,8 @@ masks; only the host frames of a replaced `_shard_fn` go up once more (`png.save
 ValueError; "device" without a GPU raises.
 
 Every driver also takes `png_reader="pil"` (the default: frameio.load_frame per file) or `"device"`: a worker's frame
-range is then decoded by the GPU (png.load_frames_device) into one resident clip.  The built-in shard functions - v1
+range is then decoded by the GPU (jpeg.load_images_device: PNG and JPEG files, told apart by their first bytes; a
+directory of PNGs is one call of png.load_frames_device) into one resident clip.  The built-in shard functions - v1
 and the model slots' `restore_frames_*_device` alike - take that clip as it is: with both options "device" a worker's
 pixels never visit the host.  A replaced `_shard_fn` gets `frames_to_host` of it.  Same errors as `png_writer`.
 
@@ -68,8 +69,8 @@ PNG_READERS = ("pil", "device")
 def _check_png_io(png_writer, png_reader) -> None:
     """`png_writer=` of the directory drivers: "pil" (frameio.save_frame / save_mask, the default) or "device" (png.py:
     the files are written by the GPU - any PNG reader decodes them to the same pixels, the bytes are not PIL's).
-    `png_reader=`: "pil" (frameio.load_frame, the default) or "device" (png.py: the files are decoded by the GPU into a
-    resident clip - the same pixels)."""
+    `png_reader=`: "pil" (frameio.load_frame, the default) or "device" (png.py, jpeg.py: the PNG and JPEG files are
+    decoded by the GPU into a resident clip - the same pixels)."""
     if png_writer not in PNG_WRITERS:
         raise ValueError(f"png_writer must be one of {PNG_WRITERS}, got {png_writer!r}")
     if png_reader not in PNG_READERS:
@@ -95,8 +96,8 @@ class PngDirSource:
     def load(self, lo: int, hi: int, device):
         paths = [os.path.join(self.in_dir, n) for n in self.names[lo:hi]]
         if self.reader == "device":
-            from .png import load_frames_device
-            return load_frames_device(paths, device)
+            from .jpeg import load_images_device
+            return load_images_device(paths, device)
         return [load_frame(p) for p in paths]
 
 

@@ -802,6 +802,49 @@ int elvis_png_inflate(const uint8_t* streams, int64_t streams_bytes, const int64
 int elvis_png_unfilter(uint8_t* filtered, int64_t stride, uint8_t* frames, uint32_t* status, int n, int h, int w, int bpp,
                        int channels, int order, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ JPEG reader (jpeg_read.hip, jpeg_decode.h)
+ * Baseline JPEG files decoded by the device: every frame loader of the reference takes .jpg / .jpeg beside .png
+ * (elvis.py:147, 193, 238, 549, 1495, 1724, 3033, 4785, 4811).  SOF0 or 8-bit SOF1, Huffman coded, one interleaved
+ * scan, gray or YCbCr with luma sampling 1x1, 2x1 or 2x2.  The host walks the markers, uploads the files as they are and
+ * tells where the entropy-coded segments lie (a file is cut at its RSTn markers); it decodes no compressed byte and
+ * touches no pixel.  The pixels are those of libjpeg-turbo with default settings (slow integer IDCT, fancy upsampling),
+ * bit for bit; tests/_jpeg_ref.py states them.  Three calls per clip and one download of the status words at the end
+ * (the caller synchronises, no entry point does):
+ *   fd       i32 [n, 32], the frame descriptors: 0 components (1 | 3), 1 hmax, 2 vmax, 3 MCUs per row, 4 MCU rows,
+ *            5 blocks of the frame, 6..7 zero; per component c at 8 + 8 c: h, v, first block, first plane byte (64 * first
+ *            block), plane pitch (8 * MCUs per row * h), DC table, AC table, quantisation table (0..3 each).  A single
+ *            component counts as 1x1.  A component's blocks are a row-major grid of whole MCUs; frame f's blocks start
+ *            at block f * stride_blocks of coef, its planes at byte f * stride_blocks * 64 of planes.  A descriptor
+ *            that does not fit stride_blocks is not followed: its segments get status 5, its frame is left unwritten.
+ *   1. elvis_jpeg_entropy: segs i32 [nseg, 5] = (byte offset in files, byte length, first MCU, MCU count, frame), the
+ *      bytes between the markers with fill FFs trimmed; huff u8 [n, 8, 272] = 16 counts and up to 256 values of the DC
+ *      tables 0..3 and the AC tables 0..3; qt u16 [n, 4, 64] in natural order.  Builds the code tables into `tables`
+ *      (n * 8 * ELVIS_JPEG_TABLE_BYTES bytes of work space) and decodes every segment, a lane each (ITU-T T.81 F.2.2; FF 00 is
+ *      one FF, the DC predictors start at 0): coef i16 [n, stride_blocks, 64], dequantised, natural order, stored as
+ *      decoded into blocks that the CALLER HAS ZEROED.  status u32 [nseg, 2] = (code, MCUs done).  Codes: 0 ok, 1 no
+ *      code of up to 16 bits matches, 2 a coefficient index past 63, 3 the bits run out before the segment's MCUs are
+ *      done, 4 a dequantised coefficient outside [-32768, 32767], 5 bad descriptor or span.  The first defect ends a
+ *      segment; bits left over at its end are ignored.  Nothing is read outside a segment's span or written outside
+ *      its frame's blocks.
+ *   2. elvis_jpeg_idct: libjpeg's jidctint.c (CONST_BITS 13, PASS1_BITS 2; columns descaled by 11 bits, rows by 18,
+ *      the range limit's wrap at 10 bits) in 64-bit integers: coef -> planes u8 [n, stride_blocks * 64].
+ *   3. elvis_jpeg_colour: planes -> frames u8 [n, h, w, channels].  Chroma of a 2x1 / 2x2 frame by libjpeg's fancy
+ *      upsampling over the ceil(w / 2) x ceil(h / vmax) samples that count, neighbours replicated at the edges (plain
+ *      replication where that width is at most 2); R = Y + ((91881 Cr + 32768) >> 16), B = Y + ((116130 Cb + 32768) >>
+ *      16), G = Y + ((-22554 Cb - 46802 Cr + 32768) >> 16) with Cb, Cr less 128, clamped.  channels 3 (gray replicated;
+ *      order 0 = RGB, 1 = BGR, swapped in the stores) or 1 (the luma plane).
+ * The same input gives the same bytes, alone or in a batch; no global atomics.
+ * ELVIS_E_INVALID before any launch: a negative count, n above 65535, files_bytes of 2^31 or more, stride_blocks outside
+ * [1, 2^25), h or w outside [1, 65535], channels outside {1, 3}, a bad order, a null pointer, coef not 16-byte or planes
+ * not 8-byte aligned.  n == 0 (nseg == 0) is a no-op. */
+#define ELVIS_JPEG_TABLE_BYTES 1312
+int elvis_jpeg_entropy(const uint8_t* files, int64_t files_bytes, const int32_t* segs, int nseg, const int32_t* fd, int n,
+                       const uint8_t* huff, const uint16_t* qt, void* tables, int16_t* coef, int64_t stride_blocks,
+                       uint32_t* status, elvis_stream_t stream);
+int elvis_jpeg_idct(const int16_t* coef, int64_t stride_blocks, const int32_t* fd, int n, uint8_t* planes, elvis_stream_t stream);
+int elvis_jpeg_colour(const uint8_t* planes, int64_t stride_blocks, const int32_t* fd, uint8_t* frames, int n, int h, int w,
+                      int channels, int order, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ Real-ESRGAN / RRDBNet (rrdb.hip)
  * The network behind RealESRGANer.enhance (elvis.py:2515): RRDBNet(3, 3, 64, num_block, 32, scale) on f16 NHWC tensors.
  * Channel counts are the padded ones the kernel runs: cin in {32, 64, 96, 128, 160, 192}, cout in {32, 64}. */
