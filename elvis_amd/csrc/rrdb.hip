@@ -1,33 +1,13 @@
 // Real-ESRGAN's RRDBNet (the network RealESRGANer.enhance runs, elvis.py:2515) on f16 NHWC tensors: the dense-block
 // 3x3 conv and the uint8 input stage.  A translation unit of its own; nothing here touches conv*.hip.
 //
-// elvis_rrdb_conv3x3: 3x3 / stride 1 / pad 1, f16 in, fp32 accumulate on v_mfma_f32_16x16x32_f16, 32 or 64 output
-// channels written at a channel offset of a wider buffer, so that a dense block appends x1..x4 to its own input and no
-// concat ever runs.  256 threads take an 8 x 32 pixel tile times all cout; wave v owns rows 2v, 2v+1.  The weights are
-// the A operand (rows = cout) and the pixels the B operand (columns), so a lane ends with 4 consecutive output channels
-// of one pixel per accumulator: one 8-byte store.  Per 32-channel K chunk the 10 x 34 halo (21.8 KB) and the chunk's
-// nine taps (18 / 36 KB) are staged in LDS once; the next chunk's global loads are issued before the MFMAs of the
-// current one and land in LDS after them.  40 / 58 KB of LDS and 172 / 232 registers per lane: two workgroups per CU.
-//
-// LDS images: rows of 64 bytes (one pixel or one (tap, cout) x 32 channels), four 16-byte slots; slot c of row p is
-// stored at slot c ^ (2 * ((p >> 2) & 1)).  A ds_read_b128 is served in four groups of 16 lanes ({0-3, 12-15, 20-27},
-// {4-11, 16-19, 28-31} and the same + 32); a fragment read has lane l at row base + l % 16, slot l / 16, and with this
-// XOR the 16 lanes of every group fall on 16 different slots of the 256-byte bank row for every base (checked by
-// enumeration; c ^ ((p >> 2) & 3) and the plain image are both 2-way).
-#include "common.h"
-#include <string.h>
+// elvis_rrdb_conv3x3: the 3x3 MFMA tile of sr_conv3x3.h (its LDS images, swizzle and fragment map are stated there) with
+// 32 or 64 output channels written at a channel offset of a wider buffer, so that a dense block appends x1..x4 to its
+// own input and no concat ever runs; a lane ends with 4 consecutive output channels of one pixel per accumulator: one
+// 8-byte store.  40 / 58 KB of LDS and 172 / 232 registers per lane: two workgroups per CU.
+#include "sr_conv3x3.h"
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int RR_TY = 8, RR_TX = 32, RR_KC = 32;
-constexpr int RR_HY = RR_TY + 2, RR_HX = RR_TX + 2;
-constexpr int RR_HALO_UNITS = RR_HY * RR_HX * 4;             // 16-byte units of one chunk's halo
-constexpr int RR_HALO_ITERS = (RR_HALO_UNITS + 255) / 256;   // 6
-constexpr int RR_HALO_BYTES = RR_HY * RR_HX * 64;
-
-__device__ __forceinline__ int rr_swz(int row, int c) { return row * 64 + ((c ^ ((row >> 1) & 2)) << 4); }
 
 struct RrdbArgs {
     const half_t* x;
@@ -43,98 +23,14 @@ struct RrdbArgs {
 
 template <int COUT>
 __global__ __launch_bounds__(256) void rrdb_conv3x3_kernel(RrdbArgs a) {
-    constexpr int W_UNITS = 9 * COUT * 4;                    // 16-byte units of one chunk's weights
-    constexpr int W_ITERS = (W_UNITS + 255) / 256;
     constexpr int NT = COUT / 16;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[RR_HALO_BYTES + W_UNITS * 16];
-    unsigned char* lds_w = lds + RR_HALO_BYTES;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tx0 = blockIdx.x * RR_TX, ty0 = blockIdx.y * RR_TY, img = blockIdx.z;
-
-    // the halo units this thread stages: source element offset (channel 0 of the chunk), or -1 for the zero border
-    long long hsrc[RR_HALO_ITERS];
-    int hdst[RR_HALO_ITERS];
-#pragma unroll
-    for (int i = 0; i < RR_HALO_ITERS; ++i) {
-        const int u = tid + i * 256;
-        hsrc[i] = -1;
-        hdst[i] = -1;
-        if (u < RR_HALO_UNITS) {
-            const int pix = u >> 2, c = u & 3;
-            const int hy = pix / RR_HX, hx = pix - hy * RR_HX;
-            const int gy = ty0 - 1 + hy, gx = tx0 - 1 + hx;
-            hdst[i] = rr_swz(pix, c);
-            if (gy >= 0 && gy < a.ho && gx >= 0 && gx < a.wo) {
-                const int sy = gy >> a.ups, sx = gx >> a.ups;
-                hsrc[i] = (((long long)img * a.h + sy) * a.w + sx) * a.x_pitch + c * 8;
-            }
-        }
-    }
-
-    u32x4 hreg[RR_HALO_ITERS], wreg[W_ITERS];
-    auto fetch = [&](int kc) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < RR_HALO_ITERS; ++i) {
-            hreg[i] = u32x4{0u, 0u, 0u, 0u};
-            if (hsrc[i] >= 0) hreg[i] = *reinterpret_cast<const u32x4*>(a.x + hsrc[i] + kc * RR_KC);
-        }
-        const u32x4* wsrc = reinterpret_cast<const u32x4*>(a.wp) + (long long)kc * W_UNITS;
-#pragma unroll
-        for (int i = 0; i < W_ITERS; ++i) {
-            const int u = tid + i * 256;
-            if (W_UNITS % 256 == 0 || u < W_UNITS) wreg[i] = wsrc[u];
-        }
-    };
-    auto stage = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < RR_HALO_ITERS; ++i)
-            if (hdst[i] >= 0) *reinterpret_cast<u32x4*>(lds + hdst[i]) = hreg[i];
-#pragma unroll
-        for (int i = 0; i < W_ITERS; ++i) {
-            const int u = tid + i * 256;
-            if (W_UNITS % 256 == 0 || u < W_UNITS) *reinterpret_cast<u32x4*>(lds_w + rr_swz(u >> 2, u & 3)) = wreg[i];
-        }
-    };
-
+    __shared__ __attribute__((aligned(16))) unsigned char lds[SR_LDS_BYTES<COUT>];
     float4v acc[4][NT];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[t][nt] = float4v{0.f, 0.f, 0.f, 0.f};
+    sr_conv3x3_tile<COUT>(a.x, a.x_pitch, a.wp, a.h, a.w, a.ho, a.wo, a.ups, a.nkc, lds, acc);
 
-    const int l15 = lane & 15, lg = lane >> 4;
-    // weight rows of a fragment start on a multiple of 16, so the swizzle term depends on the lane alone
-    const int a_lane = l15 * 64 + ((lg ^ ((l15 >> 1) & 2)) << 4);
-
-    fetch(0);
-    for (int kc = 0; kc < a.nkc; ++kc) {
-        __syncthreads();                       // the previous chunk's fragment reads are done
-        stage();
-        __syncthreads();
-        if (kc + 1 < a.nkc) fetch(kc + 1);     // in flight under the MFMAs below
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int dy = tap / 3, dx = tap - dy * 3;
-            half8 fa[NT], fb[4];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                fa[nt] = *reinterpret_cast<const half8*>(lds_w + (tap * COUT + nt * 16) * 64 + a_lane);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int p = (wave * 2 + (t >> 1) + dy) * RR_HX + (t & 1) * 16 + l15 + dx;
-                fb[t] = *reinterpret_cast<const half8*>(lds + rr_swz(p, lg));
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[nt], fb[t], acc[t][nt], 0, 0, 0);
-        }
-    }
-
-    // epilogue: accumulator register j of (t, nt) is pixel (row 2*wave + t/2, column 16*(t%2) + lane%16), output
-    // channel 16*nt + 4*(lane/16) + j
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
+    const int tx0 = blockIdx.x * SR_TX, ty0 = blockIdx.y * SR_TY, img = blockIdx.z;
+    // epilogue, on the fragment map of sr_conv3x3_tile
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int oy = ty0 + wave * 2 + (t >> 1), ox = tx0 + (t & 1) * 16 + l15;
@@ -219,33 +115,6 @@ __global__ __launch_bounds__(256) void rrdb_input_u8_kernel(const uint8_t* __res
 
 bool rr_cin_ok(int c) { return c == 32 || c == 64 || c == 96 || c == 128 || c == 160 || c == 192; }
 
-// fp32 -> f16, round to nearest even, on the host (no device code, no compiler-specific host half type)
-uint16_t rr_f32_to_f16(float f) {
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    const uint32_t mag = x & 0x7fffffffu;
-    if (mag >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (mag > 0x7f800000u ? 0x200u : 0u));   // inf, nan
-    if (mag >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                                       // rounds to inf
-    if (mag < 0x33000001u) return (uint16_t)sign;                                                    // <= 2^-25: zero
-    const int e = (int)(mag >> 23) - 127;
-    uint32_t man = (mag & 0x7fffffu) | 0x800000u;
-    int shift;
-    uint32_t base;
-    if (e < -14) {            // subnormal: value = man * 2^(e-23), unit 2^-24
-        shift = -1 - e;       // 13 + (-14 - e)
-        base = 0;
-    } else {
-        shift = 13;
-        base = (uint32_t)(e + 15) << 10;
-        man &= 0x7fffffu;
-    }
-    uint32_t q = man >> shift;
-    const uint32_t rem = man & ((1u << shift) - 1u), mid = 1u << (shift - 1);
-    if (rem > mid || (rem == mid && (q & 1u))) ++q;
-    return (uint16_t)(sign | (base + q));   // a mantissa carry moves into the exponent, as it should
-}
-
 }  // namespace
 
 extern "C" size_t elvis_rrdb_packed_weight_bytes(int cin, int cout) {
@@ -259,24 +128,8 @@ extern "C" int elvis_rrdb_pack_weights(const float* w_oihw_host, int cin_real, i
     ELVIS_REQUIRE(cin_real >= 1 && cin_real <= cin && cout_real >= 1 && cout_real <= cout,
                   "elvis_rrdb_pack_weights: real channels %d -> %d do not fit the padded %d -> %d", cin_real, cout_real, cin, cout);
     ELVIS_REQUIRE(w_oihw_host && packed_host, "elvis_rrdb_pack_weights: null pointer");
-    uint16_t* p = static_cast<uint16_t*>(packed_host);
-    // packed[kc][tap][co][ci % 32], kc = ci / 32, tap = ky * 3 + kx
-    for (int kc = 0; kc < cin / RR_KC; ++kc)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int co = 0; co < cout; ++co)
-                for (int k = 0; k < RR_KC; ++k) {
-                    const int ci = kc * RR_KC + k;
-                    float v = 0.f;
-                    if (ci < cin_real && co < cout_real) v = w_oihw_host[((size_t)co * cin_real + ci) * 9 + tap];
-                    p[(((size_t)kc * 9 + tap) * cout + co) * RR_KC + k] = rr_f32_to_f16(v);
-                }
+    sr_pack_weights(w_oihw_host, cin_real, cout_real, cin, cout, static_cast<uint16_t*>(packed_host));
     return ELVIS_OK;
-}
-
-// do the byte ranges [p, p + bytes) and [q, q + qbytes) meet
-static bool rr_ranges_meet(const void* p, long long bytes, const void* q, long long qbytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)bytes;
 }
 
 extern "C" int elvis_rrdb_conv3x3(const void* x, int x_pitch, const void* w_packed, const float* bias, void* out, int out_pitch,
@@ -307,7 +160,7 @@ extern "C" int elvis_rrdb_conv3x3(const void* x, int x_pitch, const void* w_pack
     const long long in_px = (long long)n * h * w, out_px = (long long)n * ho * wo;
     const long long x_bytes = in_px * x_pitch * 2, out_bytes = out_u8 ? out_px * 3 : out_px * out_pitch * 2;
     // aliasing: out may be x itself when the written channels lie past the read ones; any other overlap is refused
-    if (rr_ranges_meet(x, x_bytes, out, out_bytes)) {
+    if (sr_ranges_meet(x, x_bytes, out, out_bytes)) {
         ELVIS_REQUIRE(x == out && !out_u8 && !ups && out_pitch == x_pitch && out_coff >= cin,
                       "elvis_rrdb_conv3x3: out overlaps x: channels [%d, %d) written, [0, %d) read (out may alias x only at the same "
                       "pointer and pitch, without upsample, on disjoint channels)", out_coff, out_coff + cout, cin);
@@ -315,12 +168,12 @@ extern "C" int elvis_rrdb_conv3x3(const void* x, int x_pitch, const void* w_pack
     const void* rs[2] = {r1, r2};
     const int rp[2] = {r1_pitch, r2_pitch};
     for (int k = 0; k < 2; ++k) {
-        if (!rs[k] || !rr_ranges_meet(rs[k], out_px * rp[k] * 2, out, out_bytes)) continue;
+        if (!rs[k] || !sr_ranges_meet(rs[k], out_px * rp[k] * 2, out, out_bytes)) continue;
         // a residual inside out's allocation: element for element (read, then written, by one lane), or on other channels
         ELVIS_REQUIRE(rs[k] == out && !out_u8 && rp[k] == out_pitch && (out_coff == 0 || out_coff >= cout),
                       "elvis_rrdb_conv3x3: r%d overlaps out: channels [0, %d) read, [%d, %d) written", k + 1, cout, out_coff, out_coff + cout);
     }
-    const int tiles_x = cdiv(wo, RR_TX), tiles_y = cdiv(ho, RR_TY);
+    const int tiles_x = cdiv(wo, SR_TX), tiles_y = cdiv(ho, SR_TY);
     ELVIS_REQUIRE(n <= 65535 && tiles_y <= 65535, "elvis_rrdb_conv3x3: n=%d ho=%d is more than one launch holds", n, ho);
     RrdbArgs a;
     a.x = static_cast<const half_t*>(x);
@@ -330,7 +183,7 @@ extern "C" int elvis_rrdb_conv3x3(const void* x, int x_pitch, const void* w_pack
     a.r1 = static_cast<const half_t*>(r1);
     a.r2 = static_cast<const half_t*>(r2);
     a.x_pitch = x_pitch; a.out_pitch = out_pitch; a.out_coff = out_coff; a.r1_pitch = r1_pitch; a.r2_pitch = r2_pitch;
-    a.h = h; a.w = w; a.ho = ho; a.wo = wo; a.nkc = cin / RR_KC; a.ups = ups; a.lrelu = lrelu ? 1 : 0;
+    a.h = h; a.w = w; a.ho = ho; a.wo = wo; a.nkc = cin / SR_KC; a.ups = ups; a.lrelu = lrelu ? 1 : 0;
     a.out_u8 = out_u8 ? 1 : 0; a.swap_rb = swap_rb ? 1 : 0;
     a.s0 = s0; a.s1 = s1;
     const dim3 grid(tiles_x, tiles_y, n);

@@ -21,13 +21,13 @@ and restore nothing.  The trained checkpoints (`RealESRGAN_x4plus.pth`, ...) loa
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from ._srnet import SRModel, pack_conv as _pack_conv
 from .weights import RRDBNetConfig, load_realesrgan_state_dict, make_rrdbnet_weights, rrdbnet_layout
 
 # device bytes one low-resolution pixel of one frame costs inside `forward`: three 192-channel buffers, the 64-channel
@@ -36,26 +36,10 @@ BYTES_PER_LR_PIXEL = 2 * (3 * 192 + 64 + 32) + 4 * 2 * 64 + 16 * 2 * (64 + 64 + 
 MAX_INVOCATION_BYTES = 12 << 30
 
 
-def _pad32(c: int) -> int:
-    return (c + 31) // 32 * 32
-
-
 def pack_conv(w_oihw: torch.Tensor, bias: torch.Tensor):
     """(packed f16 weights as a uint16 numpy array, fp32 bias padded to the kernel's cout, cin, cout) of one conv:
     `elvis_rrdb_pack_weights` on the host, input and output channels padded to multiples of 32 with zeros."""
-    w = np.ascontiguousarray(w_oihw.detach().to("cpu", torch.float32).numpy())
-    cout_real, cin_real = w.shape[:2]
-    cin, cout = _pad32(cin_real), _pad32(cout_real)
-    lib = L.lib()
-    nbytes = lib.elvis_rrdb_packed_weight_bytes(cin, cout)
-    if nbytes == 0:
-        raise ValueError(f"no RRDB conv kernel for {cin_real} -> {cout_real} channels")
-    packed = np.empty(nbytes // 2, dtype=np.uint16)
-    L.check(lib.elvis_rrdb_pack_weights(w.ctypes.data_as(C.c_void_p), cin_real, cout_real, cin, cout,
-                                        packed.ctypes.data_as(C.c_void_p)))
-    b = np.zeros(cout, dtype=np.float32)
-    b[:cout_real] = bias.detach().to("cpu", torch.float32).numpy()
-    return packed, b, cin, cout
+    return _pack_conv("rrdb", w_oihw, bias, pad_cout=True)
 
 
 class _Conv:
@@ -67,20 +51,19 @@ class _Conv:
         self.b = torch.from_numpy(b).to(device)
 
 
-class RRDBNetModel:
+class RRDBNetModel(SRModel):
     """The packed network on one device.  `state_dict` is a checked dict (`load_realesrgan_state_dict`), a path, a
-    checkpoint dict, or None for the seeded synthetic weights (`weight_seed`)."""
+    checkpoint dict, or None for the seeded synthetic weights (`weight_seed`).  `forward` (`SRModel.forward`) scales by
+    `cfg.scale`; its `as_float` gives the f16 output of conv_last."""
 
     def __init__(self, cfg: RRDBNetConfig = RRDBNetConfig(), state_dict=None, device="cuda:0", weight_seed: int = 0):
+        super().__init__(device)
         self.cfg = cfg
-        self.device = L.resolve_device(device)
-        self.dtype = torch.float16
         self.scale = cfg.scale
         sd = make_rrdbnet_weights(cfg, weight_seed) if state_dict is None else load_realesrgan_state_dict(state_dict, cfg)
         with torch.cuda.device(self.device):
             self.convs: Dict[str, _Conv] = {key: _Conv(sd[key + ".weight"], sd[key + ".bias"], self.device)
                                             for key, _, _ in rrdbnet_layout(cfg)}
-        self._bufs = None
 
     # ------------------------------------------------------------------ plumbing
     def _conv(self, key: str, x: torch.Tensor, out: torch.Tensor, n: int, h: int, w: int, *, out_coff: int = 0,
@@ -93,19 +76,15 @@ class RRDBNetModel:
             n, h, w, cv.cin if cin is None else cin, cv.cout, int(upsample), int(lrelu), s0, s1, int(out_u8), int(swap_rb),
             L.stream_handle(self.device)), self.device)
 
-    def _buffers(self, n: int, h: int, w: int):
-        key = (n, h, w)
-        if self._bufs is None or self._bufs[0] != key:
-            self._bufs = None   # free the previous shape's buffers first
-            f16 = dict(dtype=torch.float16, device=self.device)
-            self._bufs = (key, dict(
-                x0=torch.empty((n, h, w, 32), **f16),
-                dense=[torch.empty((n, h, w, 192), **f16) for _ in range(3)],
-                feat=torch.empty((n, h, w, 64), **f16),
-                up1=torch.empty((n, 2 * h, 2 * w, 64), **f16),
-                up2=torch.empty((n, 4 * h, 4 * w, 64), **f16),
-                hr=torch.empty((n, 4 * h, 4 * w, 64), **f16)))
-        return self._bufs[1]
+    def _alloc_buffers(self, n: int, h: int, w: int):
+        f16 = dict(dtype=torch.float16, device=self.device)
+        return dict(
+            x0=torch.empty((n, h, w, 32), **f16),
+            dense=[torch.empty((n, h, w, 192), **f16) for _ in range(3)],
+            feat=torch.empty((n, h, w, 64), **f16),
+            up1=torch.empty((n, 2 * h, 2 * w, 64), **f16),
+            up2=torch.empty((n, 4 * h, 4 * w, 64), **f16),
+            hr=torch.empty((n, 4 * h, 4 * w, 64), **f16))
 
     def _dense_block(self, prefix: str, src: torch.Tensor, dst: torch.Tensor, n, h, w, *, tail_of: Optional[torch.Tensor] = None):
         """One dense block on `src` ([n,h,w,192], input in channels [0, 64)): x1..x4 appended in place, then
@@ -150,27 +129,6 @@ class RRDBNetModel:
             out = out[:, :s * H, :s * W]
         return out.contiguous()
 
-    def max_batch(self, H: int, W: int) -> int:
-        """Frames of H x W one invocation takes: capped by the bytes of its activations."""
+    def _lr_pixels(self, H: int, W: int) -> int:
         s_in = 2 if self.cfg.scale == 2 else 1
-        px = ((H + s_in - 1) // s_in) * ((W + s_in - 1) // s_in)
-        return max(1, MAX_INVOCATION_BYTES // (BYTES_PER_LR_PIXEL * px))
-
-    def forward(self, lr_u8_d: torch.Tensor, swap_rb: bool = True, as_float: bool = False) -> torch.Tensor:
-        """[n,h,w,3] uint8 on the device -> [n,s*h,s*w,3] uint8 on the device (s = cfg.scale).  `swap_rb`: the frames
-        are BGR (the reference's decoded frames); the network sees RGB and the output is BGR again.  `as_float`: the
-        f16 output of conv_last before `clamp * 255, round`, for tests.  Frames go through in groups capped by bytes;
-        every kernel is per-sample, so the result does not depend on the grouping."""
-        if lr_u8_d.dtype != torch.uint8 or lr_u8_d.dim() != 4 or lr_u8_d.shape[-1] != 3:
-            raise ValueError(f"RRDBNetModel.forward takes [n,h,w,3] uint8, got {tuple(lr_u8_d.shape)} {lr_u8_d.dtype}")
-        if lr_u8_d.device != self.device:
-            raise ValueError(f"RRDBNetModel.forward: frames on {lr_u8_d.device}, model on {self.device}")
-        n, H, W, _ = lr_u8_d.shape
-        s = self.cfg.scale
-        if n == 0 or H == 0 or W == 0:
-            return torch.empty((n, s * H, s * W, 3), dtype=torch.float16 if as_float else torch.uint8, device=self.device)
-        lr = lr_u8_d.contiguous()
-        step = self.max_batch(H, W)
-        with torch.cuda.device(self.device):
-            outs = [self._forward_batch(lr[i:i + step], swap_rb, as_float) for i in range(0, n, step)]
-        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+        return ((H + s_in - 1) // s_in) * ((W + s_in - 1) // s_in)

@@ -20,13 +20,13 @@ downloaded.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import List
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from ._srnet import SRModel, pack_conv as _pack_conv
 from .weights import SRVGGConfig, load_srvgg_state_dict, make_srvgg_weights
 
 # device bytes one low-resolution pixel of one frame costs inside `forward`: the 32-channel input, two 64-channel
@@ -38,18 +38,7 @@ MAX_INVOCATION_BYTES = 12 << 30
 def pack_conv(w_oihw: torch.Tensor, bias: torch.Tensor):
     """(packed f16 weights as a uint16 numpy array, fp32 bias, cin, cout) of one conv: `elvis_srvgg_pack_weights` on
     the host, input channels padded to a multiple of 32 with zeros."""
-    w = np.ascontiguousarray(w_oihw.detach().to("cpu", torch.float32).numpy())
-    cout, cin_real = w.shape[:2]
-    cin = (cin_real + 31) // 32 * 32
-    lib = L.lib()
-    nbytes = lib.elvis_srvgg_packed_weight_bytes(cin, cout)
-    if nbytes == 0:
-        raise ValueError(f"no SRVGG conv kernel for {cin_real} -> {cout} channels")
-    packed = np.empty(nbytes // 2, dtype=np.uint16)
-    L.check(lib.elvis_srvgg_pack_weights(w.ctypes.data_as(C.c_void_p), cin_real, cout, cin, cout,
-                                         packed.ctypes.data_as(C.c_void_p)))
-    b = np.ascontiguousarray(bias.detach().to("cpu", torch.float32).numpy())
-    return packed, b, cin, cout
+    return _pack_conv("srvgg", w_oihw, bias, pad_cout=False)
 
 
 class _Layer:
@@ -62,14 +51,14 @@ class _Layer:
         self.a = None if slope is None else slope.detach().to(device, torch.float32).contiguous()   # fp32, not rounded
 
 
-class SRVGGModel:
+class SRVGGModel(SRModel):
     """The packed network on one device, with the interface of `realesrgan.RRDBNetModel`.  `state_dict` is a checked
-    dict (`load_srvgg_state_dict`), a path, a checkpoint dict, or None for the seeded synthetic weights (`weight_seed`)."""
+    dict (`load_srvgg_state_dict`), a path, a checkpoint dict, or None for the seeded synthetic weights (`weight_seed`).
+    `forward` (`SRModel.forward`) scales by 4; its `as_float` gives the f16 sum of the shuffled last conv and the base."""
 
     def __init__(self, cfg: SRVGGConfig = SRVGGConfig(), state_dict=None, device="cuda:0", weight_seed: int = 0):
+        super().__init__(device)
         self.cfg = cfg
-        self.device = L.resolve_device(device)
-        self.dtype = torch.float16
         self.scale = cfg.upscale
         sd = make_srvgg_weights(cfg, weight_seed) if state_dict is None else load_srvgg_state_dict(state_dict, cfg)
         last = cfg.num_conv + 1
@@ -77,16 +66,10 @@ class SRVGGModel:
             self.layers: List[_Layer] = [
                 _Layer(sd[f"body.{2 * i}.weight"], sd[f"body.{2 * i}.bias"],
                        None if i == last else sd[f"body.{2 * i + 1}.weight"], self.device) for i in range(last + 1)]
-        self._bufs = None
 
-    def _buffers(self, n: int, h: int, w: int):
-        key = (n, h, w)
-        if self._bufs is None or self._bufs[0] != key:
-            self._bufs = None   # free the previous shape's buffers first
-            f16 = dict(dtype=torch.float16, device=self.device)
-            self._bufs = (key, (torch.empty((n, h, w, 32), **f16), torch.empty((n, h, w, 64), **f16),
-                                torch.empty((n, h, w, 64), **f16)))
-        return self._bufs[1]
+    def _alloc_buffers(self, n: int, h: int, w: int):
+        f16 = dict(dtype=torch.float16, device=self.device)
+        return torch.empty((n, h, w, 32), **f16), torch.empty((n, h, w, 64), **f16), torch.empty((n, h, w, 64), **f16)
 
     def _forward_batch(self, lr: torch.Tensor, swap_rb: bool, as_float: bool) -> torch.Tensor:
         n, h, w, _ = lr.shape
@@ -105,24 +88,5 @@ class SRVGGModel:
                                      out.data_ptr(), n, h, w, int(not as_float), int(swap_rb), stream), self.device)
         return out
 
-    def max_batch(self, H: int, W: int) -> int:
-        """Frames of H x W one invocation takes: capped by the bytes of its activations."""
-        return max(1, MAX_INVOCATION_BYTES // (BYTES_PER_LR_PIXEL * H * W))
-
-    def forward(self, lr_u8_d: torch.Tensor, swap_rb: bool = True, as_float: bool = False) -> torch.Tensor:
-        """[n,h,w,3] uint8 on the device -> [n,4h,4w,3] uint8 on the device.  `swap_rb`: the frames are BGR (the
-        reference's decoded frames); the network sees RGB and the output is BGR again.  `as_float`: the f16 sum of the
-        shuffled last conv and the base before `clamp * 255, round`, for tests.  Frames go through in groups capped by
-        bytes; every kernel is per-sample, so the result does not depend on the grouping."""
-        if lr_u8_d.dtype != torch.uint8 or lr_u8_d.dim() != 4 or lr_u8_d.shape[-1] != 3:
-            raise ValueError(f"SRVGGModel.forward takes [n,h,w,3] uint8, got {tuple(lr_u8_d.shape)} {lr_u8_d.dtype}")
-        if lr_u8_d.device != self.device:
-            raise ValueError(f"SRVGGModel.forward: frames on {lr_u8_d.device}, model on {self.device}")
-        n, H, W, _ = lr_u8_d.shape
-        if n == 0 or H == 0 or W == 0:
-            return torch.empty((n, 4 * H, 4 * W, 3), dtype=torch.float16 if as_float else torch.uint8, device=self.device)
-        lr = lr_u8_d.contiguous()
-        step = self.max_batch(H, W)
-        with torch.cuda.device(self.device):
-            outs = [self._forward_batch(lr[i:i + step], swap_rb, as_float) for i in range(0, n, step)]
-        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+    def _lr_pixels(self, H: int, W: int) -> int:
+        return H * W

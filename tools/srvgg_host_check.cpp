@@ -7,90 +7,15 @@
 //         -o srvgg_host_check && ./srvgg_host_check
 //
 // Packing: every supported (cin, cout) with full and ragged real channel counts, into a heap block of exactly
-// elvis_srvgg_packed_weight_bytes; each element is compared with a conversion written here (a write past the block or a
-// read past the fp32 tensor stops the run).  Argument checks: every refusal must come back as -1 before any launch.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "../include/elvis_amd.h"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::fprintf(stderr, "line %d: %s\n", __LINE__, #cond);         \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
-
-// f16 bits -> float, exact
-static float f16_value(uint16_t h) {
-    const int s = h >> 15, e = (h >> 10) & 31, m = h & 1023;
-    float v;
-    if (e == 0) v = std::ldexp((float)m, -24);
-    else if (e == 31) v = m ? NAN : INFINITY;
-    else v = std::ldexp((float)(m + 1024), e - 25);
-    return s ? -v : v;
-}
-
-// is `h` a nearest f16 of `f` (ties: the even one)
-static bool is_rne16(float f, uint16_t h) {
-    const float v = f16_value(h);
-    if (std::isnan(f)) return std::isnan(v);
-    if (std::isinf(v)) return std::fabs(f) >= 65520.0f && (v > 0) == (f > 0);
-    if (std::signbit(v) != std::signbit(f)) return false;
-    const uint16_t mag = h & 0x7fff;
-    const float up = f16_value((uint16_t)(mag + 1)), dn = mag ? f16_value((uint16_t)(mag - 1)) : -f16_value(1);
-    const double a = std::fabs((double)f), c = std::fabs((double)v);
-    const double hi = (mag + 1 == 0x7c00) ? 65520.0 : 0.5 * (c + up), lo = 0.5 * (c + dn);
-    if (a > hi || a < lo) return false;
-    if ((a == hi || a == lo) && (mag & 1)) return false;
-    return true;
-}
+// elvis_srvgg_packed_weight_bytes; each element is compared with sr_host_check.h's own conversion (a write past the
+// block or a read past the fp32 tensor stops the run).  Argument checks: every refusal must come back as -1 before any
+// launch.
+#include "sr_host_check.h"
 
 int main() {
     const int cins[] = {32, 64}, couts[] = {48, 64};
-    uint32_t seed = 54321u;
-    auto next = [&]() { seed = seed * 1664525u + 1013904223u; return seed; };
-    for (int cin : cins)
-        for (int cout : couts)
-            for (int ragged = 0; ragged < 2; ++ragged) {
-                const int cin_real = ragged ? (cin == 32 ? 3 : cin - 5) : cin, cout_real = ragged ? cout - 1 : cout;
-                const size_t nw = (size_t)cout_real * cin_real * 9;
-                std::vector<float> w(nw);
-                for (size_t i = 0; i < nw; ++i) {
-                    const uint32_t r = next();
-                    switch (r % 11) {
-                        case 0: w[i] = std::ldexp(1.0f, -25); break;                  // tie at the smallest subnormal
-                        case 1: w[i] = -std::ldexp(3.0f, -25); break;                 // tie between subnormals
-                        case 2: w[i] = 65519.9f; break;
-                        case 3: w[i] = 65520.0f; break;                               // rounds to infinity
-                        case 4: w[i] = 1.0f + std::ldexp(1.0f, -11); break;           // tie, even below
-                        case 5: w[i] = 1.0f + std::ldexp(3.0f, -11); break;           // tie, even above
-                        case 6: w[i] = -0.0f; break;
-                        default: w[i] = ((int)(r >> 8) % 20001 - 10000) * 1e-4f * std::ldexp(1.0f, (int)(r % 7) - 8);
-                    }
-                }
-                const size_t bytes = elvis_srvgg_packed_weight_bytes(cin, cout);
-                EXPECT(bytes == (size_t)9 * cin * cout * 2);
-                uint16_t* packed = (uint16_t*)std::malloc(bytes);
-                std::memset(packed, 0xff, bytes);
-                EXPECT(elvis_srvgg_pack_weights(w.data(), cin_real, cout_real, cin, cout, packed) == 0);
-                for (int kc = 0; kc < cin / 32; ++kc)
-                    for (int tap = 0; tap < 9; ++tap)
-                        for (int co = 0; co < cout; ++co)
-                            for (int k = 0; k < 32; ++k) {
-                                const int ci = kc * 32 + k;
-                                const uint16_t got = packed[(((size_t)kc * 9 + tap) * cout + co) * 32 + k];
-                                if (ci < cin_real && co < cout_real) EXPECT(is_rne16(w[((size_t)co * cin_real + ci) * 9 + tap], got));
-                                else EXPECT(got == 0);
-                            }
-                std::free(packed);
-            }
+    check_packing(elvis_srvgg_packed_weight_bytes, elvis_srvgg_pack_weights, cins, couts,
+                  [](int cout) { return cout - 1; }, 54321u);
     EXPECT(elvis_srvgg_packed_weight_bytes(96, 64) == 0);
     EXPECT(elvis_srvgg_packed_weight_bytes(64, 32) == 0);
     float one = 1.0f;
