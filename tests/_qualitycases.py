@@ -35,15 +35,16 @@ SRC_NAMES, BORDER_NAMES = ("luma", "channels"), ("reflect", "valid")
 def kernel_names(lib_path: str, source_path: str):
     """The kernels of one source file in the built library, spelled as elvis_last_launch spells them:
     `_Z16ssim_tile_kernelILi0ELi1EEv10SsimParams` -> `ssim_tile_kernel<luma,valid>`, `..ssim_finish_kernelILi1EE..`
-    -> `ssim_finish_kernel<valid>`, `_ZN12_GLOBAL__N_119inpaint_fill_kernelILi3EEEv..` -> `inpaint_fill_kernel<3>`."""
+    -> `ssim_finish_kernel<valid>`, `_ZN12_GLOBAL__N_119inpaint_fill_kernelILi3EEEv..` -> `inpaint_fill_kernel<3>`,
+    `..srvgg_conv3x3_kernelILi64ELb0EE..` -> `srvgg_conv3x3_kernel<64,false>`."""
     stems = kernel_stems(source_path)
     out = set()
     for sym in elf_symbols(lib_path):
         stem = demangle_kernel(sym, stems)
         if stem is None:
             continue
-        t = re.match(r"_Z(?:N12_GLOBAL__N_1)?\d+" + stem + r"I((?:Li\d+E)+)E", sym)
-        args = [int(v) for v in re.findall(r"Li(\d+)E", t.group(1))] if t else []
+        t = re.match(r"_Z(?:N12_GLOBAL__N_1)?\d+" + stem + r"I((?:L[ib]\d+E)+)E", sym)
+        args = [int(v) if k == "i" else ("false", "true")[int(v)] for k, v in re.findall(r"L([ib])(\d+)E", t.group(1))] if t else []
         if stem == "ssim_tile_kernel":
             out.add(f"{stem}<{SRC_NAMES[args[0]]},{BORDER_NAMES[args[1]]}>")
         elif stem == "ssim_finish_kernel":

@@ -32,7 +32,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from _convref import U24, rne16, ulp16
+import _srmut as M
+from _convref import U24, rne16, trunc16, ulp16
 
 # ----------------------------------------------------------------------------------------------- one conv
 class ConvRef:
@@ -43,40 +44,74 @@ class ConvRef:
         return 0.5 * ulp16(self.ref.abs() + self.e) + self.e
 
 
-def conv_ref(x_hat, w, b, *, upsample=False, lrelu=False, s0=1.0, s1=0.0, r1=None, r2=None) -> ConvRef:
+# The statement with one clause changed (tests/test_sr_ledger.py: each must move a named case of tests/_srcases.py past
+# the bound).  The sum's mutants are those of tests/_srmut.py; the epilogue's:
+#   bias_roll_1 / _4 / _16   the bias of the neighbouring channel, lane group (4 channels) or accumulator (16)
+#   s0_s1_swapped            s1 v + s0 r1 + r2
+#   r1_r2_swapped            s0 v + s1 r2 + r1
+#   ups_source_round_up      the upsampled row y reads source row (y + 1) >> 1 (the last row again past the end)
+#   store_f16_trunc          the f16 store rounds toward zero: `ref` is then the stored value itself
+MUTANTS = M.SUM + M.WEIGHTS + ("bias_roll_1", "bias_roll_4", "bias_roll_16", "s0_s1_swapped", "r1_r2_swapped", "ups_source_round_up",
+                               "store_f16_trunc")
+U8_MUTANTS = ("u8_half_up", "u8_truncate")
+
+
+def conv_ref(x_hat, w, b, *, upsample=False, lrelu=False, s0=1.0, s1=0.0, r1=None, r2=None, mutant=None) -> ConvRef:
     """x_hat NCHW float64 (the stored f16 values, before `upsample`), w OIHW fp32 (rounded to f16 here), b fp32 [cout],
-    r1 / r2 NCHW float64 at the output size or None.  s0, s1 as the fp32 values the kernel receives."""
+    r1 / r2 NCHW float64 at the output size or None.  s0, s1 as the fp32 values the kernel receives.  `mutant`: one of
+    MUTANTS - the error model stays the statement's own."""
+    if mutant is not None and mutant not in MUTANTS:
+        raise ValueError("unknown mutant")
     s0, s1 = float(np.float32(s0)), float(np.float32(s1))
     w_hat = rne16(w.double())
     b = b.double()
     if upsample:
+        x_src = x_hat
         x_hat = F.interpolate(x_hat, scale_factor=2, mode="nearest")
     z = F.conv2d(x_hat, w_hat, None, padding=1) + b[None, :, None, None]
     A = F.conv2d(x_hat.abs(), w_hat.abs(), None, padding=1) + b.abs()[None, :, None, None]
+    if mutant in M.SUM:
+        z = M.mutated_sum(x_hat, w_hat, mutant) + b[None, :, None, None]
+    elif mutant in M.WEIGHTS:
+        z = F.conv2d(x_hat, M.weights(w, mutant), None, padding=1) + b[None, :, None, None]
+    elif mutant is not None and mutant.startswith("bias_roll_"):
+        z = F.conv2d(x_hat, w_hat, None, padding=1) + b.roll(-int(mutant[10:]))[None, :, None, None]
+    elif mutant == "ups_source_round_up" and upsample:
+        rows = ((torch.arange(2 * x_src.shape[2]) + 1) >> 1).clamp(max=x_src.shape[2] - 1)
+        z = F.conv2d(x_src[:, :, rows].repeat_interleave(2, dim=3), w_hat, None, padding=1) + b[None, :, None, None]
+    elif mutant == "s0_s1_swapped":
+        s0, s1 = s1, s0
+    elif mutant == "r1_r2_swapped":
+        r1, r2 = r2, r1
     v = torch.where(z > 0, z, 0.2 * z) if lrelu else z
     t1 = torch.zeros_like(z) if r1 is None else s1 * r1
     t2 = torch.zeros_like(z) if r2 is None else r2
     ref = s0 * v + t1 + t2
     K = 9 * x_hat.shape[1]
     e = abs(s0) * (K + 2) * U24 * A + 3 * U24 * ((s0 * v).abs() + t1.abs() + t2.abs())
+    if mutant == "store_f16_trunc":
+        ref = trunc16(ref)
     return ConvRef(ref, e)
 
 
-def u8_ref(r: ConvRef):
-    """(expected byte, mask of the elements that may differ by one) of the out_u8 epilogue, NCHW over 3 channels."""
+def u8_ref(r: ConvRef, mutant=None):
+    """(expected byte, mask of the elements that may differ by one) of the out_u8 epilogue, NCHW over 3 channels.
+    `mutant`: "u8_half_up" (floor(q + 0.5)) or "u8_truncate" (floor(q)) in the place of half to even."""
+    if mutant is not None and mutant not in U8_MUTANTS:
+        raise ValueError("unknown mutant")
     q = 255.0 * r.ref[:, :3].clamp(0.0, 1.0)
-    byte = torch.from_numpy(np.round(q.numpy())).to(torch.int64)          # numpy rounds half to even
+    byte = M.round_u8(q, mutant)                                          # numpy rounds half to even
     frac = q - torch.floor(q)
     near = (frac - 0.5).abs() <= 255.0 * r.e[:, :3]
     return byte, near
 
 
-def u8_inputs(cin, h, w, n, swap, res):
+def u8_inputs(cin, h, w, n, swap, res, seed=None):
     """Inputs of an out_u8 case, chosen so that few values lie within 255 e of a half-integer.  e grows with
     (9 cin + 2) * A, A = sum |x||w| + |b|, so A is kept near the size of the output itself: only `active` input channels
     are non-zero (A / |z| ~ 0.64 sqrt(9 active)), and where there is a residual the picture's level comes in through
     r2, which costs 3 * 2^-24 and not (K + 2) * 2^-24.  The output still spans [-0.2, 1.2], so both clamps are reached."""
-    g = torch.Generator().manual_seed(cin + h + swap)
+    g = torch.Generator().manual_seed(cin + h + swap if seed is None else seed)
     active, z_std = (4, 0.1) if "2" in res else (2, 0.35)
     wt = torch.randn((3, cin, 3, 3), generator=g) * (z_std / math.sqrt(9 * active))
     b = torch.randn(3, generator=g) * 0.02 if "2" in res else torch.full((3,), 0.5) + torch.randn(3, generator=g) * 0.05

@@ -35,7 +35,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from _convref import U24, rne16, ulp16
+import _srmut as M
+from _convref import U24, rne16, trunc16, ulp16
 
 
 # ----------------------------------------------------------------------------------------------- one call
@@ -47,20 +48,48 @@ class ConvRef:
         return 0.5 * ulp16(self.ref.abs() + self.e) + self.e
 
 
-def _sum(x_hat, w, b):
+# The statement with one clause changed (tests/test_sr_ledger.py: each must move a named case of tests/_srcases.py past
+# the bound).  The sum's mutants are those of tests/_srmut.py; the others:
+#   bias_roll_1 / _4 / _16    the bias of the neighbouring channel, lane group (4 channels) or accumulator (16)
+#   slope_roll_1 / _4 / _16   the same for the PReLU slope (the layer)
+#   shuffle_dy_dx             channel 16c + 4dy + dx goes to (4y + dx, 4x + dy) (the tail)
+#   base_left                 the base of the pixel to the left, the first column its own (the tail)
+#   base_not_swapped          under swap_rb the base keeps its order while the conv's channels are exchanged: in the RGB
+#                             order `tail_ref` speaks, the base's channels reversed (the tail)
+#   store_f16_trunc           the f16 store rounds toward zero: `ref` is then the stored value itself
+_BIAS = ("bias_roll_1", "bias_roll_4", "bias_roll_16")
+CONV_MUTANTS = M.SUM + M.WEIGHTS + _BIAS + ("slope_roll_1", "slope_roll_4", "slope_roll_16", "store_f16_trunc")
+TAIL_MUTANTS = M.SUM + M.WEIGHTS + _BIAS + ("shuffle_dy_dx", "base_left", "base_not_swapped", "store_f16_trunc")
+U8_MUTANTS = ("u8_half_up", "u8_truncate")
+
+
+def _sum(x_hat, w, b, mutant=None):
     w_hat = rne16(w.double())
     b = b.double()
     z = F.conv2d(x_hat, w_hat, None, padding=1) + b[None, :, None, None]
     A = F.conv2d(x_hat.abs(), w_hat.abs(), None, padding=1) + b.abs()[None, :, None, None]
+    if mutant in M.SUM:
+        z = M.mutated_sum(x_hat, w_hat, mutant) + b[None, :, None, None]
+    elif mutant in M.WEIGHTS:
+        z = F.conv2d(x_hat, M.weights(w, mutant), None, padding=1) + b[None, :, None, None]
+    elif mutant in _BIAS:
+        z = F.conv2d(x_hat, w_hat, None, padding=1) + b.roll(-int(mutant[10:]))[None, :, None, None]
     return z, A, 9 * x_hat.shape[1]
 
 
-def conv_ref(x_hat, w, b, slope) -> ConvRef:
-    """x_hat NCHW float64 (the stored f16 values), w OIHW fp32 (rounded to f16 here), b and slope fp32 [64]."""
-    z, A, K = _sum(x_hat, w, b)
+def conv_ref(x_hat, w, b, slope, mutant=None) -> ConvRef:
+    """x_hat NCHW float64 (the stored f16 values), w OIHW fp32 (rounded to f16 here), b and slope fp32 [64].  `mutant`:
+    one of CONV_MUTANTS - the error model stays the statement's own."""
+    if mutant is not None and mutant not in CONV_MUTANTS:
+        raise ValueError("unknown mutant")
+    z, A, K = _sum(x_hat, w, b, mutant)
     a = slope.double()[None, :, None, None]
     ref = torch.where(z > 0, z, a * z)
     e = a.abs().clamp(min=1.0) * (K + 2) * U24 * A + U24 * ref.abs()
+    if mutant is not None and mutant.startswith("slope_roll_"):
+        ref = torch.where(z > 0, z, a.roll(-int(mutant[11:]), 1) * z)
+    elif mutant == "store_f16_trunc":
+        ref = trunc16(ref)
     return ConvRef(ref, e)
 
 
@@ -79,19 +108,34 @@ def nearest4(t):
     return t.repeat_interleave(4, dim=2).repeat_interleave(4, dim=3)
 
 
-def tail_ref(x_hat, w, b, base_hat) -> ConvRef:
+def tail_ref(x_hat, w, b, base_hat, mutant=None) -> ConvRef:
     """x_hat NCHW float64 [n,64,h,w], w OIHW fp32 [48,64,3,3], b fp32 [48], base_hat NCHW float64 [n,3,h,w] (the stored
-    f16 values): [n,3,4h,4w] in RGB order (no swap)."""
-    z, A, K = _sum(x_hat, w, b)
+    f16 values): [n,3,4h,4w] in RGB order (no swap).  `mutant`: one of TAIL_MUTANTS - the error model stays the
+    statement's own."""
+    if mutant is not None and mutant not in TAIL_MUTANTS:
+        raise ValueError("unknown mutant")
+    z, A, K = _sum(x_hat, w, b, mutant)
     zs, As, bs = shuffle4(z), shuffle4(A), nearest4(base_hat)
     e = (K + 2) * U24 * As + U24 * (zs.abs() + bs.abs())
-    return ConvRef(zs + bs, e)
+    if mutant == "shuffle_dy_dx":
+        zs = shuffle4(z.reshape(z.shape[0], 3, 4, 4, *z.shape[2:]).transpose(2, 3).reshape(z.shape))
+    elif mutant == "base_left":
+        bs = nearest4(torch.cat((base_hat[..., :1], base_hat[..., :-1]), -1))
+    elif mutant == "base_not_swapped":
+        bs = nearest4(base_hat.flip(1))
+    ref = zs + bs
+    if mutant == "store_f16_trunc":
+        ref = trunc16(ref)
+    return ConvRef(ref, e)
 
 
-def u8_ref(r: ConvRef):
-    """(expected byte, mask of the elements that may differ by one) of the u8 mode, [n,3,4h,4w]."""
+def u8_ref(r: ConvRef, mutant=None):
+    """(expected byte, mask of the elements that may differ by one) of the u8 mode, [n,3,4h,4w].  `mutant`: "u8_half_up"
+    (floor(q + 0.5)) or "u8_truncate" (floor(q)) in the place of half to even."""
+    if mutant is not None and mutant not in U8_MUTANTS:
+        raise ValueError("unknown mutant")
     q = 255.0 * r.ref.clamp(0.0, 1.0)
-    byte = torch.from_numpy(np.round(q.numpy())).to(torch.int64)          # numpy rounds half to even
+    byte = M.round_u8(q, mutant)                                          # numpy rounds half to even
     frac = q - torch.floor(q)
     near = (frac - 0.5).abs() <= 255.0 * (r.e + U24)
     return byte, near
@@ -101,13 +145,13 @@ def u8_ref(r: ConvRef):
 U8_CASES = [(9, 33, 2, 0, 3), (17, 70, 1, 1, 5), (8, 32, 1, 1, 32), (7, 31, 1, 0, 4), (1, 1, 2, 1, 8)]
 
 
-def u8_inputs(h, w, n, swap, base_pitch):
+def u8_inputs(h, w, n, swap, base_pitch, seed=None):
     """Inputs of a u8 case, chosen so that few values lie within 255 e8 of a half-integer.  e grows with
     (9 * 64 + 2) * A, A = sum |x||w| + |b|, so A is kept near the size of the conv's own output: only two input channels
     are non-zero (A / |z| ~ 0.64 sqrt(18)), the conv's output is small (std 0.1) and the picture's level comes in
     through the base, which costs 2^-24 and not (K + 2) * 2^-24.  The sum still spans about [-0.3, 1.3], so both clamps
     are reached.  The one-pixel case has too few elements for random values to reach anything: its base is set by hand."""
-    g = torch.Generator().manual_seed(1000 * h + 10 * w + swap)
+    g = torch.Generator().manual_seed(1000 * h + 10 * w + swap if seed is None else seed)
     active, z_std = 2, 0.1
     wt = torch.randn((48, 64, 3, 3), generator=g) * (z_std / math.sqrt(9 * active))
     b = torch.randn(48, generator=g) * 0.02
