@@ -32,6 +32,8 @@ from .shrink import (apply_selective_removal, block_gather_device, shrink_frame_
                      stretch_frame_removal_indices, stretch_frame_row_only, stretch_index_device, stretch_video_frames)
 from .inpaint import (inpaint_blocks_device, inpaint_device, inpaint_frame, inpaint_with_opencv,  # noqa: F401
                       stretch_and_inpaint_device)
+from .inpaint_temporal import (inpaint_temporal, inpaint_temporal_device, temporal_fill_blocks_device,  # noqa: F401
+                               temporal_fill_device)
 from .complexity import (BlockComplexity, EVCAConfig, analyze_frames, block_complexity_device,  # noqa: F401
                          removability_from_complexity, resize_masks_nearest)
 from .lpips import (LpipsAlex, calculate_lpips, calculate_lpips_per_frame, get_lpips_model,  # noqa: F401

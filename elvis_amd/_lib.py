@@ -97,6 +97,8 @@ SIGNATURES = {
     "elvis_inpaint_workspace_bytes": [i32, i32, i32],
     "elvis_inpaint_prepare": [vp, i32, vp, i32, i32, i32, vp],
     "elvis_inpaint_fill": [vp, vp, i32, i32, i32, i32, vp, i32, vp],
+    "elvis_tfill_limits_ok": [i32, i32, i32, i32, i32, i32, i32, i32, i32],
+    "elvis_tfill": [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_block_complexity_f64": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_lpips_stem_u8": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_lpips_conv5_f32": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],

@@ -8,7 +8,9 @@
                                       Blur driver's shape
   stretch_shrunk_frames            <- the ELVIS v1 client-side stretch loop   (elvis.py:4534-4580)
   restore_shrunk_frames            <- the same loop and the CV2 inpaint loop after it (elvis.py:4534-4610), with the
-                                      build-defined wavefront Telea (inpaint.py) in cv2.inpaint's place
+                                      build-defined wavefront Telea (inpaint.py) in cv2.inpaint's place; with
+                                      inpainter="temporal" the slot of inpaint_with_propainter / inpaint_with_e2fgvi
+                                      (elvis.py:1458, 1693): the build-defined temporal fill (inpaint_temporal.py), then Telea
   calculate_removability_scores_from_frames
                                    <- calculate_removability_scores (elvis.py:968-1224) from frames and masks in memory,
                                       with the build-defined block complexity (complexity.py) in EVCA's place
@@ -45,7 +47,7 @@ from __future__ import annotations
 
 import multiprocessing
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
@@ -315,22 +317,34 @@ def _write_clip(clip: torch.Tensor, directory: str, names: Sequence[str], png_wr
 
 
 def _v1_shard(clip, maps, block_size, device, first_frame_index, inpaint=False, stretched_dir=None,
-              fullres_masks_dir=None, png_writer="pil", **kw):
+              fullres_masks_dir=None, png_writer="pil", inpainter="telea", inpaint_params=None, own=None, **kw):
     """Stretch a run of decoded shrunk frames in one launch pair and, with `inpaint`, fill their holes without leaving
     the device: the hole mask goes from the gather to the inpainter as a resident tensor.  The stretched frames and the
-    full-resolution masks are written only where a directory asks for them, under the global frame numbers."""
+    full-resolution masks are written only where a directory asks for them, under the global frame numbers.
+
+    `own` = (start, end), global frame numbers: the frames of the run that are this worker's (all of them when None);
+    the others are temporal context read for `inpainter="temporal"`.  Only the worker's own frames are written to the
+    side directories and go through the spatial inpainter; the context frames come back temporally filled at most, and
+    the worker drops them."""
     from .shrink import stretch_device
+    a, b = (0, len(clip)) if own is None else (own[0] - first_frame_index, own[1] - first_frame_index)
+    if not 0 <= a <= b <= len(clip):
+        raise ValueError(f"frames [{own[0]}, {own[1]}) are not in the run of {len(clip)} from {first_frame_index}")
     with torch.cuda.device(device):
         md = torch.from_numpy(np.ascontiguousarray(np.asarray(maps) != 0).view(np.uint8)).to(device)
         out, full = stretch_device(clip, md, block_size, "flat", fullres_mask=True)
-        names = [f"{first_frame_index + i + 1:05d}.png" for i in range(len(clip))]
+        names = [f"{first_frame_index + i + 1:05d}.png" for i in range(a, b)]
         if stretched_dir is not None:
-            _write_clip(out, stretched_dir, names, png_writer)
+            _write_clip(out[a:b], stretched_dir, names, png_writer)
         if fullres_masks_dir is not None:
-            _write_clip(full, fullres_masks_dir, names, png_writer)
+            _write_clip(full[a:b], fullres_masks_dir, names, png_writer)
         if inpaint:
             from .inpaint import inpaint_device
-            return inpaint_device(out, full, out=out)
+            if inpainter == "temporal":
+                from .inpaint_temporal import temporal_fill_device
+                out, full = temporal_fill_device(out, full, **(inpaint_params or {}))
+            if b > a:
+                inpaint_device(out[a:b], full[a:b], out=out[a:b])
         return out
 
 
@@ -535,11 +549,35 @@ def _v1_kw(png_writer: str, **dirs) -> dict:
     return dict(dirs, png_writer=png_writer) if png_writer != "pil" else dirs
 
 
+INPAINTERS = ("telea", "temporal")
+
+
+def _check_inpainter(inpainter, inpaint_params) -> dict:
+    """`inpainter=` of `restore_shrunk_frames`: "telea" (the wavefront Telea of inpaint.py alone, the default; it takes
+    no parameters) or "temporal" (inpaint_temporal.py: the temporal fill, then Telea on what is left; `inpaint_params`
+    are the fill's block, margin, radius, search, max_mad).  Returns the fill's parameters with the defaults filled in
+    ({} for "telea"); ValueError for anything else."""
+    if inpainter not in INPAINTERS:
+        raise ValueError(f"inpainter must be one of {INPAINTERS}, got {inpainter!r}")
+    if inpaint_params is not None and not isinstance(inpaint_params, dict):
+        raise ValueError(f"inpaint_params must be a dict or None, got {type(inpaint_params).__name__}")
+    if inpainter == "telea":
+        if inpaint_params:
+            raise ValueError(f"inpainter='telea' takes no inpaint_params, got {sorted(inpaint_params)}")
+        return {}
+    from .inpaint_temporal import check_params
+    return check_params("restore_shrunk_frames", **(inpaint_params or {}))
+
+
 def _run_v1(inpaint: bool, frames_dir: str, masks_npz: str, block_size: int, out_dir: str, block_masks_dir: Optional[str],
-            devices, png_writer: str, png_reader: str, _shard_fn: Optional[ShardFn], **dirs) -> np.ndarray:
+            devices, png_writer: str, png_reader: str, _shard_fn: Optional[ShardFn], inpainter: str = "telea",
+            inpaint_params: Optional[dict] = None, **dirs) -> np.ndarray:
     """What the two v1 drivers share: the checks, the directories (`dirs`: the ones the shard step writes, by keyword),
-    the block-resolution masks, and the stretch (and `inpaint`) of every frame of `frames_dir` into `out_dir`."""
+    the block-resolution masks, and the stretch (and `inpaint`) of every frame of `frames_dir` into `out_dir`.  With the
+    temporal inpainter every worker also reads `radius` frames on either side of its own, and its shard step is told
+    which frames are its own (`own`): no two workers write the same file."""
     _check_png_io(png_writer, png_reader)
+    params = _check_inpainter(inpainter, inpaint_params)
     masks, names = _v1_clip(frames_dir, masks_npz, block_size)
     for d in (out_dir, *dirs.values(), block_masks_dir):
         if d is not None:
@@ -551,8 +589,15 @@ def _run_v1(inpaint: bool, frames_dir: str, masks_npz: str, block_size: int, out
     gpus = [d for d in devs if d.type == "cuda"]
     workers = gpus or (devs if _shard_fn is not None else devs[:1])
     kw = _v1_kw(png_writer, **dirs)
-    _run_jobs(_png_jobs(_v1_shard, _shard_fn, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
-                        block_size, 0, kw if _shard_fn is not None else dict(kw, inpaint=inpaint), png_writer, png_reader))
+    temporal = inpainter == "temporal"
+    if temporal:
+        kw = dict(kw, inpainter=inpainter, inpaint_params=params)
+    jobs = _png_jobs(_v1_shard, _shard_fn, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
+                     block_size, params["radius"] if temporal else 0, kw if _shard_fn is not None else dict(kw, inpaint=inpaint),
+                     png_writer, png_reader)
+    if temporal:
+        jobs = [replace(job, kw=dict(job.kw, own=(job.start, job.end))) for job in jobs]
+    _run_jobs(jobs)
     return masks
 
 
@@ -593,6 +638,8 @@ def restore_shrunk_frames(
     *,
     png_writer: str = "pil",
     png_reader: str = "pil",
+    inpainter: str = "telea",
+    inpaint_params: Optional[dict] = None,
     _shard_fn: Optional[ShardFn] = None,
 ) -> np.ndarray:
     """The whole ELVIS v1 client side over a directory (elvis.py:4534-4610): unpack the removal masks of `masks_npz`,
@@ -603,11 +650,18 @@ def restore_shrunk_frames(
     (`stretched_dir`), the 0/255 masks at frame resolution (`fullres_masks_dir`) and at block resolution
     (`block_masks_dir`) are written only where a directory is given.  Validation and sharding are those of
     `stretch_shrunk_frames`: ValueError before anything is written, frames dealt by the `chunk_for_devices` rule,
-    one worker per GPU.  Returns the unpacked masks."""
+    one worker per GPU.  Returns the unpacked masks.
+
+    `inpainter="temporal"` stands where the reference runs its video inpainters (`inpaint_with_propainter` /
+    `inpaint_with_e2fgvi`, elvis.py:1458, 1693): the build-defined temporal fill of `inpaint_temporal.py` - neither of
+    those networks - takes what it can from the `radius` frames on either side, and the wavefront Telea fills the rest.
+    `inpaint_params` are that fill's block, margin, radius, search and max_mad.  Every worker reads `radius` extra
+    frames on either side of its own, so the result is the same for every device count.  Any other `inpainter` is a
+    ValueError, before anything is written."""
     if out_dir is None:
         raise ValueError("restore_shrunk_frames: out_dir is required")
     return _run_v1(True, frames_dir, masks_npz, block_size, out_dir, block_masks_dir, devices, png_writer, png_reader,
-                   _shard_fn, stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir)
+                   _shard_fn, inpainter, inpaint_params, stretched_dir=stretched_dir, fullres_masks_dir=fullres_masks_dir)
 
 
 # ----------------------------------------------------------------------------- clip files: decoder output in, encoder input out

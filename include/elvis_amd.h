@@ -303,7 +303,7 @@ int elvis_swin_proj_mlp(const void* attn, const void* y, void* out, const void* 
 
 /* Normalised instantiation name (e.g. "swin_fused_kernel<192,2,1,true>", "dcnv2_tile_kernel<7>") of the last kernel that
  * elvis_window_attention, elvis_swin_*, elvis_dcnv2, elvis_block_gather_u8, elvis_inpaint_prepare ("inpaint_scatter_kernel", its
- * last), elvis_inpaint_fill ("inpaint_fill_kernel<3>"; unchanged when it launches nothing), or an entry point of csrc/norm.hip / csrc/misc.hip
+ * last), elvis_inpaint_fill ("inpaint_fill_kernel<3>"; unchanged when it launches nothing), elvis_tfill ("tfill_kernel<3>"), or an entry point of csrc/norm.hip / csrc/misc.hip
  * (elvis_groupnorm_sums reports its gn_channel_sums_kernel, elvis_gn_partials_to_sums which of its two reductions it chose)
  * launched on the calling thread; "" before the first.  Static storage:
  * no allocation, no device synchronisation. */
@@ -548,6 +548,31 @@ int elvis_inpaint_prepare(const uint8_t* mask, int block_size, void* workspace, 
  * stay as they are.  wave_counts_host: HOST int32 [num_counts], the first num_counts entries of the workspace. */
 int elvis_inpaint_fill(uint8_t* frames, const void* workspace, int n, int h, int w, int c, const int32_t* wave_counts_host,
                        int num_counts, elvis_stream_t stream);
+
+/* ------------------------------------------------------------------ ELVIS v1 temporal fill (tfill.hip)
+ * The reference's v1 results come from trained video inpainters (inpaint_with_propainter / inpaint_with_e2fgvi,
+ * elvis.py:1458, 1693; utils.py:1395-1425; presley.py:854-885), which take a removed block's content from frames where
+ * the same scene point was not removed.  This is a BUILD-DEFINED restatement of the part of those methods that needs no
+ * training, in integers: for every block (size B, grid anchored at (0, 0)) of frame t that holds a hole pixel, the
+ * window of the block and a margin G is matched against the frames t-1, t+1, t-2, ... t+R over the (2S+1)^2
+ * displacements - mean absolute difference over the pixels known in both, exact comparison, ties to the earlier
+ * displacement in raster order, at least half of the window's known pixels compared, at most M a channel - and the
+ * best displacement's known pixels are copied under the hole.  "Known" is always the input mask and sources are always
+ * input bytes, so the result does not depend on any order.  It claims no parity with ProPainter or E2FGVI; DESIGN.md 7
+ * is the contract, tests/_tfill_ref.py states it in numpy and the kernel equals that bit for bit.  Holes it cannot fill
+ * are reported in `left`, the mask for elvis_inpaint_prepare. */
+
+/* Host only: 1 where elvis_tfill takes the shape and the parameters, 0 otherwise: n, h, w >= 1, c in {1, 3},
+ * h, w <= 32767, n * h * w * c < 2^31, B in 1..32, G in 0..16, R in 0..8, S in 0..7, M in 0..255. */
+int elvis_tfill_limits_ok(int n, int h, int w, int c, int B, int G, int R, int S, int M);
+
+/* frames u8 [n, h, w, c]; masks u8, non-zero = hole: [n, h, w] with block_mask_size 0, or [n, h / block_mask_size,
+ * w / block_mask_size] expanded over whole blocks as for elvis_inpaint_prepare.  out u8 [n, h, w, c]: the frames with
+ * the filled pixels (every byte is written; known pixels and pixels under remaining holes get the input's bytes).
+ * left u8 [n, h, w]: 255 where a hole stayed unfilled, 0 elsewhere.  out and left may alias neither each other nor an
+ * input.  Everything outside the limits is refused before the launch of tfill_kernel<c>. */
+int elvis_tfill(const uint8_t* frames, const uint8_t* masks, int block_mask_size, uint8_t* out, uint8_t* left, int n,
+                int h, int w, int c, int B, int G, int R, int S, int M, elvis_stream_t stream);
 
 /* ------------------------------------------------------------------ block complexity (complexity.hip)
  * The first server-side stage: the per-block spatial (SC) and temporal (TC) complexity maps that the reference takes
