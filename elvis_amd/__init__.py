@@ -52,6 +52,8 @@ from .restore import (get_sinsr_model, get_sinsr_upsample_fn, restore_frames_blu
 from .restore import (get_realesrgan_upsample_fn, get_realesrgan_upsampler, restore_frames_realesrgan,  # noqa: F401
                       restore_frames_realesrgan_device, restore_with_realesrgan_naive)
 from .drivers import restore_downsampled_with_realesrgan  # noqa: F401
+from .enhance import (RealESRGANer, lanczos4_resize_taps, plan_tiles, reflect_index_maps, resize_lanczos4_device,  # noqa: F401
+                      upscale_with_realesrgan)
 from .weights import RRDBNetConfig, load_realesrgan_state_dict  # noqa: F401
 from .weights import SRVGGConfig, dni_state_dicts, load_srvgg_state_dict  # noqa: F401
 

@@ -422,6 +422,7 @@ def restore_downsampled_with_realesrgan(
     png_writer: str = "pil",
     png_reader: str = "pil",
     _shard_fn: Optional[ShardFn] = None,
+    enhance: str = "area",
 ) -> None:
     """Adaptive Real-ESRGAN restoration over a directory of frames: the reference's function of this name
     (elvis.py:2685-2769) with its own networks, RRDBNet or SRVGGNetCompact by `model_name`, in the model slot
@@ -429,14 +430,16 @@ def restore_downsampled_with_realesrgan(
     `denoise_strength` is honoured for `realesr-general-x4v3` and refused elsewhere).  `model_path` is the checkpoint
     file (e.g. "RealESRGAN_x4plus.pth"; for `denoise_strength != 1` a pair of files, or one with
     `realesr-general-wdn-x4v3.pth` beside it); without it the weights are seeded and synthetic.
-    `parallel_chunk_length` / `per_device_workers` are accepted and ignored, as in the reference (elvis.py:2698-2699)."""
+    `parallel_chunk_length` / `per_device_workers` are accepted and ignored, as in the reference (elvis.py:2698-2699).
+    `enhance="reference"` (default "area"): `tile`, `tile_pad` and `pre_pad` are honoured and every stage resizes with
+    Lanczos4, as `restore.restore_frames_realesrgan` describes."""
     _ = (parallel_chunk_length, per_device_workers)
     _check_png_io(png_writer, png_reader)
     if _shard_fn is None:
         from .restore import _check_realesrgan_args
-        _check_realesrgan_args(denoise_strength, pre_pad, fp32, model_name)
+        _check_realesrgan_args(denoise_strength, pre_pad, fp32, model_name, enhance)
     kw = dict(model_name=model_name, denoise_strength=denoise_strength, tile=tile, tile_pad=tile_pad, pre_pad=pre_pad,
-              fp32=fp32, model_path=model_path, schedule=schedule)
+              fp32=fp32, model_path=model_path, schedule=schedule, enhance=enhance)
     _restore_downsampled(_realesrgan_clip_shard, kw, input_frames_dir, output_frames_dir, downscale_maps, block_size, devices,
                          png_writer, png_reader, _shard_fn)
 

@@ -327,17 +327,24 @@ def restore_with_sinsr_naive(frames: List[np.ndarray], device="cuda", seed: int 
 
 
 # ----------------------------------------------------------------------------- Real-ESRGAN in the Downsample slot
-def _check_realesrgan_args(denoise_strength, pre_pad, fp32, model_name=None):
+ENHANCE_MODES = ("area", "reference")
+
+
+def _check_realesrgan_args(denoise_strength, pre_pad, fp32, model_name=None, enhance: str = "area"):
     """The departures from the reference call: each is refused, none is silently ignored.  With `model_name` the name is
     checked too and its configuration returned (`weights.RRDBNetConfig` or `weights.SRVGGConfig`); `denoise_strength`
     other than 1 (`math.isclose`, as elvis.py:2472) is taken for `realesr-general-x4v3` alone, the one model the
-    reference applies it to."""
+    reference applies it to.  `pre_pad` is taken with `enhance="reference"` alone."""
     from .weights import REALESRGAN_SRVGG_MODELS, SRVGG_DNI_MODEL, realesrgan_config, srvgg_config
+    if enhance not in ENHANCE_MODES:
+        raise ValueError(f"Real-ESRGAN: enhance must be one of {ENHANCE_MODES}, got {enhance!r}")
     if fp32:
         raise ValueError("Real-ESRGAN: fp32=True is not built; the network runs in f16 with fp32 accumulation "
                          "(the reference's GPU precision, half=True)")
-    if int(pre_pad) != 0:
-        raise ValueError(f"Real-ESRGAN: pre_pad={pre_pad} is not built; only pre_pad=0")
+    if int(pre_pad) != 0 and enhance != "reference":
+        raise ValueError(f"Real-ESRGAN: pre_pad={pre_pad} is not built; only pre_pad=0 (or enhance=\"reference\")")
+    if int(pre_pad) < 0:
+        raise ValueError(f"Real-ESRGAN: pre_pad={pre_pad} must not be negative")
     name = None if model_name is None else str(model_name).split(".")[0]
     s = float(denoise_strength)
     if not math.isclose(s, 1.0):
@@ -434,6 +441,26 @@ def get_realesrgan_upsampler(device, *, model_name: str = "RealESRGAN_x4plus", d
     return _cached_model("Real-ESRGAN", device, (cfg, s, ident), None, make)
 
 
+def _realesrgan_model(device, enhance: str, *, model_name, denoise_strength, tile, tile_pad, pre_pad, fp32, model_path=None,
+                      state_dict=None):
+    """The cached model of a Real-ESRGAN call, its arguments checked for the mode: `pre_pad != 0` is refused with
+    `enhance="area"` and taken with `enhance="reference"`."""
+    _check_realesrgan_args(denoise_strength, pre_pad, fp32, model_name, enhance)
+    _ = (tile, tile_pad)
+    return get_realesrgan_upsampler(device, model_name=model_name, denoise_strength=denoise_strength, fp32=fp32,
+                                    model_path=model_path, state_dict=state_dict)
+
+
+def _realesrgan_enhancer(device, enhance: str, **kw):
+    """(model, enhancer) of a Real-ESRGAN call: with `enhance="area"` the cached model and None - `tile` / `tile_pad` ignored,
+    `pre_pad != 0` refused; with `enhance="reference"` the model inside an `enhance.RealESRGANer` that honours all three."""
+    model = _realesrgan_model(device, enhance, **kw)
+    if enhance == "area":
+        return model, None
+    from .enhance import RealESRGANer
+    return model, RealESRGANer(model, tile=kw["tile"], tile_pad=kw["tile_pad"], pre_pad=kw["pre_pad"])
+
+
 def _realesrgan_up(model, cur: torch.Tensor, swap_rb: bool = True) -> torch.Tensor:
     try:
         return model.forward(cur, swap_rb=swap_rb)
@@ -441,13 +468,22 @@ def _realesrgan_up(model, cur: torch.Tensor, swap_rb: bool = True) -> torch.Tens
         raise RuntimeError(f"Real-ESRGAN failed on {model.device}: {exc}") from exc
 
 
-def get_realesrgan_upsample_fn(device, *, model_name: str = "RealESRGAN_x4plus", scale: int = 2, **kw) -> Callable[[np.ndarray], np.ndarray]:
+def get_realesrgan_upsample_fn(device, *, model_name: str = "RealESRGAN_x4plus", scale: int = 2, enhance: str = "area",
+                               **kw) -> Callable[[np.ndarray], np.ndarray]:
     """P1: "a single 2x upscale" of a BGR uint8 HWC image (elvis.py:2528, 2575), what `enhance(img, outscale=scale)`
     returns.  An x2 model at scale=2 and an x4 model at scale=4 return the network's output; an x4 model at scale=2
-    area-halves it, where `enhance` resizes with cv2.INTER_LANCZOS4 (PARITY UNPINNED vs cv2)."""
-    model = get_realesrgan_upsampler(device, model_name=model_name, **kw)
+    area-halves it, where `enhance` resizes with cv2.INTER_LANCZOS4 (PARITY UNPINNED vs cv2).  `enhance="reference"`:
+    the function is `enhance.RealESRGANer(...).enhance(img, outscale=scale)` itself - Lanczos4, `tile`, `tile_pad`, `pre_pad`."""
+    if enhance != "area":
+        args = dict(denoise_strength=1.0, tile=0, tile_pad=10, pre_pad=0, fp32=False)
+        args.update(kw)
+        model, enh = _realesrgan_enhancer(device, enhance, model_name=model_name, **args)
+    else:
+        model, enh = get_realesrgan_upsampler(device, model_name=model_name, **kw), None
     if scale not in (2, 4) or scale > model.scale:
         raise ValueError(f"scale must be 2 or 4 and at most the model's {model.scale}, got {scale!r}")
+    if enh is not None:
+        return lambda img: enh.enhance(img, outscale=scale)[0]
 
     def upsample_fn(img: np.ndarray) -> np.ndarray:
         with torch.cuda.device(model.device):
@@ -462,11 +498,13 @@ def get_realesrgan_upsample_fn(device, *, model_name: str = "RealESRGAN_x4plus",
 def restore_frames_realesrgan_device(frames_d: torch.Tensor, downscale_maps, block_size: int, *,
                                      model_name: str = "RealESRGAN_x4plus", denoise_strength: float = 1.0, tile: int = 0,
                                      tile_pad: int = 10, pre_pad: int = 0, fp32: bool = False, model_path=None,
-                                     state_dict=None, schedule: str = "staged", **_ignored) -> torch.Tensor:
+                                     state_dict=None, schedule: str = "staged", enhance: str = "area",
+                                     **_ignored) -> torch.Tensor:
     """`restore_frames_realesrgan` on a resident clip: [n,H,W,3] u8 BGR on the device and the host maps in, the
     restored resident clip out, on the clip's device; no pixel visits the host."""
-    model = get_realesrgan_upsampler(frames_d.device, model_name=model_name, denoise_strength=denoise_strength, tile=tile,
-                                     tile_pad=tile_pad, pre_pad=pre_pad, fp32=fp32, model_path=model_path, state_dict=state_dict)
+    model, enh = _realesrgan_enhancer(frames_d.device, enhance, model_name=model_name, denoise_strength=denoise_strength,
+                                      tile=tile, tile_pad=tile_pad, pre_pad=pre_pad, fp32=fp32, model_path=model_path,
+                                      state_dict=state_dict)
     if schedule not in ("staged", "single4x"):
         raise ValueError(f"unknown schedule '{schedule}'")
     if schedule == "single4x" and model.scale != 4:
@@ -487,7 +525,8 @@ def restore_frames_realesrgan_device(frames_d: torch.Tensor, downscale_maps, blo
             if idx:
                 it = torch.tensor(idx, device=model.device)
                 sub_f, sub_m = frames_d[it].contiguous(), maps_d[it].contiguous()
-                sr = _realesrgan_up(model, ops.area_downscale_u8(sub_f, 4))
+                lr = ops.area_downscale_u8(sub_f, 4)
+                sr = _realesrgan_up(model, lr) if enh is None else enh.enhance_device(lr)
                 out[it] = ops.recompose_u8(sub_f, sr, sub_m, block_size, 0)
             return out
         # the reference derives the stage schedule from each frame's own max level (elvis.py:2561): group frames by it
@@ -497,15 +536,19 @@ def restore_frames_realesrgan_device(frames_d: torch.Tensor, downscale_maps, blo
                 out[idx] = frames_d[idx]
                 continue
             it = torch.tensor(idx, device=model.device)
-            out[it] = upscale_adaptive_device(frames_d[it].contiguous(), maps_d[it].contiguous(), block_size,
-                                              lambda cur: _realesrgan_up(model, cur), sr_scale=model.scale)
+            if enh is None:
+                out[it] = upscale_adaptive_device(frames_d[it].contiguous(), maps_d[it].contiguous(), block_size,
+                                                  lambda cur: _realesrgan_up(model, cur), sr_scale=model.scale)
+            else:       # elvis.py:2515 per stage: enhance(img, outscale=2), whatever the network's scale
+                out[it] = upscale_adaptive_device(frames_d[it].contiguous(), maps_d[it].contiguous(), block_size,
+                                                  lambda cur: enh.enhance_device(cur, outscale=2), sr_scale=2)
         return out
 
 
 def restore_frames_realesrgan(frames: List[np.ndarray], downscale_maps: np.ndarray, block_size: int, device, *,
                               model_name: str = "RealESRGAN_x4plus", denoise_strength: float = 1.0, tile: int = 0,
                               tile_pad: int = 10, pre_pad: int = 0, fp32: bool = False, model_path=None, state_dict=None,
-                              schedule: str = "staged", **_ignored) -> List[np.ndarray]:
+                              schedule: str = "staged", enhance: str = "area", **_ignored) -> List[np.ndarray]:
     """The reference's `restore_frames_realesrgan` (elvis.py:2640-2682) with the networks it runs there - RRDBNet, or
     SRVGGNetCompact for `realesr-animevideov3` / `realesr-general-x4v3` (x4 models) - on the device: BGR uint8 frames +
     per-block log2 downscale maps -> restored frames.  Host to host around `restore_frames_realesrgan_device`.
@@ -520,27 +563,36 @@ def restore_frames_realesrgan(frames: List[np.ndarray], downscale_maps: np.ndarr
     ones; nothing is downloaded.  `tile` / `tile_pad` are accepted and ignored (whole frames fit); `fp32=True` and
     `pre_pad != 0` are a ValueError.  `denoise_strength != 1` blends two weight sets for `realesr-general-x4v3`
     (`get_realesrgan_upsampler`) and is a ValueError for every other model.  A runtime failure is
-    `RuntimeError("Real-ESRGAN failed on <device>: ...")` (elvis.py:2517-2519)."""
+    `RuntimeError("Real-ESRGAN failed on <device>: ...")` (elvis.py:2517-2519).
+
+    `enhance="reference"` (the default "area" is everything above): every stage is `enhance.RealESRGANer.enhance_device(cur,
+    outscale=2)` with `sr_scale=2`, as elvis.py:2515 - `tile`, `tile_pad` and `pre_pad` are honoured as the `realesrgan`
+    package applies them, and an x4 model's output is resized to 2x with Lanczos4 (cv2's 8-bit rule) instead of area-halved."""
     kw = dict(model_name=model_name, denoise_strength=denoise_strength, tile=tile, tile_pad=tile_pad, pre_pad=pre_pad,
               fp32=fp32, model_path=model_path, state_dict=state_dict)
-    return _host_to_host(frames, lambda: get_realesrgan_upsampler(device, **kw).device, restore_frames_realesrgan_device,
-                         downscale_maps, block_size, schedule=schedule, **kw)
+    return _host_to_host(frames, lambda: _realesrgan_model(device, enhance, **kw).device, restore_frames_realesrgan_device,
+                         downscale_maps, block_size, schedule=schedule, enhance=enhance, **kw)
 
 
 def restore_with_realesrgan_naive(frames: List[np.ndarray], device="cuda", model_name: str = "RealESRGAN_x4plus",
                                   tile: int = 0, tile_pad: int = 10, pre_pad: int = 0, fp32: bool = False,
-                                  denoise_strength: float = 1.0, **kwargs) -> List[np.ndarray]:
+                                  denoise_strength: float = 1.0, enhance: str = "area", **kwargs) -> List[np.ndarray]:
     """P3 restore_fn (utils.py:1428-1473): RGB uint8 frames, each upscaled by the network and brought back to its own
     size - by an area downscale where the reference resizes with cv2.INTER_LANCZOS4 (PARITY UNPINNED vs cv2).
-    `model_path=` / `state_dict=` choose the weights; other unknown keywords are accepted and ignored."""
+    `model_path=` / `state_dict=` choose the weights; other unknown keywords are accepted and ignored.
+    `enhance="reference"`: `enhance(frame, outscale=4)` with `tile`, `tile_pad` and `pre_pad` honoured, then the
+    Lanczos4 resize back to (w, h) of utils.py:1465-1466."""
     if not frames:
         return []
     dev = L.resolve_device(device)
-    model = get_realesrgan_upsampler(dev, model_name=model_name, denoise_strength=denoise_strength, tile=tile,
-                                     tile_pad=tile_pad, pre_pad=pre_pad, fp32=fp32, model_path=kwargs.get("model_path"),
-                                     state_dict=kwargs.get("state_dict"))
+    model, enh = _realesrgan_enhancer(dev, enhance, model_name=model_name, denoise_strength=denoise_strength, tile=tile,
+                                      tile_pad=tile_pad, pre_pad=pre_pad, fp32=fp32, model_path=kwargs.get("model_path"),
+                                      state_dict=kwargs.get("state_dict"))
     with torch.cuda.device(model.device):
         d = frames_to_device(frames, model.device)
+        if enh is not None:
+            from .enhance import resize_lanczos4_device
+            return frames_to_host(resize_lanczos4_device(enh.enhance_device(d, outscale=4, swap_rb=False), d.shape[1], d.shape[2]))
         return frames_to_host(ops.area_downscale_u8(_realesrgan_up(model, d, swap_rb=False), model.scale))
 
 

@@ -948,6 +948,47 @@ int elvis_srvgg_conv3x3(const void* x, int x_pitch, const void* w_packed, const 
 int elvis_srvgg_tail(const void* x, int x_pitch, const void* w_packed, const float* bias, const void* base, int base_pitch,
                      void* out, int n, int h, int w, int out_u8, int swap_rb, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ RealESRGANer.enhance around the network
+ * csrc/sr_enhance.hip.  Tables come in a host copy (`*_h`, validated before the launch) and a device copy (read by
+ * the kernel, which clamps whatever it reads from it into range). */
+
+/* cv2.resize(src, (wd, hd), interpolation=cv2.INTER_LANCZOS4) of 8-bit frames: the resize to `outscale` inside
+ * RealESRGANer.enhance (elvis.py:2515, presley.py:1308) and the resize back to (w, h) after it (utils.py:1466,
+ * presley.py:1309).  src u8 [n,hs,ws,c], dst u8 [n,hd,wd,c], c in 1..4, any ratio.  Per destination column d:
+ * xfirst[d] (the first of eight source columns, before the BORDER_REPLICATE clamp to [0, ws-1]) and xtaps[d][8] int16
+ * (rint(coef * 2048)); rows likewise.  dst = saturate((sum_ky sum_kx p * tx * ty + 2^21) >> 22), exact in int32 when
+ * the caller's tap sums keep 255 * (Px*Py + Nx*Ny) + 2^21 below 2^31.  One launch; a workgroup owns a th x tw
+ * destination tile and keeps its source footprint and the int32 intermediate in at most 64 KiB of LDS.
+ * ELVIS_E_INVALID: a null pointer, a non-positive size, c outside 1..4, a first index outside [-4, size-4] or a
+ * decreasing table, tap tables not 16-byte aligned, or a tile whose footprint exceeds the LDS limit.
+ * elvis_last_launch: "resize_lanczos4_u8_kernel<c>". */
+int elvis_resize_lanczos4_u8(const uint8_t* src, uint8_t* dst, int n, int hs, int ws, int hd, int wd, int c,
+                             const int32_t* xfirst_h, const int32_t* yfirst_h, const int32_t* xfirst,
+                             const int16_t* xtaps, const int32_t* yfirst, const int16_t* ytaps, int th, int tw,
+                             elvis_stream_t stream);
+/* Host only: the bytes of LDS a workgroup of elvis_resize_lanczos4_u8 needs for th x tw destination tiles of these
+ * tables (the same validation; ELVIS_E_INVALID = -1 on a bad argument). */
+int elvis_resize_lanczos4_lds_bytes(const int32_t* xfirst_h, const int32_t* yfirst_h, int hs, int ws, int hd, int wd,
+                                    int c, int th, int tw);
+
+/* The padded input boxes of RealESRGANer.tile_process (the `input_tile` slice), all of one shape:
+ * dst[t, y, x] = src[frame_t, rowmap[y0_t + y], colmap[x0_t + x]] with desc int32 [T][3] = (frame, y0, x0).  rowmap
+ * int32 [Hp] and colmap int32 [Wp] map the padded image to the frame: the F.pad(..., (0, pre_pad, 0, pre_pad),
+ * 'reflect') of pre_process, then for an x2 network its reflect pad to an even size.  src u8 [n,H,W,3], dst u8
+ * [T,th,tw,3].  ELVIS_E_INVALID: a null pointer, a non-positive size, a map entry outside the frame, a tile outside
+ * the padded image or naming a frame outside [0, n).  elvis_last_launch: "sr_gather_tiles_u8_kernel". */
+int elvis_sr_gather_tiles_u8(const uint8_t* src, uint8_t* dst, int n, int H, int W, int T, int th, int tw,
+                             const int32_t* desc_h, const int32_t* desc, const int32_t* rowmap_h, const int32_t* rowmap,
+                             int Hp, const int32_t* colmap_h, const int32_t* colmap, int Wp, elvis_stream_t stream);
+
+/* The paste of tile_process (`self.output[...] = output_tile[...]`) and the crop of post_process: tiles u8
+ * [T,tth,ttw,3] (the network's output per tile), desc int32 [T][7] = (frame, crop y, crop x inside the tile,
+ * destination y, x, crop height, width); dst u8 [n,OH,OW,3] receives each crop, clipped at OH x OW (the pre_pad and
+ * mod-pad removal).  ELVIS_E_INVALID: a null pointer, a non-positive size, a crop outside its tile, a negative
+ * destination, a frame outside [0, n).  elvis_last_launch: "sr_paste_tiles_u8_kernel". */
+int elvis_sr_paste_tiles_u8(const uint8_t* tiles, uint8_t* dst, int T, int tth, int ttw, int n, int OH, int OW,
+                            const int32_t* desc_h, const int32_t* desc, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
