@@ -99,6 +99,9 @@ SIGNATURES = {
     "elvis_inpaint_fill": [vp, vp, i32, i32, i32, i32, vp, i32, vp],
     "elvis_tfill_limits_ok": [i32, i32, i32, i32, i32, i32, i32, i32, i32],
     "elvis_tfill": [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_segment_workspace_bytes": [i32, i32, i32, i32],
+    "elvis_segment_foreground_u8": [vp, vp, i32, vp, i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                    i32, i32, vp],
     "elvis_block_complexity_f64": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_lpips_stem_u8": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_lpips_conv5_f32": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
@@ -174,6 +177,7 @@ def lib() -> C.CDLL:
         handle.elvis_ssim_workspace_bytes.restype = C.c_size_t
         handle.elvis_inpaint_workspace_bytes.restype = C.c_size_t
         handle.elvis_lpips_distance_workspace_bytes.restype = C.c_size_t
+        handle.elvis_segment_workspace_bytes.restype = C.c_size_t
         handle.elvis_rrdb_packed_weight_bytes.restype = C.c_size_t
         handle.elvis_srvgg_packed_weight_bytes.restype = C.c_size_t
         handle.elvis_vmaf_workspace_bytes.restype = C.c_size_t

@@ -771,3 +771,19 @@ def calculate_removability_scores_from_frames(frames, foreground_masks, block_si
     from .complexity import EVCAConfig, analyze_frames, removability_from_complexity
     maps = analyze_frames(frames, EVCAConfig(block_size=block_size), device, order=order, chunk_frames=chunk_frames)
     return removability_from_complexity(maps.SC, maps.TC, foreground_masks, alpha, smoothing_beta)
+
+
+def calculate_removability_scores_device(frames, block_size: int, alpha: float = 0.5, smoothing_beta: float = 1, device="cuda:0",
+                                         *, order: str = "bgr", cfg=None, chunk_frames: Optional[int] = None,
+                                         return_masks: bool = False):
+    """`calculate_removability_scores_from_frames` with the foreground masks made here too: `segment_frames` in UFO's
+    place (elvis.py:1057-1158), then the existing function with those masks - decoded frames to removability scores
+    without an outside program.  `cfg`: a `segment.SegmentConfig`.  Returns the scores, float64 [F, H // block_size,
+    W // block_size]; with `return_masks=True` the pair (scores, masks uint8 [F,H,W] of 0 / 1).
+    THE MASKS ARE NOT UFO'S: the segmenter is build-defined, its defaults untuned and unmeasured on real video
+    (segment.py), as the complexity maps are not EVCA's pixels."""
+    from .segment import segment_frames
+    masks = segment_frames(frames, device, order=order, cfg=cfg, chunk_frames=chunk_frames)
+    scores = calculate_removability_scores_from_frames(frames, list(masks), block_size, alpha, smoothing_beta, device, order=order,
+                                                       chunk_frames=chunk_frames)
+    return (scores, masks) if return_masks else scores

@@ -574,6 +574,38 @@ int elvis_tfill_limits_ok(int n, int h, int w, int c, int B, int G, int R, int S
 int elvis_tfill(const uint8_t* frames, const uint8_t* masks, int block_mask_size, uint8_t* out, uint8_t* left, int n,
                 int h, int w, int c, int B, int G, int R, int S, int M, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ foreground masks (segment.hip)
+ * The reference takes its foreground masks from UFO, a trained video salient-object network (presley.py:203
+ * `segment_frames(frames, device=device)`; elvis.py:1187 reads its mask files).  Neither UFO's architecture nor its weights
+ * are available to this build, so this is a BUILD-DEFINED, training-free segmenter behind that call surface and it claims
+ * no parity with UFO.  On the 1/4-resolution grid (Ry = h / 4, Rx = w / 4, P = Ry * Rx; Y, U, V of i420.h summed over
+ * 4 x 4 pixels): the global shift in [-R, R]^2 against the previous frame (the first frame: the next) by 64-bit SAD over
+ * the common window, ties to the least (dy*dy + dx*dx, dy, dx); the motion residual (3 x 3 min, 3 x 3 sum) and the least
+ * colour distance to the means of the four border strips, each scaled to 0..255 by max(its maximum, its floor); their
+ * weighted mean, a 5 x 5 mean, Otsu's threshold in float64 (none where the peak is below min_peak); close, open and
+ * `dilation` dilations; 2 of 3 over t - 1, t, t + 1; all ones where the share is 0 or above max_share; x 4 nearest.
+ * tests/_segment_ref.py states every stage in numpy and the kernels equal it bit for bit.
+ *
+ * The extended clip is before (n_before in 0..2 frames) + frames (n) + after (n_after in 0..1), m frames of [h, w, c] u8,
+ * c in {1, 3} (bgr: the channel order of c == 3).  Frame e > 0 of it is paired with e - 1, frame 0 with frame 1; with two
+ * frames before, the first is a partner only.  m <= 4096, 4 <= h, w <= 16384, Ry and Rx >= 2 * radius + 1, radius in
+ * 0..16, dilation in 0..4, weights in 1..1024, floors >= 1, min_peak in 0..255, share_num = max_share * 10000 in 1..10000.
+ *
+ * The workspace (device, 8-byte aligned, caller-owned) holds every intermediate, each section at the next multiple of
+ * 256 bytes, in this order, with D = 2 * radius + 1:
+ *   red u16 [m][3][P] | sad u64 [m][D*D] | maxima i32 [m][2] | hist u32 [m][256] | count u32 [m] | shift i32 [m][2] |
+ *   means i32 [m][4][3] | M u16 [m][P] | S u16 [m][P] | Mn u8 [m][P] | Sn u8 [m][P] | F u8 [m][P] | thr i32 [m] |
+ *   pre u8 [m][P] (the mask before the vote) | voted u8 [m][P] (the first n frames)
+ * elvis_segment_workspace_bytes returns their total, 0 for a shape the entry point refuses. */
+size_t elvis_segment_workspace_bytes(int m, int h, int w, int radius);
+
+/* masks u8 [n, h, w] of 0 / 1.  Ten launches (eight for a clip of one frame, which has no motion term) and one memset
+ * on `stream`, nothing read back; the last launch is seg_upsample_kernel.  The inputs are not written. */
+int elvis_segment_foreground_u8(const uint8_t* frames, const uint8_t* before, int n_before, const uint8_t* after, int n_after,
+                                uint8_t* masks, void* workspace, long long workspace_bytes, int n, int h, int w, int c, int bgr,
+                                int radius, int motion_weight, int spatial_weight, int motion_floor, int spatial_floor,
+                                int min_peak, int dilation, int share_num, int temporal_vote, elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ block complexity (complexity.hip)
  * The first server-side stage: the per-block spatial (SC) and temporal (TC) complexity maps that the reference takes
  * from EVCA - elvis.py:968-1224 runs it as a subprocess and reads evca_SC_blocks.csv / evca_TC_blocks.csv,
