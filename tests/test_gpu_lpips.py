@@ -112,6 +112,14 @@ def test_maxpool_is_bit_exact(gpu_device, n, h, w, c):
     assert torch.equal(view.cpu(), want) and guards_intact(full)
 
 
+def distance_tolerance(xd, yd, lin):
+    """The bound of test_distance_per_tap (its docstring derives it) for float64 NCHW features and one tap's weights."""
+    xh = xd / (torch.sqrt((xd * xd).sum(1, keepdim=True)) + 1e-10)
+    yh = yd / (torch.sqrt((yd * yd).sum(1, keepdim=True)) + 1e-10)
+    d = (xh - yh).abs()
+    return (32 * CR.U24 * ((d * (xh.abs() + yh.abs()) + d * d) * lin.double()[None, :, None, None]).sum(1).mean((1, 2))).numpy()
+
+
 @pytest.mark.parametrize("tap", range(5))
 def test_distance_per_tap(model, gpu_device, tap):
     """Bound: xh carries at most ~9 roundings of 2^-24 (the sum of squares: a chain of up to 6 and 6 butterfly steps, halved
@@ -132,10 +140,7 @@ def test_distance_per_tap(model, gpu_device, tap):
     got = view.cpu().numpy().copy()
     xd, yd = x.permute(0, 3, 1, 2).double(), y.permute(0, 3, 1, 2).double()
     want = R.tap_distance(xd, yd, lin).numpy()
-    xh = xd / (torch.sqrt((xd * xd).sum(1, keepdim=True)) + 1e-10)
-    yh = yd / (torch.sqrt((yd * yd).sum(1, keepdim=True)) + 1e-10)
-    d = (xh - yh).abs()
-    tol = (32 * CR.U24 * ((d * (xh.abs() + yh.abs()) + d * d) * lin.double()[None, :, None, None]).sum(1).mean((1, 2))).numpy()
+    tol = distance_tolerance(xd, yd, lin)
     print(f"tap {tap}: got {got}, want {want}, |err| / tol = {np.abs(got - want) / tol}")
     assert (np.abs(got - want) <= tol).all()
     lpips.distance_device(x.to(gpu_device), y.to(gpu_device), c, model.lin[tap], view, accumulate=True)
