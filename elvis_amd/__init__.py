@@ -56,6 +56,9 @@ from .restore import (get_realesrgan_upsample_fn, get_realesrgan_upsampler, rest
 from .drivers import restore_downsampled_with_realesrgan  # noqa: F401
 from .enhance import (RealESRGANer, lanczos4_resize_taps, plan_tiles, reflect_index_maps, resize_lanczos4_device,  # noqa: F401
                       upscale_with_realesrgan)
+from .intake import (intake_device, load_clip_device, resize_area, resize_area_device, resize_area_plan,  # noqa: F401
+                     resize_masks_nearest_device, resize_nearest_device)
+from .drivers import analyze_clip_file  # noqa: F401
 from .weights import RRDBNetConfig, load_realesrgan_state_dict  # noqa: F401
 from .weights import SRVGGConfig, dni_state_dicts, load_srvgg_state_dict  # noqa: F401
 

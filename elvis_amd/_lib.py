@@ -140,6 +140,8 @@ SIGNATURES = {
     "elvis_resize_lanczos4_lds_bytes": [vp, vp, i32, i32, i32, i32, i32, i32, i32],
     "elvis_sr_gather_tiles_u8": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp],
     "elvis_sr_paste_tiles_u8": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "elvis_resize_area_u8": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "elvis_resize_nearest_u8": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_dcnv2": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_temporal_stack": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_plane_merge": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],

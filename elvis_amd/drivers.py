@@ -787,3 +787,17 @@ def calculate_removability_scores_device(frames, block_size: int, alpha: float =
     scores = calculate_removability_scores_from_frames(frames, list(masks), block_size, alpha, smoothing_beta, device, order=order,
                                                        chunk_frames=chunk_frames)
     return (scores, masks) if return_masks else scores
+
+
+def analyze_clip_file(path: str, width: int, height: int, block_size: int, alpha: float = 0.5, smoothing_beta: float = 1,
+                      device="cuda:0", **load_kw):
+    """From a source file to removability scores: `intake.load_clip_device(path, width, height, device, **load_kw)` -
+    the `.y4m` or raw `.yuv` clip decoded, strided, capped and INTER_AREA-resized to the working size on the device
+    (presley.py:177-198) - then `calculate_removability_scores_device` on that clip, in the `order` the clip was loaded
+    in ("rgb" unless `load_kw` says otherwise).  `load_kw`: `src_width`, `src_height`, `frame_stride`, `max_frames`,
+    `order`, `chunk_frames`.  The working-size clip comes down once: the analysis functions take host clips and upload
+    them in their own chunks.  Returns float64 [k, height // block_size, width // block_size]."""
+    from .intake import load_clip_device
+    clip_d, _ = load_clip_device(path, width, height, device, **load_kw)
+    return calculate_removability_scores_device(clip_d.cpu().numpy(), block_size, alpha, smoothing_beta, device,
+                                                order=load_kw.get("order", "rgb"))

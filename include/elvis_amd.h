@@ -1021,6 +1021,38 @@ int elvis_sr_gather_tiles_u8(const uint8_t* src, uint8_t* dst, int n, int H, int
 int elvis_sr_paste_tiles_u8(const uint8_t* tiles, uint8_t* dst, int T, int tth, int ttw, int n, int OH, int OW,
                             const int32_t* desc_h, const int32_t* desc, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ clip intake (csrc/resize.hip) */
+
+/* cv2.resize(frame, (wd, hd), interpolation=cv2.INTER_AREA) of every frame of a clip: the resize to the working size
+ * that Presley applies to each decoded frame before anything else reads it (presley.py:186).  src u8 [n,hs,ws,c], dst u8
+ * [n,hd,wd,c], c in {1, 3, 4}, hd <= hs and wd <= ws, any ratio >= 1 on each axis, one launch.  Per axis the table of
+ * cv::computeResizeAreaTab in three arrays: start int32 [dst + 1] (the entries of destination d are start[d] ..
+ * start[d + 1]), first int32 [dst] (the source index of d's first entry; its entries are consecutive source indices)
+ * and w float32 [start[dst]].  start and first come in a host copy (`*_h`, validated before the launch) and a device
+ * copy (read by the kernel); w on the device only.
+ *   hs == fy * hd and ws == fx * wd: the integer box sum s; dst = s at 1x1, (s + 2) >> 2 at 2x2, otherwise
+ *     rint(float(s) * float(1.0 / (fx * fy))), half to even; w is not read.
+ *   otherwise cv::ResizeArea_<uchar, float>, on both axes: buf = sum_x S[sy][sx] * xw, sum = sum_y yw * buf, float32
+ *     from 0 in table order, every product and every sum rounded on its own; dst = clip(rint(sum), 0, 255).
+ * A workgroup owns th x tw destination pixels (th * tw * c <= 1024) and streams the source rows it needs through LDS,
+ * rows_per_chunk rows of row_stride bytes at a time (row_stride a multiple of 4 and at least the widest tile's source
+ * segment + 3; rows_per_chunk * row_stride <= 64 KiB); row_stride == 0 reads the source in place, for segments no LDS
+ * holds.  The tiling does not change a byte.  ELVIS_E_INVALID, before any launch: a null pointer, a non-positive
+ * size, another c, a destination larger than the source on either axis (cv2 switches to its area-mode bilinear
+ * there; not built), a table that leaves the source, steps back or, at whole ratios, is not the box, a tile or a chunk
+ * beyond the limits above. */
+int elvis_resize_area_u8(const uint8_t* src, uint8_t* dst, int n, int hs, int ws, int hd, int wd, int c,
+                         const int32_t* xstart_h, const int32_t* xfirst_h, const int32_t* ystart_h, const int32_t* yfirst_h,
+                         const int32_t* xstart, const int32_t* xfirst, const float* xw, const int32_t* ystart,
+                         const int32_t* yfirst, const float* yw, int th, int tw, int rows_per_chunk, int row_stride,
+                         elvis_stream_t stream);
+
+/* cv2.resize(mask, (wd, hd), interpolation=cv2.INTER_NEAREST) (presley.py:427, 846, 867, 884; elvis.py:206, 564, 4578):
+ * dst[f, dy, dx] = src[f, floor(dy * hs / hd), floor(dx * ws / wd)] in integers, up or down.  src u8 [n,hs,ws,c], dst u8
+ * [n,hd,wd,c], c in {1, 3, 4}. */
+int elvis_resize_nearest_u8(const uint8_t* src, uint8_t* dst, int n, int hs, int ws, int hd, int wd, int c,
+                            elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ DCT slot (LaplacianVCAR-style) */
 
 /* DCNv2 modulated deformable 3x3 convolution (stride 1, pad 1, dilation 1), NHWC.
