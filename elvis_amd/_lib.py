@@ -122,6 +122,8 @@ SIGNATURES = {
     "elvis_fvmd_finish_f64": [vp, vp, vp, i32, i32, i32, vp],
     "elvis_png_stats": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_png_pack": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_png_stats_rle": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_png_pack_rle": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp],
     "elvis_png_gather": [vp, i64, vp, i32, vp, i64, vp, vp],
     "elvis_png_inflate": [vp, i64, vp, vp, i64, vp, vp, i32, vp],
     "elvis_png_unfilter": [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],

@@ -28,10 +28,12 @@ from the directory, so results do not depend on the device count.
 
 Every driver that writes frames takes `png_writer="pil"` (the default: frameio.save_frame / save_mask, files as before)
 or `"device"`: the PNGs are then written by the GPU (png.py) - decodable by any PNG reader to the same pixels, bytes not
-PIL's or cv2's.  Every built-in shard function returns a resident clip, and the writer takes it as it is
+PIL's or cv2's.  `"device-rle"` is "device" with `deflate="rle"` on everything it writes - frames, stretched frames and
+full-resolution masks: a mask or a stretched frame, whose filtered bytes are nearly all 0, is then a match per 258 bytes
+instead of a bit per byte.  Every built-in shard function returns a resident clip, and the writer takes it as it is
 (`png.save_frames_device`: only finished files come down), as it takes a v1 shard's stretched frames and full-resolution
 masks; only the host frames of a replaced `_shard_fn` go up once more (`png.save_frames`).  Any other value is a
-ValueError; "device" without a GPU raises.
+ValueError; "device" or "device-rle" without a GPU raises.
 
 Every driver also takes `png_reader="pil"` (the default: frameio.load_frame per file) or `"device"`: a worker's frame
 range is then decoded by the GPU (jpeg.load_images_device: PNG and JPEG files, told apart by their first bytes; a
@@ -64,13 +66,15 @@ ShardFn = Callable[..., List[np.ndarray]]
 ClipShardFn = Callable[..., torch.Tensor]
 
 
-PNG_WRITERS = ("pil", "device")
+PNG_WRITERS = ("pil", "device", "device-rle")
+_DEVICE_DEFLATE = {"device": "literal", "device-rle": "rle"}   # the device writers and the deflate= they pass to png.py
 PNG_READERS = ("pil", "device")
 
 
 def _check_png_io(png_writer, png_reader) -> None:
     """`png_writer=` of the directory drivers: "pil" (frameio.save_frame / save_mask, the default) or "device" (png.py:
-    the files are written by the GPU - any PNG reader decodes them to the same pixels, the bytes are not PIL's).
+    the files are written by the GPU - any PNG reader decodes them to the same pixels, the bytes are not PIL's) or
+    "device-rle" (the same with `deflate="rle"`: runs of equal filtered bytes become matches, for masks and flat frames).
     `png_reader=`: "pil" (frameio.load_frame, the default) or "device" (png.py, jpeg.py: the PNG and JPEG files are
     decoded by the GPU into a resident clip - the same pixels)."""
     if png_writer not in PNG_WRITERS:
@@ -114,12 +118,12 @@ class PngDirSink:
 
     def save(self, frames, start: int, device) -> None:
         paths = [os.path.join(self.out_dir, n) for n in self.names[start:start + len(frames)]]
-        if self.writer == "device":
+        if self.writer in _DEVICE_DEFLATE:
             from .png import save_frames, save_frames_device
             if isinstance(frames, torch.Tensor):
-                save_frames_device(frames.contiguous(), paths)
+                save_frames_device(frames.contiguous(), paths, deflate=_DEVICE_DEFLATE[self.writer])
             else:
-                save_frames(frames, paths, device)
+                save_frames(frames, paths, device, deflate=_DEVICE_DEFLATE[self.writer])
             return
         for f, p in zip(recompose.frames_to_host(frames) if isinstance(frames, torch.Tensor) else frames, paths):
             save_frame(f, p)
@@ -267,10 +271,10 @@ def _png_jobs(builtin: Callable, _shard_fn: Optional[ShardFn], in_dir: str, out_
     """The jobs of a directory driver, one per chunk: the resident `builtin` shard function, or the caller's `_shard_fn`
     on host frames.  `png_writer` / `png_reader` "device" need a GPU on every chunk."""
     for what, value in (("png_writer", png_writer), ("png_reader", png_reader)):
-        if value == "device":
+        if value != "pil":
             for c in chunks:
                 if c.device.type != "cuda":
-                    raise RuntimeError(f"{what}='device' needs a GPU (got device '{c.device}'); there is no CPU path")
+                    raise RuntimeError(f"{what}='{value}' needs a GPU (got device '{c.device}'); there is no CPU path")
     source, sink = PngDirSource(in_dir, names, png_reader), PngDirSink(out_dir, names, png_writer)
     return [ShardJob(_shard_fn or builtin, source, sink, _shard_fn is None, c.start, c.end, halo, maps, block_size,
                      _device_str(c.device), kw) for c in chunks]
@@ -305,9 +309,9 @@ def _write_clip(clip: torch.Tensor, directory: str, names: Sequence[str], png_wr
     """A resident clip of frames [n,H,W,3] or of masks [n,H,W] as PNGs `names` of `directory`, with either writer: the
     device writer takes the clip as it is and only finished files come down."""
     paths = [os.path.join(directory, name) for name in names]
-    if png_writer == "device":
+    if png_writer in _DEVICE_DEFLATE:
         from .png import save_frames_device
-        save_frames_device(clip.contiguous(), paths)
+        save_frames_device(clip.contiguous(), paths, deflate=_DEVICE_DEFLATE[png_writer])
     elif clip.dim() == 4:
         for f, p in zip(recompose.frames_to_host(clip), paths):
             save_frame(f, p)

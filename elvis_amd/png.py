@@ -11,6 +11,13 @@ stream: literal-only dynamic-Huffman deflate, one block and one IDAT chunk per `
 literal code per frame).  Opt-in: `frameio.save_frame` / `save_mask` stay PIL and every directory driver writes through
 PIL unless it is called with `png_writer="device"`.
 
+`deflate="rle"` on the three functions (`png_writer="device-rle"` on the drivers) is the stream for masks and flat or
+stretched frames, whose filtered bytes are nearly all 0 and which literals cannot bring under a bit a byte: a run of equal
+bytes inside a 4096-byte span of a row becomes its first byte and distance-1 matches of up to 258 (csrc/png_rle.h has the
+rule, include/elvis_amd.h the contract, tests/_png_rle_ref.py states it).  286 symbols, a 1222-bit block header with one
+distance code of length 1, 1160 bytes of statistics a segment; everything else - filters, segments, chunks, checksums,
+the two phases - is the literal path's.  The default, "literal", and its bytes are unchanged.
+
 Synchronisation: one per clip, as for the inpainter.  Phase 1 (`elvis_png_stats`) leaves every segment's histogram and
 Adler partial on the device; they are downloaded with one blocking copy on the current stream (1040 bytes a segment),
 the codes, bit lengths, chunk offsets and Adler trailers are worked out here, and phase 2 (`elvis_png_pack`) writes the
@@ -60,18 +67,29 @@ FILE_HEAD, FILE_TAIL = 33, 12   # signature + IHDR chunk, IEND chunk
 UPLOAD_CHUNK_BYTES = 32 << 20
 _CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
 _IEND = struct.pack(">I", 0) + b"IEND" + struct.pack(">I", zlib.crc32(b"IEND"))
+DEFLATES = ("literal", "rle")
+# deflate="rle": literals and distance-1 matches (csrc/png_rle.h, include/elvis_amd.h "PNG writer")
+RLE_SPAN = 4096                 # filtered bytes of a row tokenised on their own: the pack kernel's staging tile
+RLE_SYMBOLS = 286               # literals, EOB, the length symbols 257..285
+RLE_HEADER_BITS = 1222          # 3 + 5 + 5 + 4 + 19 * 3 + 287 * 4
+RLE_HEADER_WORDS = 39
+RLE_STATS_STRIDE = 290          # 286 bins, Adler A, Adler B, length, 0
+RLE_FRAME_TAB = 328             # 286 code entries, the Adler trailer, 39 header words, padding
+RLE_TAB_ADLER, RLE_TAB_HEADER = 286, 287
+# RFC 1951 3.2.5: extra bits of the length symbols 257..285
+RLE_LENGTH_EXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
 
 
 # ----------------------------------------------------------------------------- the literal code (host)
-def limited_code_lengths(hist, max_len: int = MAX_CODE_LEN) -> np.ndarray:
-    """Code lengths (uint8 [257], 0 = unused) of a complete prefix code for the 257-bin histogram `hist` (256 literals
-    and EOB), none longer than `max_len`: package-merge, so the lengths are optimal under the limit and their Kraft sum
-    is exactly 1.  Deterministic: equal counts are ordered by symbol value, a leaf before a package of the same weight.
-    EOB is always coded; a histogram with a single used symbol gets a second one (EOB, or literal 0 when the one symbol
-    is EOB itself) so that the code stays complete."""
+def limited_code_lengths(hist, max_len: int = MAX_CODE_LEN, symbols: int = 257) -> np.ndarray:
+    """Code lengths (uint8 [symbols], 0 = unused) of a complete prefix code for the `symbols`-bin histogram `hist` (257:
+    256 literals and EOB; 286: the length symbols too), none longer than `max_len`: package-merge, so the lengths are
+    optimal under the limit and their Kraft sum is exactly 1.  Deterministic: equal counts are ordered by symbol value,
+    a leaf before a package of the same weight.  EOB is always coded; a histogram with a single used symbol gets a
+    second one (EOB, or literal 0 when the one symbol is EOB itself) so that the code stays complete."""
     h = np.array(hist, dtype=np.int64).reshape(-1)
-    if h.size != 257 or (h < 0).any():
-        raise ValueError("limited_code_lengths: the histogram has 257 non-negative bins")
+    if symbols <= EOB or h.size != symbols or (h < 0).any():
+        raise ValueError(f"limited_code_lengths: the histogram has {symbols} non-negative bins")
     if h[EOB] == 0:
         h[EOB] = 1
     if np.count_nonzero(h) == 1:
@@ -95,7 +113,7 @@ def limited_code_lengths(hist, max_len: int = MAX_CODE_LEN) -> np.ndarray:
         m = w.size // 2 * 2
         pack_w = w[0:m:2] + w[1:m:2]
         pack_v = v[0:m:2] + v[1:m:2]
-    lens = np.zeros(257, dtype=np.uint8)
+    lens = np.zeros(symbols, dtype=np.uint8)
     lens[order] = v[:2 * n - 2].sum(axis=0)
     if int(lens.max()) > max_len or sum(1 << (max_len - int(l)) for l in lens[lens > 0]) != 1 << max_len:
         raise RuntimeError("limited_code_lengths: the code is not complete")
@@ -159,6 +177,34 @@ def block_header_bits(lengths, final: bool = False) -> Tuple[int, int]:
     return acc, n
 
 
+def block_header_bits_rle(lengths, final: bool = False) -> Tuple[int, int]:
+    """The header of a dynamic-Huffman block of the run-length stream for the literal/length code `lengths` [286], as
+    (bits packed LSB first into a Python int, bit count = 1222): BFINAL, BTYPE 2, HLIT field 29 (286 codes), HDIST field
+    0 (one distance code), HCLEN field 15, the flat 4-bit code-length code of `block_header_bits`, then the 286 lengths
+    and the distance length 1 as 4-bit codes.  One distance code of length 1 is the one incomplete distance set that
+    deflate allows; every match's distance is that code's single bit, 0."""
+    if len(lengths) != RLE_SYMBOLS:
+        raise ValueError(f"block_header_bits_rle: {RLE_SYMBOLS} code lengths, got {len(lengths)}")
+    acc, n = 0, 0
+
+    def put(v, k):
+        nonlocal acc, n
+        acc |= v << n
+        n += k
+
+    put(1 if final else 0, 1)
+    put(2, 2)
+    put(RLE_SYMBOLS - 257, 5)
+    put(0, 5)
+    put(15, 4)
+    for s in _CL_ORDER:
+        put(0 if s >= 16 else 4, 3)
+    for l in list(lengths) + [1]:
+        put(reverse_bits(int(l), 4), 4)
+    assert n == RLE_HEADER_BITS
+    return acc, n
+
+
 def adler_combine(partials, start: Tuple[int, int] = (1, 0)) -> int:
     """Adler-32 of a stream from its pieces' partials (A = sum d_i, B = sum (len - i) d_i, len), in stream order."""
     a, b = start
@@ -176,8 +222,8 @@ def ihdr_chunk(width: int, height: int, channels: int) -> bytes:
 @dataclass
 class PngPlan:
     """Where everything goes, from the statistics of phase 1 alone."""
-    lengths: np.ndarray       # uint8 [n, 257]
-    frame_tab: np.ndarray     # uint32 [n, FRAME_TAB]
+    lengths: np.ndarray       # uint8 [n, 257]; [n, 286] for the run-length stream
+    frame_tab: np.ndarray     # uint32 [n, FRAME_TAB]; [n, RLE_FRAME_TAB]
     chunks: np.ndarray        # int64 [n * segments, 2]: byte offset of the chunk in the output buffer, length of its data
     file_offsets: np.ndarray  # int64 [n + 1]: file f is bytes file_offsets[f] .. file_offsets[f + 1]
     adler: np.ndarray         # uint32 [n]
@@ -200,6 +246,43 @@ def plan_layout(stats: np.ndarray) -> PngPlan:
         frame_tab[f, TAB_HEADER:TAB_HEADER + HEADER_WORDS] = [(acc >> (32 * k)) & 0xFFFFFFFF for k in range(HEADER_WORDS)]
     ll = lengths.astype(np.int64)
     bits = HEADER_BITS + np.einsum("fsk,fk->fs", hist, ll[:, :256]) + ll[:, 256:257]
+    chunks, file_offsets, adler = _lay_out(bits, st[:, :, 256:259])
+    frame_tab[:, TAB_ADLER] = adler
+    return PngPlan(lengths, frame_tab, chunks, file_offsets, adler)
+
+
+def plan_layout_rle(stats: np.ndarray) -> PngPlan:
+    """`plan_layout` for the run-length stream, from stats u32 [n, segments, 290]: one 286-symbol literal/length code per
+    frame from its token histogram (EOB count = segments), the 1222-bit header, and a segment's bits as header + sum
+    hist[s] * (len[s] + extra[s]) + one distance bit per match + EOB."""
+    st = np.asarray(stats, dtype=np.uint32)
+    if st.ndim != 3 or st.shape[2] != RLE_STATS_STRIDE or st.shape[1] < 1:
+        raise ValueError(f"plan_layout_rle: stats must be [n, segments, {RLE_STATS_STRIDE}], got {st.shape}")
+    n, nseg, _ = st.shape
+    hist = st[:, :, :RLE_SYMBOLS].astype(np.int64)
+    hist[:, :, EOB] = 0                                        # the device counts no EOB
+    lengths = np.zeros((n, RLE_SYMBOLS), dtype=np.uint8)
+    frame_tab = np.zeros((n, RLE_FRAME_TAB), dtype=np.uint32)
+    frame_hist = hist.sum(axis=1)
+    frame_hist[:, EOB] = nseg
+    for f in range(n):
+        lengths[f] = limited_code_lengths(frame_hist[f], symbols=RLE_SYMBOLS)
+        frame_tab[f, :RLE_SYMBOLS] = code_entries(lengths[f])
+        acc, _ = block_header_bits_rle(lengths[f])
+        frame_tab[f, RLE_TAB_HEADER:RLE_TAB_HEADER + RLE_HEADER_WORDS] = [(acc >> (32 * k)) & 0xFFFFFFFF for k in range(RLE_HEADER_WORDS)]
+    cost = lengths.astype(np.int64)
+    cost[:, 257:] += np.asarray(RLE_LENGTH_EXTRA, dtype=np.int64) + 1      # a match: its extra bits and the distance bit
+    bits = RLE_HEADER_BITS + np.einsum("fsk,fk->fs", hist, cost) + cost[:, EOB:EOB + 1]
+    chunks, file_offsets, adler = _lay_out(bits, st[:, :, RLE_SYMBOLS:RLE_SYMBOLS + 3])
+    frame_tab[:, RLE_TAB_ADLER] = adler
+    return PngPlan(lengths, frame_tab, chunks, file_offsets, adler)
+
+
+def _lay_out(bits: np.ndarray, partials: np.ndarray):
+    """Chunk table, file offsets and Adler trailers from every segment's block bits [n, segments] (header to EOB) and its
+    Adler partial (A, B, length) [n, segments, 3]."""
+    n, nseg = bits.shape
+    bits = bits.copy()
     bits[:, :-1] += 3                                          # the empty stored block's header
     data_len = (bits + 7) // 8 + 4                             # + 00 00 FF FF, or the Adler-32 on the last
     data_len[:, 0] += 2                                        # 78 01
@@ -211,13 +294,12 @@ def plan_layout(stats: np.ndarray) -> PngPlan:
     chunks = np.stack([chunk_off, data_len], axis=2).reshape(n * nseg, 2).astype(np.int64)
     a = np.ones(n, dtype=np.int64)
     b = np.zeros(n, dtype=np.int64)
-    sa, sb, sl = (st[:, :, 256 + k].astype(np.int64) for k in range(3))
+    sa, sb, sl = (partials[:, :, k].astype(np.int64) for k in range(3))
     for s in range(nseg):
         b = (b + sl[:, s] % ADLER_MOD * a + sb[:, s]) % ADLER_MOD
         a = (a + sa[:, s]) % ADLER_MOD
     adler = ((b << 16) | a).astype(np.uint32)
-    frame_tab[:, TAB_ADLER] = adler
-    return PngPlan(lengths, frame_tab, np.ascontiguousarray(chunks), file_offsets, adler)
+    return np.ascontiguousarray(chunks), file_offsets, adler
 
 
 # ----------------------------------------------------------------------------- the device forms
@@ -228,6 +310,14 @@ def _filter_code(filter) -> int:
     elif isinstance(filter, (int, np.integer)) and not isinstance(filter, bool) and 0 <= int(filter) <= 4:
         return int(filter)
     raise ValueError(f"png: filter must be 'adaptive' or 0..4, got {filter!r}")
+
+
+def _check_deflate(deflate, who: str) -> bool:
+    """deflate= of the writers: "literal" (the default: every byte its own Huffman code) or "rle" (literals and distance-1
+    matches, for masks and flat frames).  True for "rle"."""
+    if not isinstance(deflate, str) or deflate not in DEFLATES:
+        raise ValueError(f"{who}: deflate must be one of {DEFLATES}, got {deflate!r}")
+    return deflate == "rle"
 
 
 def _check_clip(frames_d, order, filter, segment_rows, who: str):
@@ -256,9 +346,10 @@ def _check_clip(frames_d, order, filter, segment_rows, who: str):
     return n, h, w, c, int(order == "bgr"), fcode, int(segment_rows)
 
 
-def _encode_clip(frames_d: torch.Tensor, order, filter, segment_rows, who: str, guard: int = 0):
+def _encode_clip(frames_d: torch.Tensor, order, filter, segment_rows, who: str, guard: int = 0, deflate: str = "literal"):
     """Both phases.  Returns (the output buffer on the device with `guard` bytes of 0xA5 on either side, the plan, the
     filter types u8 [n, H] on the device); (None, None, None) for an empty clip."""
+    rle = _check_deflate(deflate, who)
     n, h, w, c, ocode, fcode, rows = _check_clip(frames_d, order, filter, segment_rows, who)
     if n == 0:
         return None, None, None
@@ -267,12 +358,14 @@ def _encode_clip(frames_d: torch.Tensor, order, filter, segment_rows, who: str, 
     dev = frames_d.device
     nseg = (h + rows - 1) // rows
     with torch.cuda.device(dev):
+        stride = RLE_STATS_STRIDE if rle else STATS_STRIDE
+        stats_fn, pack_fn = (lib().elvis_png_stats_rle, lib().elvis_png_pack_rle) if rle else (lib().elvis_png_stats, lib().elvis_png_pack)
         types = torch.empty(n * h, dtype=torch.uint8, device=dev)
-        stats_d = torch.empty(n * nseg * STATS_STRIDE, dtype=torch.int32, device=dev)
-        check(lib().elvis_png_stats(ptr(frames_d), ptr(types), ptr(stats_d), n, h, w, c, ocode, fcode, rows, _s(frames_d)), dev)
+        stats_d = torch.empty(n * nseg * stride, dtype=torch.int32, device=dev)
+        check(stats_fn(ptr(frames_d), ptr(types), ptr(stats_d), n, h, w, c, ocode, fcode, rows, _s(frames_d)), dev)
         # the one synchronisation of a clip: every segment's histogram and Adler partial
-        stats = stats_d.cpu().numpy().view(np.uint32).reshape(n, nseg, STATS_STRIDE)
-        plan = plan_layout(stats)
+        stats = stats_d.cpu().numpy().view(np.uint32).reshape(n, nseg, stride)
+        plan = plan_layout_rle(stats) if rle else plan_layout(stats)
         total = int(plan.file_offsets[-1])
         chunks_d = torch.from_numpy(plan.chunks).to(dev)
         tab_d = torch.from_numpy(plan.frame_tab.view(np.int32)).to(dev)
@@ -280,8 +373,8 @@ def _encode_clip(frames_d: torch.Tensor, order, filter, segment_rows, who: str, 
         if guard:
             out[:guard] = 0xA5
             out[guard + total:] = 0xA5
-        check(lib().elvis_png_pack(ptr(frames_d), ptr(types), ptr(chunks_d), ptr(tab_d), ptr(out) + guard, total, n, h, w, c, ocode,
-                                   rows, _s(frames_d)), dev)
+        check(pack_fn(ptr(frames_d), ptr(types), ptr(chunks_d), ptr(tab_d), ptr(out) + guard, total, n, h, w, c, ocode, rows,
+                      _s(frames_d)), dev)
     return out, plan, types.view(n, h)
 
 
@@ -299,8 +392,8 @@ def _finish_files(host: np.ndarray, plan: PngPlan, h: int, w: int, c: int) -> Li
     return files
 
 
-def _encode_to_host(frames_d, order, filter, segment_rows, who: str) -> List[np.ndarray]:
-    out, plan, _ = _encode_clip(frames_d, order, filter, segment_rows, who)
+def _encode_to_host(frames_d, order, filter, segment_rows, who: str, deflate: str = "literal") -> List[np.ndarray]:
+    out, plan, _ = _encode_clip(frames_d, order, filter, segment_rows, who, deflate=deflate)
     if out is None:
         return []
     c = int(frames_d.shape[3]) if frames_d.dim() == 4 else 1
@@ -308,33 +401,38 @@ def _encode_to_host(frames_d, order, filter, segment_rows, who: str) -> List[np.
 
 
 def encode_png_device(frames_d: torch.Tensor, order: str = "bgr", filter: Union[str, int] = "adaptive",
-                      segment_rows: int = 16) -> List[bytes]:
+                      segment_rows: int = 16, deflate: str = "literal") -> List[bytes]:
     """One complete PNG file per frame of a resident contiguous uint8 clip [n,H,W,3], [n,H,W,1] or [n,H,W].  `order` is
     the channel order of a 3-channel clip ("bgr", what `save_frame` takes, or "rgb"); `filter` is "adaptive" (per row
     the type with the least sum of min(v, 256 - v), ties to the lower type) or one type 0..4 for every row; a frame is
-    cut into deflate blocks and IDAT chunks of `segment_rows` rows.  A frame's bytes do not depend on the frames it is
-    encoded with.  ValueError before any launch for a bad argument; an empty clip gives []."""
-    return [v.tobytes() for v in _encode_to_host(frames_d, order, filter, segment_rows, "encode_png_device")]
+    cut into deflate blocks and IDAT chunks of `segment_rows` rows.  `deflate` is "literal" (every filtered byte its own
+    Huffman code: at least a bit a byte) or "rle" (runs of equal bytes inside 4096-byte spans of a row become distance-1
+    matches: the stream for masks and flat or stretched frames, whose filtered bytes are nearly all 0).  A frame's bytes
+    do not depend on the frames it is encoded with.  ValueError before any launch for a bad argument; an empty clip
+    gives []."""
+    return [v.tobytes() for v in _encode_to_host(frames_d, order, filter, segment_rows, "encode_png_device", deflate)]
 
 
 def save_frames_device(frames_d: torch.Tensor, paths: Sequence, order: str = "bgr", filter: Union[str, int] = "adaptive",
-                       segment_rows: int = 16) -> None:
+                       segment_rows: int = 16, deflate: str = "literal") -> None:
     """`encode_png_device`, one download, and frame i written to paths[i]; directories are created as `save_frame`
     does."""
+    _check_deflate(deflate, "save_frames_device")
     paths = list(paths)
     if not isinstance(frames_d, torch.Tensor) or frames_d.dim() < 1 or len(paths) != frames_d.shape[0]:
         raise ValueError(f"save_frames_device: {len(paths)} path(s) for the clip {tuple(getattr(frames_d, 'shape', ()))}")
-    for path, view in zip(paths, _encode_to_host(frames_d, order, filter, segment_rows, "save_frames_device")):
+    for path, view in zip(paths, _encode_to_host(frames_d, order, filter, segment_rows, "save_frames_device", deflate)):
         os.makedirs(os.path.dirname(os.fspath(path)) or ".", exist_ok=True)
         with open(path, "wb") as f:
             f.write(memoryview(view))
 
 
 def save_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=None, order: str = "bgr",
-                filter: Union[str, int] = "adaptive", segment_rows: int = 16) -> None:
+                filter: Union[str, int] = "adaptive", segment_rows: int = 16, deflate: str = "literal") -> None:
     """Host frames - uint8 (H,W,3), (H,W,1) or (H,W) arrays, a list or one [n,...] array - written as PNGs to `paths`
     through the device.  Uploaded and encoded `chunk_frames` frames at a time, by default as many as make 32 MB (5 at
     1080p); a run of equal shapes is one clip.  The files do not depend on the chunk size."""
+    _check_deflate(deflate, "save_frames")
     paths = list(paths)
     if len(frames) != len(paths):
         raise ValueError(f"save_frames: {len(frames)} frame(s) for {len(paths)} path(s)")
@@ -355,7 +453,7 @@ def save_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=None, 
             while end < len(arrays) and end - at < step and arrays[end].shape == shape:
                 end += 1
             clip = torch.from_numpy(np.ascontiguousarray(np.stack(arrays[at:end], axis=0))).to(dev)
-            save_frames_device(clip, paths[at:end], order, filter, segment_rows)
+            save_frames_device(clip, paths[at:end], order, filter, segment_rows, deflate)
             at = end
 
 

@@ -826,6 +826,31 @@ int elvis_png_stats(const uint8_t* frames, uint8_t* types, uint32_t* stats, int 
                     int segment_rows, elvis_stream_t stream);
 int elvis_png_pack(const uint8_t* frames, const uint8_t* types, const int64_t* chunks, const uint32_t* frame_tab, uint8_t* out,
                    int64_t out_bytes, int n, int h, int w, int c, int order, int segment_rows, elvis_stream_t stream);
+/* The same two phases for the run-length stream (png_stats_rle_kernel, png_pack_rle_kernel; csrc/png_rle.h has the token
+ * rule, tests/_png_rle_ref.py states the stream): masks and flat frames, whose filtered bytes are nearly all 0, cost a
+ * match per 258 bytes instead of a bit per byte.  Frames, filters, filter choice, segments, IDAT chunking, the 78 01
+ * header, the empty stored block between segments, Adler-32 and CRC-32 are exactly as above; only the contents of a
+ * segment's dynamic-Huffman block differ:
+ *   tokens   a row's type byte is one literal.  The row's w * c filtered bytes are cut into spans of 4096 bytes, each
+ *            tokenised on its own.  A run is a maximal sequence of equal bytes inside a span; a run of length L and value
+ *            v is the literal v, then with R = L - 1: R / 258 matches of length 258 and, with r = R % 258, one match of
+ *            length r if r >= 3, else r literals v.  Every match has distance 1; none reaches across a span, a row, a
+ *            type byte or a segment.
+ *   symbols  286 literal/length symbols (0..255, EOB 256, 257..285 by RFC 1951's table; 258 is symbol 285 without extra
+ *            bits), extra bits behind the code LSB first; one distance symbol (code 0) of length 1, so every match ends
+ *            with one distance bit, 0.
+ *   header   HLIT field 29, HDIST field 0, HCLEN 15; the flat 4-bit code-length code carries the 286 lengths and the
+ *            distance length 1: 3 + 5 + 5 + 4 + 57 + 287 * 4 = 1222 bits, 39 dwords.
+ *   1. elvis_png_stats_rle writes types u8 [n, h] and stats u32 [n, segments, 290]: the 286-bin histogram of the
+ *      segment's tokens (type bytes included, EOB not), then the Adler partial, the length and a 0 as above.
+ *   2. the host builds one literal/length code per frame (EOB count = segments); a segment is 1222 + sum hist[s] *
+ *      (len[s] + extra[s]) + sum hist[257..285] bits plus EOB.  elvis_png_pack_rle takes chunks as above and frame_tab u32
+ *      [n, 328] = 286 entries (bit-reversed code << 4 | length), the Adler-32 trailer, the 39 header dwords with BFINAL
+ *      0, padding.  Same clipping, same masks, no global atomics, the same errors before any launch. */
+int elvis_png_stats_rle(const uint8_t* frames, uint8_t* types, uint32_t* stats, int n, int h, int w, int c, int order, int filter,
+                        int segment_rows, elvis_stream_t stream);
+int elvis_png_pack_rle(const uint8_t* frames, const uint8_t* types, const int64_t* chunks, const uint32_t* frame_tab, uint8_t* out,
+                       int64_t out_bytes, int n, int h, int w, int c, int order, int segment_rows, elvis_stream_t stream);
 
 /* ------------------------------------------------------------------ PNG reader (png_read.hip, inflate.h)
  * PNG files decoded by the device in place of the cv2.imread that starts every client-side entry point of the reference
