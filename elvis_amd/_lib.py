@@ -65,6 +65,8 @@ SIGNATURES = {
     "elvis_groupnorm_workspace_floats": [i32, i32, i32, i32],
     "elvis_groupnorm_sums": [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp],
     "elvis_groupnorm_affine": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "elvis_gn_partials_affine_span": [i32, i32],
+    "elvis_gn_partials_affine": [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "elvis_affine_act": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp],
     "elvis_layernorm": [vp, vp, i32, i64, i32, i32, i32, vp, vp, f32, vp],
     "elvis_swin_packed_bytes": [i32, i32, i32],
@@ -76,6 +78,9 @@ SIGNATURES = {
     "elvis_window_attention": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, f32, vp],
     "elvis_bicubic_upsample": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_vq_nearest": [vp, vp, vp, i32, i64, i32, i32, i32, vp, i32, vp],
+    "elvis_vq_index_bytes": [i32, i32],
+    "elvis_vq_index_build": [vp, i32, i32, vp, vp],
+    "elvis_vq_nearest_indexed": [vp, vp, vp, i32, i64, i32, i32, i32, vp, i32, vp, vp],
     "elvis_pad_reflect_axpy": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, f32, vp],
     "elvis_crop_copy": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "elvis_convert_act": [vp, i32, vp, i32, i64, i32, vp],
@@ -178,6 +183,7 @@ def lib() -> C.CDLL:
         handle.elvis_conv_packed_weight_bytes.restype = C.c_size_t
         handle.elvis_groupnorm_workspace_floats.restype = C.c_size_t
         handle.elvis_swin_packed_bytes.restype = C.c_size_t
+        handle.elvis_vq_index_bytes.restype = C.c_size_t
         handle.elvis_ssim_workspace_bytes.restype = C.c_size_t
         handle.elvis_inpaint_workspace_bytes.restype = C.c_size_t
         handle.elvis_lpips_distance_workspace_bytes.restype = C.c_size_t

@@ -522,6 +522,13 @@ def groupnorm_affine(xs, gamma, beta, groups, eps, scale=None, shift=None):
     n, hw = x0.n, x0.h * x0.w
     ctot = sum(x.c for x in xs)
     dev = x0.t.device
+    pa = torch.empty((n, ctot), dtype=torch.float32, device=dev)
+    pb = torch.empty((n, ctot), dtype=torch.float32, device=dev)
+    if len(xs) == 1 and x0.stats is not None and lib().elvis_gn_partials_affine_span(ctot, groups) > 0:
+        # one buffer of fused partials: reduction and affine in one launch, the same fp64 operations in the same order
+        check(lib().elvis_gn_partials_affine(ptr(x0.stats), x0.stats.shape[0] // n, ptr(gamma), ptr(beta), ptr(scale),
+                                             ptr(shift), ptr(pa), ptr(pb), n, hw, ctot, groups, float(eps), _s(x0.t)), dev)
+        return pa, pb
     sums = torch.empty((n, ctot, 2), dtype=torch.float64, device=dev)   # every entry is written below
     off = 0
     for x in xs:
@@ -534,8 +541,6 @@ def groupnorm_affine(xs, gamma, beta, groups, eps, scale=None, shift=None):
             check(lib().elvis_groupnorm_sums(ptr(x.t), x.dtype_code, n, hw, x.c, x.pitch, ptr(sums), ctot, off,
                                              ptr(ws), _s(x.t)), dev)
         off += x.c
-    pa = torch.empty((n, ctot), dtype=torch.float32, device=dev)
-    pb = torch.empty((n, ctot), dtype=torch.float32, device=dev)
     check(lib().elvis_groupnorm_affine(ptr(sums), ptr(gamma), ptr(beta), ptr(scale), ptr(shift), ptr(pa), ptr(pb), n,
                                        hw, ctot, groups, float(eps), _s(x0.t)), dev)
     return pa, pb
@@ -649,11 +654,28 @@ def bicubic_upsample(x: Act, sf: int) -> Act:
     return out
 
 
-def vq_nearest(z: Act, codebook: torch.Tensor, want_idx=False):
+def vq_index(codebook: torch.Tensor) -> Optional[torch.Tensor]:
+    """The grid index of a device codebook f32[n_embed, c] for `vq_nearest` (csrc/vq_index.hip), built once per loaded
+    model; None where the indexed search does not apply (c != 3, or a codebook with a non-finite entry): the scan serves."""
+    n_embed, c = codebook.shape
+    nbytes = lib().elvis_vq_index_bytes(n_embed, c)
+    if nbytes == 0 or not bool(torch.isfinite(codebook).all()):
+        return None
+    index = torch.zeros(nbytes, dtype=torch.uint8, device=codebook.device)
+    check(lib().elvis_vq_index_build(ptr(codebook), n_embed, c, ptr(index), _s(codebook)), codebook.device)
+    return index
+
+
+def vq_nearest(z: Act, codebook: torch.Tensor, want_idx=False, index: Optional[torch.Tensor] = None):
+    """`index` (from `vq_index(codebook)`): search the codebook's grid instead of scanning it; the same result."""
     out = new_act(z.n, z.h, z.w, z.c, z.t.dtype, z.t.device, zero=False)
     idx = torch.empty((z.n, z.h, z.w), dtype=torch.int32, device=z.t.device) if want_idx else None
-    check(lib().elvis_vq_nearest(ptr(z.t), ptr(out.t), ptr(idx), z.dtype_code, z.n * z.h * z.w, z.c, z.pitch,
-                                 out.pitch, ptr(codebook), codebook.shape[0], _s(z.t)), z.t.device)
+    if index is not None:
+        check(lib().elvis_vq_nearest_indexed(ptr(z.t), ptr(out.t), ptr(idx), z.dtype_code, z.n * z.h * z.w, z.c, z.pitch,
+                                             out.pitch, ptr(codebook), codebook.shape[0], ptr(index), _s(z.t)), z.t.device)
+    else:
+        check(lib().elvis_vq_nearest(ptr(z.t), ptr(out.t), ptr(idx), z.dtype_code, z.n * z.h * z.w, z.c, z.pitch,
+                                     out.pitch, ptr(codebook), codebook.shape[0], _s(z.t)), z.t.device)
     return (out, idx) if want_idx else out
 
 

@@ -185,6 +185,8 @@ class SinSRModel:
             self._build_unet(sd)
             self._build_ae(sd)
         self.codebook = sd["ae.quantize.embedding.weight"].to(device=dev, dtype=torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            self.vq_index = ops.vq_index(self.codebook)   # the codebook is a weight: its search grid is built once
 
     # ------------------------------------------------------------------ construction
     def _build_unet(self, sd):
@@ -334,7 +336,7 @@ class SinSRModel:
     def decode(self, z: Act, quantize: Optional[bool] = None, want_idx=False):
         idx = None
         if self.cfg.quantize if quantize is None else quantize:
-            z, idx = ops.vq_nearest(z, self.codebook, want_idx=True)
+            z, idx = ops.vq_nearest(z, self.codebook, want_idx=True, index=self.vq_index)
         z = ops.convert_act(z, self.sec_dtype[self._ae_section("dec", len(self.cfg.ae_ch_mult) - 1)])
         h = self.d_conv_in(self.post_quant_conv(z), want_stats=self.fuse_gn)
         for b in self.d_mid:

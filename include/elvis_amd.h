@@ -260,6 +260,15 @@ int elvis_groupnorm_affine(const double* sums, const float* gamma, const float* 
                            const float* shift, float* pa, float* pb, int n, int hw, int c, int groups,
                            float eps, elvis_stream_t stream);
 
+/* elvis_gn_partials_to_sums followed by elvis_groupnorm_affine in one launch, for the case where all c channels come from
+ * one partials buffer [n * tiles_per_image, c, 2]: same fp64 operations in the same order, bit-identical pa / pb
+ * (csrc/gn_fused.hip).  elvis_gn_partials_affine_span(c, groups) is the number of channels one workgroup covers, 0 when
+ * the shape is not served (more than 32 channels per group): callers then keep the two entries above. */
+int elvis_gn_partials_affine_span(int c, int groups);
+int elvis_gn_partials_affine(const float* partials, int tiles_per_image, const float* gamma, const float* beta,
+                             const float* scale, const float* shift, float* pa, float* pb, int n, int hw, int c,
+                             int groups, float eps, elvis_stream_t stream);
+
 /* Pad channels.  pitch_for(c) = c rounded up to a multiple of 8 is the pitch a tensor of c channels needs; the convs
  * read whole 8-channel groups, so what an op leaves in [c, pitch_out) is part of its contract:
  *   elvis_affine_act, elvis_layernorm        zero [c, pitch_for(c)) (f16 and f32), leave [pitch_for(c), pitch_out) alone
@@ -303,7 +312,9 @@ int elvis_swin_proj_mlp(const void* attn, const void* y, void* out, const void* 
 
 /* Normalised instantiation name (e.g. "swin_fused_kernel<192,2,1,true>", "dcnv2_tile_kernel<7>") of the last kernel that
  * elvis_window_attention, elvis_swin_*, elvis_dcnv2, elvis_block_gather_u8, elvis_inpaint_prepare ("inpaint_scatter_kernel", its
- * last), elvis_inpaint_fill ("inpaint_fill_kernel<3>"; unchanged when it launches nothing), elvis_tfill ("tfill_kernel<3>"), or an entry point of csrc/norm.hip / csrc/misc.hip
+ * last), elvis_inpaint_fill ("inpaint_fill_kernel<3>"; unchanged when it launches nothing), elvis_tfill ("tfill_kernel<3>"),
+ * elvis_gn_partials_affine ("gn_partials_affine_kernel<8>" / "<4>"), elvis_vq_nearest_indexed ("vq_grid_nearest_kernel<half>" / "<float>"),
+ * or an entry point of csrc/norm.hip / csrc/misc.hip
  * (elvis_groupnorm_sums reports its gn_channel_sums_kernel, elvis_gn_partials_to_sums which of its two reductions it chose)
  * launched on the calling thread; "" before the first.  Static storage:
  * no allocation, no device synchronisation. */
@@ -324,6 +335,17 @@ int elvis_bicubic_upsample(const void* x, void* y, int dtype, int n, int h, int 
 /* Nearest-codebook lookup: zq = codebook[argmin_k sum_c (z_c - e_kc)^2] (first index wins). */
 int elvis_vq_nearest(const void* z, void* zq, int32_t* idx_out, int dtype, long long pixels, int c,
                      int pitch_in, int pitch_out, const float* codebook, int n_embed, elvis_stream_t stream);
+
+/* The same lookup through a uniform grid over the codebook, c == 3 only (csrc/vq_index.hip): value for value the result of
+ * elvis_vq_nearest - indices, zq and pad channels - for finite inputs, visiting only the cells that can hold the minimum.
+ * elvis_vq_index_build lays a finite device codebook out into `workspace` (elvis_vq_index_bytes(n_embed, c) bytes of device
+ * memory, 16-byte aligned; 0 bytes: no index for this shape); it synchronises the stream and is meant to run once per
+ * loaded codebook.  elvis_vq_nearest_indexed takes elvis_vq_nearest's arguments and that index. */
+size_t elvis_vq_index_bytes(int n_embed, int c);
+int elvis_vq_index_build(const float* codebook, int n_embed, int c, void* workspace, elvis_stream_t stream);
+int elvis_vq_nearest_indexed(const void* z, void* zq, int32_t* idx_out, int dtype, long long pixels, int c,
+                             int pitch_in, int pitch_out, const float* codebook, int n_embed, const void* index,
+                             elvis_stream_t stream);
 
 /* Reflect-pad (right/bottom) copy of a float NHWC image into a larger one, optionally into a
  * channel slice, with y = x*mul + add_mul*add[...] (used for x_T = z_y + kappa*sqrt(eta)*eps
