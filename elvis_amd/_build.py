@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIBPATH = os.path.join(LIBDIR, "libelvis_amd.so")
-SOURCES = ["conv.hip", "conv_f32.hip", "dcn.hip", "swin.hip", "api.hip", "glue.hip", "misc.hip", "norm.hip", "attn.hip", "degrade.hip", "presley_degrade.hip", "classical.hip", "shrink.hip", "quality.hip", "handoff.hip", "inpaint.hip", "complexity.hip", "lpips.hip", "png.hip", "png_read.hip", "jpeg_read.hip", "i420_in.hip", "rrdb.hip", "srvgg.hip", "vmaf.hip", "fvmd.hip", "tfill.hip", "sr_enhance.hip", "segment.hip", "resize.hip", "gn_fused.hip", "vq_index.hip"]   # slowest first
+SOURCES = ["conv.hip", "conv_f32.hip", "dcn.hip", "swin.hip", "api.hip", "glue.hip", "misc.hip", "norm.hip", "attn.hip", "degrade.hip", "presley_degrade.hip", "classical.hip", "shrink.hip", "quality.hip", "handoff.hip", "inpaint.hip", "complexity.hip", "lpips.hip", "png.hip", "png_read.hip", "jpeg_read.hip", "jpeg_write.hip", "i420_in.hip", "rrdb.hip", "srvgg.hip", "vmaf.hip", "fvmd.hip", "tfill.hip", "sr_enhance.hip", "segment.hip", "resize.hip", "gn_fused.hip", "vq_index.hip"]   # slowest first
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result",
          "-ffp-contract=off"]  # bit-exact glue: no implicit FMA contraction (explicit fmaf where wanted)

@@ -1,0 +1,279 @@
+// The baseline JPEG encoder of csrc/jpeg_write.hip, host and device: the geometry of a frame's blocks in MCU scan order,
+// the sample a component has at a plane position (colour conversion, edge replication and downsampling in libjpeg's
+// order), the two passes of jfdctint.c, the quantiser, the quantisation tables of jpeg_set_quality, and the symbol rule
+// of one block (ITU-T T.81 F.1.2) over a sink that either counts bits or writes them at a bit offset - written once.  On
+// the device a lane takes a row, a column or a block; on the host the same text is plain C++, so that
+// tools/jpeg_encode_check.cpp walks the very code of the kernels over exact-size buffers under the address and
+// undefined-behaviour sanitizers.  tests/_jpeg_write_ref.py states what it computes.
+//
+// Rules kept here: every pixel read goes through a clamp to the frame; every table index goes through a mask; every
+// stream word written is checked against the frame's own word count; a block's code is at most 1658 bits.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define JPGE_HD __host__ __device__ __forceinline__
+#define JPGE_HDM __host__ __device__ __forceinline__   // on a member function
+#else
+#define JPGE_HD static inline
+#define JPGE_HDM inline
+#endif
+
+// Words of the stream that two blocks share are ORed into (they were cleared by an earlier launch); a vector atomic on
+// the device, where neighbouring blocks are other lanes, a plain OR on the host, where they are earlier iterations.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define JPGE_OR(p, v) atomicOr((p), (v))
+#else
+#define JPGE_OR(p, v) (*(p) |= (v))
+#endif
+
+#define JPGE_SAMPLING_444 0
+#define JPGE_SAMPLING_422 1
+#define JPGE_SAMPLING_420 2
+#define JPGE_HUFF_WORDS 272            // per table class (0 luma, 1 chroma): 16 DC entries by category, 256 AC entries by symbol
+#define JPGE_MAX_BLOCK_BITS 2048       // bound used for the size checks: DC 9 + 11, 63 AC symbols of at most 16 + 10
+#define JPGE_MAX_BLOCKS (1 << 20)      // blocks of a frame: its bit offsets stay below 2^31
+
+// A clip's geometry: every frame has it.  A gray frame is one component whose MCU is one block (wib x hib of them, no
+// dummy blocks); a colour frame's MCU is hmax * vmax luma blocks, then Cb, then Cr.
+struct JpegEncGeom {
+    int h, w, channels, bgr;
+    int hmax, vmax;        // luma sampling factors (1, 1 for gray)
+    int mcux, mcuy;        // MCUs per row, MCU rows
+    int wib, hib;          // luma blocks that count: ceil(w / 8), ceil(h / 8)
+    int bpm;               // blocks per MCU
+    int blocks;            // blocks of a frame: mcux * mcuy * bpm
+};
+
+JPGE_HD JpegEncGeom jpeg_enc_geometry(int h, int w, int channels, int bgr, int sampling) {
+    JpegEncGeom g;
+    g.h = h;
+    g.w = w;
+    g.channels = channels;
+    g.bgr = bgr;
+    g.hmax = channels == 3 && sampling != JPGE_SAMPLING_444 ? 2 : 1;
+    g.vmax = channels == 3 && sampling == JPGE_SAMPLING_420 ? 2 : 1;
+    g.mcux = (w + 8 * g.hmax - 1) / (8 * g.hmax);
+    g.mcuy = (h + 8 * g.vmax - 1) / (8 * g.vmax);
+    g.wib = (w + 7) / 8;
+    g.hib = (h + 7) / 8;
+    g.bpm = channels == 3 ? g.hmax * g.vmax + 2 : 1;
+    g.blocks = g.mcux * g.mcuy * g.bpm;
+    return g;
+}
+
+// Where block b of a frame lies: component, block row and column in the component's grid.  A dummy block - one that only
+// completes an MCU, past the luma blocks that count - is placed at the block whose DC it repeats: the one before it in
+// the MCU's own order, followed back until a real one (block 0 of an MCU is always real).
+struct JpegEncPlace {
+    int c, by, bx, dummy;
+};
+
+JPGE_HD JpegEncPlace jpeg_enc_place(const JpegEncGeom& g, int b) {
+    JpegEncPlace p;
+    p.dummy = 0;
+    if (g.channels == 1) {
+        p.c = 0;
+        p.by = b / g.mcux;
+        p.bx = b - p.by * g.mcux;
+        return p;
+    }
+    const int m = b / g.bpm, my = m / g.mcux, mx = m - my * g.mcux, ny = g.hmax * g.vmax;
+    int k = b - m * g.bpm;
+    if (k >= ny) {
+        p.c = 1 + (k - ny);
+        p.by = my;
+        p.bx = mx;
+        return p;
+    }
+    p.c = 0;
+    for (;;) {
+        const int vy = k / g.hmax, hx = k - vy * g.hmax;
+        p.by = my * g.vmax + vy;
+        p.bx = mx * g.hmax + hx;
+        if (k == 0 || (p.by < g.hib && p.bx < g.wib)) return p;
+        p.dummy = 1;
+        --k;
+    }
+}
+
+// The block before b among its component's blocks in scan order, whose DC is b's prediction; -1 for a component's first.
+JPGE_HD int jpeg_enc_pred_block(const JpegEncGeom& g, int b) {
+    if (g.channels == 1) return b - 1;
+    const int m = b / g.bpm, k = b - m * g.bpm, ny = g.hmax * g.vmax;
+    if (k < ny) {
+        if (k > 0) return b - 1;
+        return m > 0 ? (m - 1) * g.bpm + ny - 1 : -1;
+    }
+    return m > 0 ? b - g.bpm : -1;
+}
+
+JPGE_HD int jpeg_enc_table_class(const JpegEncGeom& g, int b) { return g.channels == 3 && b % g.bpm >= g.hmax * g.vmax ? 1 : 0; }
+
+// jccolor.c: 16-bit fixed point, F(x) = int(x * 65536 + 0.5).
+JPGE_HD int jpeg_enc_ycc(int r, int gr, int bl, int c) {
+    if (c == 0) return (19595 * r + 38470 * gr + 7471 * bl + 32768) >> 16;
+    if (c == 1) return (-11058 * r - 21710 * gr + 32768 * bl + (128 << 16) + 32767) >> 16;
+    return (32768 * r - 27439 * gr - 5329 * bl + (128 << 16) + 32767) >> 16;
+}
+
+// Component c of the pixel (y, x), both clamped to the frame: the replication of the last column and the last row.
+JPGE_HD int jpeg_enc_full(const uint8_t* frame, const JpegEncGeom& g, int c, int y, int x) {
+    y = y < 0 ? 0 : (y > g.h - 1 ? g.h - 1 : y);
+    x = x < 0 ? 0 : (x > g.w - 1 ? g.w - 1 : x);
+    const uint8_t* p = frame + ((size_t)y * g.w + x) * g.channels;
+    if (g.channels == 1) return p[0];
+    return jpeg_enc_ycc(p[g.bgr ? 2 : 0], p[1], p[g.bgr ? 0 : 2], c);
+}
+
+// The sample of component c at (py, px) of its own plane of whole blocks.  jcprepct.c / jcsample.c: the columns are
+// widened first, 4:2:0 repeats an odd frame's last row once, then the downsample (h2v1: bias 0, 1, 0, 1 ...; h2v2: 1, 2,
+// 1, 2 ... along the output row), then the plane is lengthened by its last row - so a chroma row past ceil(h / 2) is the
+// last downsampled row, not the downsample of repeated rows.
+JPGE_HD int jpeg_enc_sample(const uint8_t* frame, const JpegEncGeom& g, int c, int py, int px) {
+    if (c == 0 || (g.hmax == 1 && g.vmax == 1)) return jpeg_enc_full(frame, g, c, py, px);
+    if (g.vmax == 1) return (jpeg_enc_full(frame, g, c, py, 2 * px) + jpeg_enc_full(frame, g, c, py, 2 * px + 1) + (px & 1)) >> 1;
+    const int ch = (g.h + 1) >> 1;
+    py = py > ch - 1 ? ch - 1 : py;
+    return (jpeg_enc_full(frame, g, c, 2 * py, 2 * px) + jpeg_enc_full(frame, g, c, 2 * py, 2 * px + 1) +
+            jpeg_enc_full(frame, g, c, 2 * py + 1, 2 * px) + jpeg_enc_full(frame, g, c, 2 * py + 1, 2 * px + 1) + 1 + (px & 1)) >> 2;
+}
+
+// One 8-point pass of jfdctint.c (CONST_BITS 13, PASS1_BITS 2) in int32; the constants are those of the IDCT in
+// csrc/jpeg_read.hip.  FIRST: the row pass, outputs scaled up by 4; else the column pass, which takes that scale out
+// again.  Descales round half up.  |d| <= 128 in the first pass and <= 2^13 in the second keep every product in int32.
+template <bool FIRST>
+JPGE_HD void jpeg_fdct_pass(const int (&d)[8], int (&o)[8]) {
+    const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
+    const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    constexpr int s = FIRST ? 11 : 15, half = 1 << (s - 1);
+    if (FIRST) {
+        o[0] = (t10 + t11) * 4;
+        o[4] = (t10 - t11) * 4;
+    } else {
+        o[0] = (t10 + t11 + 2) >> 2;
+        o[4] = (t10 - t11 + 2) >> 2;
+    }
+    int z1 = (t12 + t13) * 4433;
+    o[2] = (z1 + t13 * 6270 + half) >> s;
+    o[6] = (z1 - t12 * 15137 + half) >> s;
+    z1 = t4 + t7;
+    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const int z5 = (z3 + z4) * 9633;
+    const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+    z1 *= -7373;
+    z2 *= -20995;
+    z3 = z3 * -16069 + z5;
+    z4 = z4 * -3196 + z5;
+    o[7] = (a4 + z1 + z3 + half) >> s;
+    o[5] = (a5 + z2 + z4 + half) >> s;
+    o[3] = (a6 + z2 + z3 + half) >> s;
+    o[1] = (a7 + z1 + z4 + half) >> s;
+}
+
+// The quantiser: the coefficient carries the FDCT's factor 8, so the divisor is table << 3; round half away from zero.
+JPGE_HD int jpeg_quantise(int coef, int table) {
+    const int q8 = table << 3, a = coef < 0 ? -coef : coef, q = (a + (q8 >> 1)) / q8;
+    return coef < 0 ? -q : q;
+}
+
+// natural index -> zig-zag position
+JPGE_HD int jpeg_zigzag_of(int natural) {
+    const uint8_t pos[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
+                             10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+    return pos[natural & 63];
+}
+
+// Entry i (natural order) of the quantisation table `which` (0 luma, 1 chroma): jpeg_set_quality(quality, force_baseline =
+// TRUE) of the Annex K tables, (base * scale + 50) / 100 clamped to 1..255, scale = 5000 / quality below 50 and 200 - 2 *
+// quality from there.
+JPGE_HD int jpeg_quant_value(int quality, int which, int i) {
+    const uint8_t base[2][64] = {
+        {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+         18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+        {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+         99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+    quality = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    const int v = (base[which & 1][i & 63] * scale + 50) / 100;
+    return v < 1 ? 1 : (v > 255 ? 255 : v);
+}
+
+// ----------------------------------------------------------------------------- the symbol rule of a block
+// A sink that counts.
+struct JpegBitCounter {
+    uint32_t bits = 0;
+    JPGE_HDM void put(uint32_t, int len) { bits += (uint32_t)len; }
+};
+
+// A sink that writes at a bit offset into a frame's stream of 32-bit words, the first bit of the stream in bit 31 of
+// word 0.  A word the block covers whole is stored; the word it shares with the block before it and the one it shares
+// with the block after it are ORed into.  Nothing is written at or past `nwords`.
+struct JpegBitWriter {
+    uint32_t* words;
+    uint32_t nwords, at;       // the word the accumulator goes to next
+    uint64_t acc = 0;
+    int n;                     // bits in the accumulator, the leading `lead` of them not this block's
+    bool shared;               // the next word to go out is shared with the block before
+    JPGE_HDM JpegBitWriter(uint32_t* w, uint32_t count, uint32_t bit_offset)
+        : words(w), nwords(count), at(bit_offset >> 5), n((int)(bit_offset & 31)), shared((bit_offset & 31) != 0) {}
+    JPGE_HDM void put(uint32_t code, int len) {
+        acc = (acc << len) | (code & ((1u << len) - 1u));   // len <= 16
+        n += len;
+        if (n >= 32) {
+            const uint32_t word = (uint32_t)(acc >> (n - 32));
+            if (at < nwords) {
+                if (shared) JPGE_OR(words + at, word);
+                else words[at] = word;
+            }
+            shared = false;
+            ++at;
+            n -= 32;
+            acc &= (1ull << n) - 1ull;
+        }
+    }
+    JPGE_HDM void flush() {
+        if (n > 0 && at < nwords) JPGE_OR(words + at, (uint32_t)(acc << (32 - n)));
+    }
+};
+
+JPGE_HD int jpeg_category(int v) {
+    const uint32_t a = (uint32_t)(v < 0 ? -v : v);
+    return a ? 32 - __builtin_clz(a) : 0;
+}
+
+// One block's symbols (T.81 F.1.2): the DC difference's category and bits, then per non-zero AC coefficient ZRLs for
+// runs above 15, the (run, category) symbol and the bits; EOB unless coefficient 63 is not zero.  zz: the block in zig-zag
+// order; tab: JPGE_HUFF_WORDS entries of the block's table class, (code << 5) | length, length 0 for a symbol the table
+// does not have (nothing goes out for it).
+template <class Sink>
+JPGE_HD void jpeg_encode_block(const int16_t* zz, int pred, const uint32_t* tab, Sink& sink) {
+    int v = (int)zz[0] - pred, cat = jpeg_category(v);
+    uint32_t e = tab[cat & 15];
+    sink.put(e >> 5, (int)(e & 31));
+    if (cat) sink.put((uint32_t)(v < 0 ? v + (1 << cat) - 1 : v), cat);
+    int run = 0;
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        v = zz[k];
+        if (v == 0) {
+            ++run;
+            continue;
+        }
+        while (run > 15) {
+            e = tab[16 + 0xF0];
+            sink.put(e >> 5, (int)(e & 31));
+            run -= 16;
+        }
+        cat = jpeg_category(v);
+        e = tab[16 + (((run << 4) | cat) & 255)];
+        sink.put(e >> 5, (int)(e & 31));
+        sink.put((uint32_t)(v < 0 ? v + (1 << cat) - 1 : v), cat & 15);
+        run = 0;
+    }
+    if (run) {
+        e = tab[16];
+        sink.put(e >> 5, (int)(e & 31));
+    }
+}

@@ -1,0 +1,362 @@
+// Baseline JPEG encoding on the device (include/elvis_amd.h "JPEG writer"): a resident clip goes in, the
+// finished entropy-coded scans come out; pixels and coefficients never visit the host, which writes the headers only
+// (elvis_amd/jpeg_write.py).  csrc/jpeg_encode.h holds the rule per sample and per block, tests/_jpeg_write_ref.py states
+// it in numpy, and a libjpeg-turbo PIL with optimize=False is the second oracle: same tables, same scan bytes.
+//
+//   jpeg_fdct_kernel     32 blocks a workgroup, 8 lanes a block.  A lane fetches one row of its block - colour
+//                        conversion, edge replication and downsampling in the fetch, every pixel read clamped to the
+//                        frame - and runs the row pass; the block is transposed through LDS (row pitch 9 dwords: the
+//                        32 lanes of a half wave hit 32 banks in both directions); the lane runs the column pass of
+//                        its column, quantises, and the zig-zag order is made by a second trip through LDS, so that a
+//                        lane stores 16 contiguous bytes.  Blocks are in MCU scan order; a dummy block is transformed as
+//                        the block whose DC it repeats and keeps the DC only.  int32 throughout.
+//   jpeg_bits_kernel     a lane per block: the bit length of its code from the DC difference and the AC symbols.
+//   jpeg_scan_kernel     a workgroup per frame: exclusive prefix sum in place, kScanChunk values a step with a carry;
+//                        the total goes behind the last value.  Used for the block bit offsets and the FF counts.
+//   jpeg_clear_kernel    zeroes the stream words the pack kernel ORs into: no result depends on what the buffer held.
+//   jpeg_pack_kernel     a lane per block: the same symbol walk, writing at the block's bit offset.  Words a block covers
+//                        whole are stored, the two it may share with its neighbours are ORed (vector atomics).  The
+//                        frame's last block adds the 1-fill to the byte boundary.
+//   jpeg_ff_kernel       FF bytes per chunk of kStuffChunk stream bytes.
+//   jpeg_sizes_kernel    per frame: stream bytes + FF bytes + 2 (EOI).
+//   jpeg_stuff_kernel    every stream byte to its place in the output, a 00 behind every FF, EOI at the end.
+//
+// No kernel waits on another wave's progress.  Every global write is checked against its frame's own span.
+#include <algorithm>
+#include "common.h"
+#include "jpeg_encode.h"
+
+namespace {
+
+constexpr int kFdctBlocks = 32, kFdctThreads = kFdctBlocks * 8;
+constexpr int kBlockThreads = 256;     // bits and pack: a lane per block
+constexpr int kScanChunk = 256;        // values of one step of the prefix sum
+constexpr int kStuffChunk = 1024;      // stream bytes of one workgroup of the stuffing pass: a dword a lane
+static_assert(kScanChunk == ELVIS_JPEG_SCAN_CHUNK && kStuffChunk == ELVIS_JPEG_STUFF_CHUNK, "the header names the chunks");
+
+// frames u8 [n, h, w, channels] -> coef i16 [n, blocks, 64]; grid (blocks / 32, n).
+__global__ __launch_bounds__(kFdctThreads) void jpeg_fdct_kernel(const uint8_t* __restrict__ frames, JpegEncGeom g, int quality,
+                                                                 int16_t* __restrict__ coef) {
+    __shared__ int ws[kFdctBlocks][72];
+    __shared__ __attribute__((aligned(16))) int16_t zz[kFdctBlocks][64];
+    __shared__ uint16_t qt[128];
+    const int tid = threadIdx.x, blk = tid >> 3, lane = tid & 7;
+    const int b = blockIdx.x * kFdctBlocks + blk;
+    const bool live = b < g.blocks;     // the last workgroup is ragged; every lane still reaches the barriers
+    const size_t f = blockIdx.y;
+    const uint8_t* frame = frames + f * (size_t)g.h * g.w * g.channels;
+    if (tid < 128) qt[tid] = (uint16_t)jpeg_quant_value(quality, tid >> 6, tid & 63);
+    JpegEncPlace p = {0, 0, 0, 0};
+    if (live) {
+        p = jpeg_enc_place(g, b);
+        int d[8], o[8];
+#pragma unroll
+        for (int x = 0; x < 8; ++x) d[x] = jpeg_enc_sample(frame, g, p.c, p.by * 8 + lane, p.bx * 8 + x) - 128;
+        jpeg_fdct_pass<true>(d, o);
+#pragma unroll
+        for (int x = 0; x < 8; ++x) ws[blk][lane * 9 + x] = o[x];
+    }
+    __syncthreads();
+    if (live) {
+        int d[8], o[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = ws[blk][i * 9 + lane];
+        jpeg_fdct_pass<false>(d, o);
+        const uint16_t* table = qt + (p.c ? 64 : 0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int nat = i * 8 + lane;
+            const int q = jpeg_quantise(o[i], table[nat]);
+            zz[blk][jpeg_zigzag_of(nat)] = (int16_t)((p.dummy && nat) ? 0 : q);
+        }
+    }
+    __syncthreads();
+    if (live) *reinterpret_cast<int4*>(coef + (f * (size_t)g.blocks + (size_t)b) * 64 + lane * 8) = *reinterpret_cast<const int4*>(&zz[blk][lane * 8]);
+}
+
+// The tables of both classes into LDS; every lane of the workgroup calls it.
+__device__ __forceinline__ void stage_tables(uint32_t* tab, const uint32_t* __restrict__ ehuff) {
+    for (int i = threadIdx.x; i < 2 * JPGE_HUFF_WORDS; i += kBlockThreads) tab[i] = ehuff[i];
+    __syncthreads();
+}
+
+// A block's coefficients as eight 16-byte loads.
+__device__ __forceinline__ void load_block(const int16_t* __restrict__ src, int16_t (&zz)[64]) {
+    const int4* s = reinterpret_cast<const int4*>(src);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int4 q = s[r];
+        const int w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            zz[r * 8 + 2 * k] = (int16_t)(w[k] & 0xffff);
+            zz[r * 8 + 2 * k + 1] = (int16_t)(w[k] >> 16);
+        }
+    }
+}
+
+// coef -> bits u32 [n, blocks + 1]: element b of a frame is block b's bit length (the scan makes offsets of them).
+__global__ __launch_bounds__(kBlockThreads) void jpeg_bits_kernel(const int16_t* __restrict__ coef, JpegEncGeom g,
+                                                                  const uint32_t* __restrict__ ehuff, uint32_t* __restrict__ bits) {
+    __shared__ uint32_t tab[2 * JPGE_HUFF_WORDS];
+    stage_tables(tab, ehuff);
+    const size_t f = blockIdx.y;
+    const int b = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (b >= g.blocks) return;
+    const int16_t* base = coef + f * (size_t)g.blocks * 64;
+    int16_t zz[64];
+    load_block(base + (size_t)b * 64, zz);
+    const int pb = jpeg_enc_pred_block(g, b);
+    const int pred = pb >= 0 ? base[(size_t)pb * 64] : 0;
+    JpegBitCounter count;
+    jpeg_encode_block(zz, pred, tab + JPGE_HUFF_WORDS * jpeg_enc_table_class(g, b), count);
+    bits[f * ((size_t)g.blocks + 1) + b] = count.bits;
+}
+
+// Inclusive scan over the workgroup's kScanChunk lanes; `total` is the sum.  lds: 4 words.
+__device__ __forceinline__ uint32_t workgroup_scan(uint32_t v, uint32_t* lds, uint32_t& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(v, o, 64);
+        if (lane >= o) v += up;
+    }
+    __syncthreads();                 // the last use of lds is over
+    if (lane == 63) lds[wave] = v;
+    __syncthreads();
+    uint32_t before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < kScanChunk / 64; ++k) {
+        const uint32_t t = lds[k];
+        if (k < wave) before += t;
+        total += t;
+    }
+    return v + before;
+}
+
+// vals u32 [n, count + 1]: the first `count` values of a frame become their exclusive prefix sums, element `count`
+// the total.  grid n.
+__global__ __launch_bounds__(kScanChunk) void jpeg_scan_kernel(uint32_t* __restrict__ vals, int count) {
+    __shared__ uint32_t lds[kScanChunk / 64];
+    uint32_t* p = vals + (size_t)blockIdx.x * ((size_t)count + 1);
+    uint32_t carry = 0;
+    for (int base = 0; base < count; base += kScanChunk) {
+        const int i = base + (int)threadIdx.x;
+        const uint32_t v = i < count ? p[i] : 0u;
+        uint32_t total;
+        const uint32_t incl = workgroup_scan(v, lds, total);
+        if (i < count) p[i] = carry + incl - v;
+        carry += total;
+    }
+    if (threadIdx.x == 0) p[count] = carry;
+}
+
+__global__ __launch_bounds__(256) void jpeg_clear_kernel(uint32_t* __restrict__ words, long long total_words) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total_words; i += (long long)gridDim.x * 256) words[i] = 0u;
+}
+
+// Whether frame f's span of the stream, words word_off[f] .. word_off[f + 1], lies inside the buffer.
+__device__ __forceinline__ bool span_ok(const long long* __restrict__ off, size_t f, long long total) {
+    return off[f] >= 0 && off[f] <= off[f + 1] && off[f + 1] <= total && off[f + 1] - off[f] < 0x40000000LL;
+}
+
+// coef, bits (offsets) -> the frame's unstuffed stream in words[word_off[f] ..]; grid (blocks / 256, n).
+__global__ __launch_bounds__(kBlockThreads) void jpeg_pack_kernel(const int16_t* __restrict__ coef, JpegEncGeom g,
+                                                                  const uint32_t* __restrict__ ehuff, const uint32_t* __restrict__ bits,
+                                                                  const long long* __restrict__ word_off, uint32_t* __restrict__ words,
+                                                                  long long total_words) {
+    __shared__ uint32_t tab[2 * JPGE_HUFF_WORDS];
+    stage_tables(tab, ehuff);
+    const size_t f = blockIdx.y;
+    const int b = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (b >= g.blocks || !span_ok(word_off, f, total_words)) return;
+    const int16_t* base = coef + f * (size_t)g.blocks * 64;
+    int16_t zz[64];
+    load_block(base + (size_t)b * 64, zz);
+    const int pb = jpeg_enc_pred_block(g, b);
+    const int pred = pb >= 0 ? base[(size_t)pb * 64] : 0;
+    JpegBitWriter out(words + word_off[f], (uint32_t)(word_off[f + 1] - word_off[f]), bits[f * ((size_t)g.blocks + 1) + b]);
+    jpeg_encode_block(zz, pred, tab + JPGE_HUFF_WORDS * jpeg_enc_table_class(g, b), out);
+    if (b == g.blocks - 1) {
+        const int pad = (8 - (out.n & 7)) & 7;      // the final fill: 1 bits to the byte boundary
+        out.put((1u << pad) - 1u, pad);
+    }
+    out.flush();
+}
+
+__device__ __forceinline__ uint32_t stream_bytes(const uint32_t* __restrict__ bits, size_t f, int blocks) {
+    return (bits[f * ((size_t)blocks + 1) + blocks] + 7u) >> 3;
+}
+
+// The lane's dword of the stream and how many of its bytes count; the bytes are in the dword most significant first.
+__device__ __forceinline__ int lane_bytes(const uint32_t* __restrict__ words, const long long* __restrict__ word_off, size_t f,
+                                          long long total_words, uint32_t nbytes, uint32_t& word) {
+    const uint32_t j0 = (blockIdx.x * (uint32_t)kStuffChunk) + threadIdx.x * 4u;
+    word = 0;
+    if (j0 >= nbytes || !span_ok(word_off, f, total_words) || (long long)(j0 >> 2) >= word_off[f + 1] - word_off[f]) return 0;
+    word = words[word_off[f] + (j0 >> 2)];
+    return (int)min(4u, nbytes - j0);
+}
+
+__device__ __forceinline__ uint32_t count_ff(uint32_t word, int valid) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c += (k < valid && ((word >> (24 - 8 * k)) & 0xffu) == 0xffu) ? 1u : 0u;
+    return c;
+}
+
+// ffc u32 [n, chunks + 1]: FF bytes of every chunk of kStuffChunk stream bytes; grid (chunks, n).
+__global__ __launch_bounds__(kScanChunk) void jpeg_ff_kernel(const uint32_t* __restrict__ bits, int blocks, const long long* __restrict__ word_off,
+                                                             const uint32_t* __restrict__ words, long long total_words,
+                                                             uint32_t* __restrict__ ffc, int chunks) {
+    __shared__ uint32_t lds[kScanChunk / 64];
+    const size_t f = blockIdx.y;
+    uint32_t word, total;
+    const int valid = lane_bytes(words, word_off, f, total_words, stream_bytes(bits, f, blocks), word);
+    workgroup_scan(count_ff(word, valid), lds, total);
+    if (threadIdx.x == 0) ffc[f * ((size_t)chunks + 1) + blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void jpeg_sizes_kernel(const uint32_t* __restrict__ bits, int blocks, const uint32_t* __restrict__ ffc,
+                                                         int chunks, uint32_t* __restrict__ sizes, int n) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f < n) sizes[f] = stream_bytes(bits, f, blocks) + ffc[(size_t)f * ((size_t)chunks + 1) + chunks] + 2u;
+}
+
+// The stream bytes to out[out_off[f] ..], a 00 behind every FF, then FF D9; grid (chunks, n).
+__global__ __launch_bounds__(kScanChunk) void jpeg_stuff_kernel(const uint32_t* __restrict__ bits, int blocks, const long long* __restrict__ word_off,
+                                                                const uint32_t* __restrict__ words, long long total_words,
+                                                                const uint32_t* __restrict__ ffc, int chunks,
+                                                                const long long* __restrict__ out_off, uint8_t* __restrict__ out,
+                                                                long long out_bytes) {
+    __shared__ uint32_t lds[kScanChunk / 64];
+    const size_t f = blockIdx.y;
+    const uint32_t nbytes = stream_bytes(bits, f, blocks);
+    uint32_t word, total;
+    const int valid = lane_bytes(words, word_off, f, total_words, nbytes, word);
+    const uint32_t mine = count_ff(word, valid);
+    const uint32_t before = workgroup_scan(mine, lds, total) - mine;
+    if (!span_ok(out_off, f, out_bytes)) return;
+    const long long first = out_off[f], end = out_off[f + 1];
+    const uint32_t* fc = ffc + f * ((size_t)chunks + 1);
+    long long at = first + (long long)blockIdx.x * kStuffChunk + threadIdx.x * 4 + fc[blockIdx.x] + before;
+    for (int k = 0; k < valid; ++k) {
+        const uint32_t byte = (word >> (24 - 8 * k)) & 0xffu;
+        if (at < end) out[at] = (uint8_t)byte;
+        ++at;
+        if (byte == 0xffu) {
+            if (at < end) out[at] = 0;
+            ++at;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const long long eoi = first + nbytes + fc[chunks];
+        if (eoi >= first && eoi + 2 <= end) {
+            out[eoi] = 0xff;
+            out[eoi + 1] = 0xd9;
+        }
+    }
+}
+
+// The argument checks every entry point shares; the geometry comes out.
+int check_shape(const char* who, int n, int h, int w, int channels, int sampling, JpegEncGeom& g) {
+    ELVIS_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 or 3, got %d", who, channels);
+    ELVIS_REQUIRE(sampling >= JPGE_SAMPLING_444 && sampling <= JPGE_SAMPLING_420, "%s: sampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got %d", who,
+                  sampling);
+    ELVIS_REQUIRE(n >= 0 && n <= 65535 && h >= 1 && w >= 1 && h <= 65535 && w <= 65535, "%s: bad shape n=%d h=%d w=%d", who, n, h, w);
+    ELVIS_REQUIRE(((long long)((w + 7) / 8 + 1) * ((h + 7) / 8 + 1)) * 3 <= JPGE_MAX_BLOCKS, "%s: a %d x %d frame has more than 2^20 blocks", who, h, w);
+    g = jpeg_enc_geometry(h, w, channels, 0, sampling);
+    return ELVIS_OK;
+}
+
+}  // namespace
+
+extern "C" int elvis_jpeg_frame_blocks(int h, int w, int channels, int sampling) {
+    JpegEncGeom g;
+    if (check_shape("elvis_jpeg_frame_blocks", 0, h, w, channels, sampling, g) != ELVIS_OK) return 0;
+    return g.blocks;
+}
+
+extern "C" int elvis_jpeg_fdct(const uint8_t* frames, int16_t* coef, int n, int h, int w, int channels, int order, int quality, int sampling,
+                               elvis_stream_t stream) {
+    JpegEncGeom g;
+    if (int rc = check_shape("elvis_jpeg_fdct", n, h, w, channels, sampling, g)) return rc;
+    ELVIS_REQUIRE(order == 0 || order == 1, "elvis_jpeg_fdct: order must be 0 (rgb) or 1 (bgr), got %d", order);
+    ELVIS_REQUIRE(quality >= 1 && quality <= 100, "elvis_jpeg_fdct: quality must be in [1, 100], got %d", quality);
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(frames && coef, "elvis_jpeg_fdct: null pointer");
+    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0, "elvis_jpeg_fdct: coef must be 16-byte aligned");
+    g.bgr = order;
+    hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)cdiv(g.blocks, kFdctBlocks), (unsigned)n), dim3(kFdctThreads), 0, (hipStream_t)stream, frames, g,
+                       quality, coef);
+    ELVIS_CHECK_LAUNCH("elvis_jpeg_fdct");
+    elvis_note_launch("jpeg_fdct_kernel");
+    return ELVIS_OK;
+}
+
+extern "C" int elvis_jpeg_bits(const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
+                               elvis_stream_t stream) {
+    JpegEncGeom g;
+    if (int rc = check_shape("elvis_jpeg_bits", n, h, w, channels, sampling, g)) return rc;
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(coef && ehuff && bits, "elvis_jpeg_bits: null pointer");
+    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)bits & 3) == 0 && ((uintptr_t)ehuff & 3) == 0,
+                  "elvis_jpeg_bits: coef must be 16-byte aligned, ehuff and bits 4-byte aligned");
+    hipLaunchKernelGGL(jpeg_bits_kernel, dim3((unsigned)cdiv(g.blocks, kBlockThreads), (unsigned)n), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g,
+                       ehuff, bits);
+    ELVIS_CHECK_LAUNCH("elvis_jpeg_bits");
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)n), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.blocks);
+    ELVIS_CHECK_LAUNCH("elvis_jpeg_bits");
+    elvis_note_launch("jpeg_bits_kernel");
+    return ELVIS_OK;
+}
+
+extern "C" int elvis_jpeg_pack(const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,
+                               int64_t total_words, uint32_t* ffc, int chunks, uint32_t* sizes, int n, int h, int w, int channels, int sampling,
+                               elvis_stream_t stream) {
+    JpegEncGeom g;
+    if (int rc = check_shape("elvis_jpeg_pack", n, h, w, channels, sampling, g)) return rc;
+    ELVIS_REQUIRE(total_words >= 0 && total_words < (1LL << 38), "elvis_jpeg_pack: total_words must be in [0, 2^38)");
+    ELVIS_REQUIRE(chunks >= 1 && chunks <= 65535 * 32, "elvis_jpeg_pack: chunks must be in [1, 2^21), got %d", chunks);
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(coef && ehuff && bits && word_off && words && ffc && sizes, "elvis_jpeg_pack: null pointer");
+    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0 && (((uintptr_t)bits | (uintptr_t)ehuff | (uintptr_t)words | (uintptr_t)ffc | (uintptr_t)sizes) & 3) == 0 &&
+                      ((uintptr_t)word_off & 7) == 0,
+                  "elvis_jpeg_pack: coef must be 16-byte, word_off 8-byte, the other buffers 4-byte aligned");
+    hipLaunchKernelGGL(jpeg_clear_kernel, dim3((unsigned)std::max(1, std::min(4096, cdiv(total_words, 256)))), dim3(256), 0, (hipStream_t)stream, words,
+                       (long long)total_words);
+    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
+    hipLaunchKernelGGL(jpeg_pack_kernel, dim3((unsigned)cdiv(g.blocks, kBlockThreads), (unsigned)n), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g,
+                       ehuff, bits, (const long long*)word_off, words, (long long)total_words);
+    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
+    hipLaunchKernelGGL(jpeg_ff_kernel, dim3((unsigned)chunks, (unsigned)n), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.blocks,
+                       (const long long*)word_off, (const uint32_t*)words, (long long)total_words, ffc, chunks);
+    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)n), dim3(kScanChunk), 0, (hipStream_t)stream, ffc, chunks);
+    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
+    hipLaunchKernelGGL(jpeg_sizes_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, bits, g.blocks, (const uint32_t*)ffc, chunks,
+                       sizes, n);
+    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
+    elvis_note_launch("jpeg_pack_kernel");
+    return ELVIS_OK;
+}
+
+extern "C" int elvis_jpeg_stuff(const uint32_t* bits, const int64_t* word_off, const uint32_t* words, int64_t total_words, const uint32_t* ffc,
+                                int chunks, const int64_t* out_off, uint8_t* out, int64_t out_bytes, int n, int h, int w, int channels,
+                                int sampling, elvis_stream_t stream) {
+    JpegEncGeom g;
+    if (int rc = check_shape("elvis_jpeg_stuff", n, h, w, channels, sampling, g)) return rc;
+    ELVIS_REQUIRE(total_words >= 0 && total_words < (1LL << 38), "elvis_jpeg_stuff: total_words must be in [0, 2^38)");
+    ELVIS_REQUIRE(out_bytes >= 0 && out_bytes < (1LL << 40), "elvis_jpeg_stuff: out_bytes must be in [0, 2^40)");
+    ELVIS_REQUIRE(chunks >= 1 && chunks <= 65535 * 32, "elvis_jpeg_stuff: chunks must be in [1, 2^21), got %d", chunks);
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(bits && word_off && words && ffc && out_off && out, "elvis_jpeg_stuff: null pointer");
+    ELVIS_REQUIRE((((uintptr_t)bits | (uintptr_t)words | (uintptr_t)ffc) & 3) == 0 && (((uintptr_t)word_off | (uintptr_t)out_off) & 7) == 0,
+                  "elvis_jpeg_stuff: word_off and out_off must be 8-byte, bits, words and ffc 4-byte aligned");
+    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)chunks, (unsigned)n), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.blocks,
+                       (const long long*)word_off, words, (long long)total_words, ffc, chunks, (const long long*)out_off, out, (long long)out_bytes);
+    ELVIS_CHECK_LAUNCH("elvis_jpeg_stuff");
+    elvis_note_launch("jpeg_stuff_kernel");
+    return ELVIS_OK;
+}

@@ -16,7 +16,7 @@ IOError("Failed to load frame: <path>") for a corrupt file, as `frameio.load_fra
 ValueError before any launch.  The pixels are those of a libjpeg-turbo PIL with default settings - the slow integer
 IDCT, fancy upsampling - bit for bit; tests/_jpeg_ref.py states them.  What PIL makes of corrupt data (warnings, partial
 pictures) is not reproduced.  Opt-in: `frameio.load_frame` stays PIL, and the directory drivers read through PIL unless
-called with `png_reader="device"`.  There is no writer: the reference never writes JPEG.
+called with `png_reader="device"`.  The writer is jpeg_write.py.
 """
 from __future__ import annotations
 

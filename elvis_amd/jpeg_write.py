@@ -1,0 +1,308 @@
+"""JPEG frames written by the device (csrc/jpeg_write.hip, csrc/jpeg_encode.h): the reference writes frames through
+`cv2.imwrite(path, frame)` and lets the suffix choose the format (`save_frame`, elvis.py:131-135; `save_frames(...,
+pattern=)`, elvis.py:160-175), and every one of its loaders takes `.jpg` / `.jpeg` beside `.png`.  This is the device
+path for those suffixes, the writer half of jpeg.py:
+
+  encode_jpeg_device(frames_d)                 resident clip -> one complete baseline JPEG file (bytes) per frame
+  save_jpeg_frames_device(frames_d, paths)     the same, written to `paths`
+  save_jpeg_frames(frames, paths, device)      host arrays, uploaded in chunks of 32 MB
+  jpeg_roundtrip_device(frames_d, quality)     encode, then jpeg.decode_jpeg_device: (decoded resident clip, bytes per frame)
+  jpeg_quant_tables(quality)                   host: the two quantisation tables
+  jpeg_file_header(width, height, ...)         host: everything in front of the entropy-coded bytes
+
+Colour conversion, edge replication, chroma downsampling, the forward DCT, the quantiser, the Huffman coding, the bit
+packing and the byte stuffing run as HIP kernels; the host plans the layout from two small downloads (a frame's bit
+count, then its byte count), writes the headers and downloads the finished scans.  Pixels and coefficients never visit
+the host.  The arithmetic is libjpeg's (jccolor.c, jcsample.c, jfdctint.c, jcdctmgr.c, jchuff.c with the Annex K tables,
+one interleaved scan, no restart interval): against a libjpeg-turbo PIL at the same quality and sampling with
+`optimize=False`, the quantisation tables, the SOF0 / SOS contents and the entropy-coded bytes are equal bit for bit;
+tests/_jpeg_write_ref.py states them.  Equality of whole files is not claimed (the JFIF header's density fields are the
+writer's own), and PARITY WITH cv2 IS UNPINNED: quality 95 and 4:2:0, the defaults here, are what `cv2.imwrite` asks its
+libjpeg for, but no cv2 is at hand to compare with.  Opt-in: `frameio.save_frame` stays PIL, and the directory drivers
+write `.jpg` names through PIL unless called with `jpeg_writer="device"`.
+"""
+from __future__ import annotations
+
+import os
+import struct
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from ._lib import check, lib, ptr
+from .jpeg import ZIGZAG
+from .ops import _s
+
+SUBSAMPLINGS = ("444", "422", "420")
+_FACTORS = {"444": (1, 1), "422": (2, 1), "420": (2, 2)}
+SCAN_CHUNK_BLOCKS = 256         # ELVIS_JPEG_SCAN_CHUNK: values of one step of the device prefix sums
+STUFF_CHUNK_BYTES = 1024        # ELVIS_JPEG_STUFF_CHUNK: stream bytes of one workgroup of the stuffing pass
+HUFF_WORDS = 272                # per table class: 16 DC entries by category, 256 AC entries by symbol
+MAX_BLOCKS = 1 << 20            # blocks of a frame
+MAX_FRAMES = 65535              # frames of one launch
+UPLOAD_CHUNK_BYTES = 32 << 20
+# ITU-T T.81 Annex K.1, K.2: the quantisation tables in natural order
+BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87,
+             80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92,
+             95, 98, 112, 100, 103, 99)
+BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99) + (99,) * 36
+# Annex K.3: the Huffman tables as (codes of each length 1..16, symbols in code order)
+STD_DC = (((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+          ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))))
+STD_AC = (((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125),
+           (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+            0x91, 0xA1, 0x08, 0x23, 0x42, 0xB1, 0xC1, 0x15, 0x52, 0xD1, 0xF0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0A, 0x16, 0x17, 0x18,
+            0x19, 0x1A, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+            0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74, 0x75,
+            0x76, 0x77, 0x78, 0x79, 0x7A, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+            0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3,
+            0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE1, 0xE2, 0xE3, 0xE4, 0xE5,
+            0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF1, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA)),
+          ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119),
+           (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+            0x14, 0x42, 0x91, 0xA1, 0xB1, 0xC1, 0x09, 0x23, 0x33, 0x52, 0xF0, 0x15, 0x62, 0x72, 0xD1, 0x0A, 0x16, 0x24, 0x34, 0xE1, 0x25,
+            0xF1, 0x17, 0x18, 0x19, 0x1A, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47,
+            0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74,
+            0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+            0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA,
+            0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE2, 0xE3, 0xE4,
+            0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA)))
+_JFIF = b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00"       # version 1.1, no units, aspect 1:1, no thumbnail
+
+
+# ----------------------------------------------------------------------------- the host's part
+def _check_quality(quality, who: str) -> int:
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise ValueError(f"{who}: quality must be an integer in 1..100, got {quality!r}")
+    return int(quality)
+
+
+def _check_subsampling(subsampling, who: str) -> int:
+    if not isinstance(subsampling, str) or subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"{who}: subsampling must be one of {SUBSAMPLINGS}, got {subsampling!r}")
+    return SUBSAMPLINGS.index(subsampling)
+
+
+def jpeg_quant_tables(quality: int = 95) -> Tuple[np.ndarray, np.ndarray]:
+    """Host only: (luma, chroma) quantisation tables, uint16 [64] in natural order, as libjpeg's
+    `jpeg_set_quality(quality, force_baseline=TRUE)` scales the Annex K tables: (base * scale + 50) // 100 clamped to
+    1..255, scale = 5000 // quality below 50 and 200 - 2 * quality from there."""
+    q = _check_quality(quality, "jpeg_quant_tables")
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((np.asarray(base, np.int64) * scale + 50) // 100, 1, 255).astype(np.uint16) for base in (BASE_LUMA, BASE_CHROMA))
+
+
+def huffman_codes(counts: Sequence[int], values: Sequence[int]) -> Dict[int, Tuple[int, int]]:
+    """symbol -> (code, length) of a (16 counts, values) table (T.81 C.2)."""
+    out, code, k = {}, 0, 0
+    for length in range(1, 17):
+        for _ in range(counts[length - 1]):
+            out[values[k]] = (code, length)
+            k += 1
+            code += 1
+        code <<= 1
+    return out
+
+
+def encode_tables() -> np.ndarray:
+    """What the kernels look up: uint32 [2, 272], per table class (0 luma, 1 chroma) 16 DC entries by category and 256 AC
+    entries by symbol, (code << 5) | length; 0 where the table has no such symbol."""
+    tab = np.zeros((2, HUFF_WORDS), np.uint32)
+    for t in range(2):
+        for sym, (code, length) in huffman_codes(*STD_DC[t]).items():
+            tab[t, sym] = code << 5 | length
+        for sym, (code, length) in huffman_codes(*STD_AC[t]).items():
+            tab[t, 16 + sym] = code << 5 | length
+    return tab
+
+
+def _segment(marker: int, body: bytes) -> bytes:
+    return bytes([0xFF, marker]) + struct.pack(">H", len(body) + 2) + body
+
+
+def jpeg_file_header(width: int, height: int, channels: int = 3, quality: int = 95, subsampling: str = "420") -> bytes:
+    """Host only: everything of a file in front of its entropy-coded bytes - SOI, the JFIF APP0 segment, one DQT segment per
+    table, SOF0, the DHT segments (DC 0, AC 0, and DC 1, AC 1 for colour) and SOS; the device's scan, which ends with
+    EOI, follows it.  Components 1 (Y: table 0, Huffman tables 0) and, for colour, 2 and 3 (Cb, Cr: table 1, Huffman
+    tables 1)."""
+    who = "jpeg_file_header"
+    q = _check_quality(quality, who)
+    _check_subsampling(subsampling, who)
+    if isinstance(channels, bool) or channels not in (1, 3):
+        raise ValueError(f"{who}: channels must be 1 or 3, got {channels!r}")
+    if not 1 <= int(width) <= 65535 or not 1 <= int(height) <= 65535:
+        raise ValueError(f"{who}: width and height must be in 1..65535, got {width} x {height}")
+    hmax, vmax = _FACTORS[subsampling] if channels == 3 else (1, 1)
+    comps = [(1, hmax, vmax, 0)] + ([(2, 1, 1, 1), (3, 1, 1, 1)] if channels == 3 else [])
+    ntab = 2 if channels == 3 else 1
+    out = bytearray(b"\xff\xd8") + _segment(0xE0, _JFIF)
+    for t, table in enumerate(jpeg_quant_tables(q)[:ntab]):
+        out += _segment(0xDB, bytes([t]) + bytes(int(table[z]) for z in ZIGZAG))
+    out += _segment(0xC0, bytes([8]) + struct.pack(">HH", int(height), int(width)) + bytes([len(comps)])
+                    + b"".join(bytes([cid, h << 4 | v, tq]) for cid, h, v, tq in comps))
+    for t in range(ntab):
+        out += _segment(0xC4, bytes([t]) + bytes(STD_DC[t][0]) + bytes(STD_DC[t][1]))
+        out += _segment(0xC4, bytes([0x10 | t]) + bytes(STD_AC[t][0]) + bytes(STD_AC[t][1]))
+    out += _segment(0xDA, bytes([len(comps)]) + b"".join(bytes([cid, tq * 0x11]) for cid, _, _, tq in comps) + bytes([0, 63, 0]))
+    return bytes(out)
+
+
+# ----------------------------------------------------------------------------- the device forms
+def _check_clip(frames_d, order, quality, subsampling, who: str):
+    """Every argument check, before the library is touched: (n, h, w, c, order code, quality, sampling code)."""
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"{who}: order must be 'bgr' or 'rgb', got {order!r}")
+    q = _check_quality(quality, who)
+    scode = _check_subsampling(subsampling, who)
+    if not isinstance(frames_d, torch.Tensor) or frames_d.dtype != torch.uint8:
+        raise ValueError(f"{who}: frames must be a uint8 tensor")
+    if frames_d.dim() not in (3, 4):
+        raise ValueError(f"{who}: frames must be [n,H,W,3], [n,H,W,1] or [n,H,W], got {tuple(frames_d.shape)}")
+    n, h, w = (int(v) for v in frames_d.shape[:3])
+    c = int(frames_d.shape[3]) if frames_d.dim() == 4 else 1
+    if c not in (1, 3):
+        raise ValueError(f"{who}: {c} channels (C must be 1 or 3)")
+    if h < 1 or w < 1:
+        raise ValueError(f"{who}: empty frames {tuple(frames_d.shape)}")
+    if h > 65535 or w > 65535 or 3 * (-(-w // 8) + 1) * (-(-h // 8) + 1) > MAX_BLOCKS:
+        raise ValueError(f"{who}: a {h} x {w} frame is too large (sides up to 65535, 3 * (W/8 + 1) * (H/8 + 1) up to 2^20)")
+    if n > MAX_FRAMES:
+        raise ValueError(f"{who}: {n} frames in one launch (at most {MAX_FRAMES}); encode the clip in parts")
+    if not frames_d.is_cuda:
+        raise ValueError(f"{who}: frames must be resident on the device (got a '{frames_d.device}' tensor)")
+    if not frames_d.is_contiguous():
+        raise ValueError(f"{who}: frames must be contiguous")
+    return n, h, w, c, int(order == "bgr"), q, scode
+
+
+def _guarded(nbytes: int, guard: int, dev, fill: int = 0):
+    """(a uint8 buffer of nbytes holding `fill` with `guard` bytes of 0xA5 on either side, the payload's view).  Every
+    byte the kernels read from a work buffer they wrote before; `fill` is the tests' knob to show it."""
+    buf = torch.full((nbytes + 2 * guard,), fill, dtype=torch.uint8, device=dev)
+    if guard:
+        buf[:guard] = 0xA5
+        buf[guard + nbytes:] = 0xA5
+    return buf, buf[guard:guard + nbytes]
+
+
+def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, guard: int = 0, fill: int = 0):
+    """The four calls and the two small downloads between them.  Returns None for an empty clip, else a dict: `out_buf`
+    (the finished scans on the device with `guard` bytes of 0xA5 on either side), `out_off` (int64 [n + 1], frame f's scan
+    is bytes out_off[f] .. out_off[f + 1] of the payload), `header`, and the work buffers with their guards (`coef_buf`,
+    `bits_buf`, `words_buf`, `ffc_buf`, `sizes_buf`) with `blocks` and `chunks`; `out` is the payload of `out_buf`."""
+    n, h, w, c, ocode, q, scode = _check_clip(frames_d, order, quality, subsampling, who)
+    if n == 0:
+        return None
+    if guard % 16:
+        raise ValueError("guard must be a multiple of 16")
+    dev = frames_d.device
+    blocks = int(lib().elvis_jpeg_frame_blocks(h, w, c, scode))      # the kernels' own count sizes the buffers
+    if blocks < 1:
+        raise ValueError(f"{who}: the library refuses a {h} x {w} frame of {c} channel(s)")
+    header = jpeg_file_header(w, h, c, q, subsampling)
+    s = _s(frames_d)
+    with torch.cuda.device(dev):
+        ehuff_d = torch.from_numpy(encode_tables().view(np.int32)).to(dev)
+        coef_buf, coef_d = _guarded(n * blocks * 128, guard, dev, fill)
+        bits_buf, bits_d = _guarded(n * (blocks + 1) * 4, guard, dev, fill)
+        check(lib().elvis_jpeg_fdct(ptr(frames_d), ptr(coef_d), n, h, w, c, ocode, q, scode, s), dev)
+        check(lib().elvis_jpeg_bits(ptr(coef_d), ptr(ehuff_d), ptr(bits_d), n, h, w, c, scode, s), dev)
+        # the first synchronisation of a clip: every frame's bit count
+        total_bits = bits_d.view(torch.int32).view(n, blocks + 1)[:, blocks].cpu().numpy().view(np.uint32).astype(np.int64)
+        stream_bytes = (total_bits + 7) // 8
+        word_off = np.concatenate([[0], np.cumsum((stream_bytes + 3) // 4)]).astype(np.int64)
+        total_words = int(word_off[-1])
+        chunks = max(1, int(-(-int(stream_bytes.max()) // STUFF_CHUNK_BYTES)))
+        word_off_d = torch.from_numpy(word_off).to(dev)
+        words_buf, words_d = _guarded(total_words * 4, guard, dev, fill)
+        ffc_buf, ffc_d = _guarded(n * (chunks + 1) * 4, guard, dev, fill)
+        sizes_buf, sizes_d = _guarded(n * 4, guard, dev, fill)
+        check(lib().elvis_jpeg_pack(ptr(coef_d), ptr(ehuff_d), ptr(bits_d), ptr(word_off_d), ptr(words_d), total_words, ptr(ffc_d), chunks,
+                                    ptr(sizes_d), n, h, w, c, scode, s), dev)
+        # the second: every frame's byte count with the stuffed zeros and EOI
+        sizes = sizes_d.cpu().numpy().view(np.uint32).astype(np.int64)
+        out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        total = int(out_off[-1])
+        out_off_d = torch.from_numpy(out_off).to(dev)
+        out_buf, out_d = _guarded(total, guard, dev, fill)
+        check(lib().elvis_jpeg_stuff(ptr(bits_d), ptr(word_off_d), ptr(words_d), total_words, ptr(ffc_d), chunks, ptr(out_off_d), ptr(out_d),
+                                     total, n, h, w, c, scode, s), dev)
+    return {"out_buf": out_buf, "out": out_d, "out_off": out_off, "header": header, "coef_buf": coef_buf, "bits_buf": bits_buf,
+            "words_buf": words_buf, "ffc_buf": ffc_buf, "sizes_buf": sizes_buf, "blocks": blocks, "chunks": chunks}
+
+
+def _encode_to_host(frames_d, order, quality, subsampling, who: str) -> List[bytes]:
+    got = _encode_clip(frames_d, order, quality, subsampling, who)
+    if got is None:
+        return []
+    host = got["out"].cpu().numpy()
+    off = got["out_off"]
+    return [got["header"] + host[int(off[f]):int(off[f + 1])].tobytes() for f in range(off.size - 1)]
+
+
+def encode_jpeg_device(frames_d: torch.Tensor, order: str = "bgr", quality: int = 95, subsampling: str = "420") -> List[bytes]:
+    """One complete baseline JPEG file per frame of a resident contiguous uint8 clip [n,H,W,3], [n,H,W,1] or [n,H,W].
+    `order` is the channel order of a 3-channel clip ("bgr", what `save_frame` takes, or "rgb"); `quality` 1..100 and
+    `subsampling` "444" | "422" | "420" are libjpeg's; quality 95 and 4:2:0, the defaults, are what `cv2.imwrite` uses.
+    A gray clip is one component and `subsampling` is ignored.  A frame's bytes do not depend on the frames it is
+    encoded with.  ValueError before any launch for a bad argument; an empty clip gives []."""
+    return _encode_to_host(frames_d, order, quality, subsampling, "encode_jpeg_device")
+
+
+def save_jpeg_frames_device(frames_d: torch.Tensor, paths: Sequence, order: str = "bgr", quality: int = 95, subsampling: str = "420") -> None:
+    """`encode_jpeg_device`, and frame i written to paths[i]; directories are created as `save_frame` does."""
+    paths = list(paths)
+    if not isinstance(frames_d, torch.Tensor) or frames_d.dim() < 1 or len(paths) != frames_d.shape[0]:
+        raise ValueError(f"save_jpeg_frames_device: {len(paths)} path(s) for the clip {tuple(getattr(frames_d, 'shape', ()))}")
+    for path, data in zip(paths, _encode_to_host(frames_d, order, quality, subsampling, "save_jpeg_frames_device")):
+        os.makedirs(os.path.dirname(os.fspath(path)) or ".", exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(data)
+
+
+def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=None, order: str = "bgr", quality: int = 95,
+                     subsampling: str = "420") -> None:
+    """Host frames - uint8 (H,W,3), (H,W,1) or (H,W) arrays, a list or one [n,...] array - written as JPEGs to `paths`
+    through the device.  Uploaded and encoded `chunk_frames` frames at a time, by default as many as make 32 MB (5 at
+    1080p); a run of equal shapes is one clip.  The files do not depend on the chunk size."""
+    who = "save_jpeg_frames"
+    paths = list(paths)
+    if len(frames) != len(paths):
+        raise ValueError(f"{who}: {len(frames)} frame(s) for {len(paths)} path(s)")
+    if chunk_frames is not None and (isinstance(chunk_frames, bool) or int(chunk_frames) < 1):
+        raise ValueError("chunk_frames must be at least 1")
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"{who}: order must be 'bgr' or 'rgb', got {order!r}")
+    _check_quality(quality, who)
+    _check_subsampling(subsampling, who)
+    arrays = [np.asarray(f) for f in frames]
+    for a in arrays:
+        if a.dtype != np.uint8 or a.ndim not in (2, 3):
+            raise ValueError(f"{who}: frames are uint8 (H,W,3), (H,W,1) or (H,W) arrays, got {a.dtype} {a.shape}")
+    dev = L.resolve_device(device)
+    at = 0
+    with torch.cuda.device(dev):
+        while at < len(arrays):
+            shape = arrays[at].shape
+            step = int(chunk_frames) if chunk_frames is not None else max(1, UPLOAD_CHUNK_BYTES // max(1, arrays[at].size))
+            end = at + 1
+            while end < len(arrays) and end - at < step and arrays[end].shape == shape:
+                end += 1
+            clip = torch.from_numpy(np.ascontiguousarray(np.stack(arrays[at:end], axis=0))).to(dev)
+            save_jpeg_frames_device(clip, paths[at:end], order, quality, subsampling)
+            at = end
+
+
+def jpeg_roundtrip_device(frames_d: torch.Tensor, quality: int = 95, subsampling: str = "420", order: str = "bgr"):
+    """An intra codec in the loop: `encode_jpeg_device` at `quality`, then `jpeg.decode_jpeg_device` of those files.
+    Returns (the decoded resident clip, uint8 [n,H,W,C] in the clip's own channel count and `order`; the bytes of every
+    frame's file, int64 [n]) - the pixels a client would see and the rate they cost."""
+    from .jpeg import decode_jpeg_device
+    files = _encode_to_host(frames_d, order, quality, subsampling, "jpeg_roundtrip_device")
+    if not files:
+        raise ValueError("jpeg_roundtrip_device: no frames")
+    c = int(frames_d.shape[3]) if frames_d.dim() == 4 else 1
+    decoded = decode_jpeg_device(files, frames_d.device, order, c)
+    return decoded, np.asarray([len(f) for f in files], dtype=np.int64)

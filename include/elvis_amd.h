@@ -949,6 +949,58 @@ int elvis_jpeg_idct(const int16_t* coef, int64_t stride_blocks, const int32_t* f
 int elvis_jpeg_colour(const uint8_t* planes, int64_t stride_blocks, const int32_t* fd, uint8_t* frames, int n, int h, int w,
                       int channels, int order, elvis_stream_t stream);
 
+/* ------------------------------------------------------------------ JPEG writer (jpeg_write.hip, jpeg_encode.h)
+ * Baseline JPEG files written by the device in place of cv2.imwrite(path, frame) with a .jpg / .jpeg suffix
+ * (save_frame, elvis.py:131-135; save_frames(..., pattern=), elvis.py:160-175): libjpeg's forward path, so that against a
+ * libjpeg-turbo at the same quality and sampling without optimised tables the quantisation tables and the entropy-coded
+ * bytes are equal bit for bit; tests/_jpeg_write_ref.py states them.  frames u8 [n, h, w, channels], channels 1 (gray,
+ * one component, sampling ignored) or 3 (order 0 = RGB, 1 = BGR; sampling 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 of Y, Cb,
+ * Cr).  One interleaved scan, no restart interval, the Annex K Huffman tables.  The host plans the layout between the
+ * calls from two small downloads - a frame's bit count, then its byte count - writes the headers and downloads the
+ * finished scans; pixels and coefficients never visit it (the caller synchronises, no entry point does):
+ *   blocks   elvis_jpeg_frame_blocks: the blocks of a frame in MCU scan order (gray: ceil(w/8) * ceil(h/8); colour:
+ *            hmax * vmax luma blocks, Cb, Cr per MCU, dummy blocks included), 0 for a shape that is refused.
+ *   1. elvis_jpeg_fdct: one launch from pixels to coef i16 [n, blocks, 64], quantised, zig-zag order, MCU scan order.
+ *      jccolor.c: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11058 R - 21710 G + 32768 B + (128 << 16) + 32767)
+ *      >> 16, Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.  jcprepct.c / jcsample.c: the last column is
+ *      repeated to whole blocks, an odd 4:2:0 frame's last row once, then h2v1 (a + b + bias) >> 1 with bias 0, 1, 0, 1 ...
+ *      or h2v2 (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2 ... along the output row, then the plane's last row is
+ *      repeated to whole blocks.  jfdctint.c on samples less 128 (CONST_BITS 13, PASS1_BITS 2, rows then columns, descales
+ *      round half up, int32).  Quantiser: sign(c) * ((|c| + (q8 >> 1)) / q8) with q8 = table << 3 and the tables of
+ *      jpeg_set_quality(quality, force_baseline = TRUE) of Annex K.  A dummy block (jccoefct.c) has AC 0 and the DC of the
+ *      block before it in its MCU.  No pixel outside the frame is read.
+ *   2. elvis_jpeg_bits: ehuff u32 [2, 272] = per table class (0 luma, 1 chroma) 16 DC entries by category and 256 AC
+ *      entries by symbol, (code << 5) | length, 0 where the table has no such symbol.  bits u32 [n, blocks + 1]: the bit
+ *      offset of every block's code in its frame's stream (T.81 F.1.2: DC differences per component in scan order, ZRL,
+ *      EOB unless coefficient 63 is set) and, in element `blocks`, the frame's bit count.  The prefix sum takes
+ *      ELVIS_JPEG_SCAN_CHUNK values a step.
+ *   3. elvis_jpeg_pack: word_off i64 [n + 1], the caller's layout: frame f's stream before stuffing is words
+ *      [word_off[f], word_off[f + 1]) of `words` (total_words of them), at least ceil(ceil(bit count / 8) / 4), bytes
+ *      most significant first in a word.  The call clears the words, every block writes its code at its own bit offset
+ *      (shared words by vector atomic OR), the last block adds the 1-fill.  ffc u32 [n, chunks + 1]: the FF bytes before
+ *      every chunk of ELVIS_JPEG_STUFF_CHUNK stream bytes and, in element `chunks`, of the frame (chunks >= the chunks of
+ *      the longest frame).  sizes u32 [n]: stream bytes + FF bytes + 2.
+ *   4. elvis_jpeg_stuff: out_off i64 [n + 1], the caller's layout of `out` from sizes: frame f's finished scan - FF
+ *      followed by 00, the filled last byte, FF D9 - is written to out[out_off[f] .. out_off[f + 1]).
+ * A frame whose span of words or of out does not lie inside the buffer is not written.  The same input gives the same
+ * bytes, alone or in a batch, whatever the buffers held.
+ * ELVIS_E_INVALID before any launch: channels outside {1, 3}, a bad order or sampling, quality outside [1, 100], n
+ * outside [0, 65535], h or w outside [1, 65535], more than 2^20 blocks a frame, chunks under 1, a negative size, a null
+ * pointer, a misaligned buffer (coef 16, the offset tables 8, the others 4 bytes).  n == 0 is a no-op. */
+#define ELVIS_JPEG_SCAN_CHUNK 256
+#define ELVIS_JPEG_STUFF_CHUNK 1024
+int elvis_jpeg_frame_blocks(int h, int w, int channels, int sampling);
+int elvis_jpeg_fdct(const uint8_t* frames, int16_t* coef, int n, int h, int w, int channels, int order, int quality, int sampling,
+                    elvis_stream_t stream);
+int elvis_jpeg_bits(const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
+                    elvis_stream_t stream);
+int elvis_jpeg_pack(const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,
+                    int64_t total_words, uint32_t* ffc, int chunks, uint32_t* sizes, int n, int h, int w, int channels, int sampling,
+                    elvis_stream_t stream);
+int elvis_jpeg_stuff(const uint32_t* bits, const int64_t* word_off, const uint32_t* words, int64_t total_words, const uint32_t* ffc,
+                     int chunks, const int64_t* out_off, uint8_t* out, int64_t out_bytes, int n, int h, int w, int channels, int sampling,
+                     elvis_stream_t stream);
+
 /* ------------------------------------------------------------------ Real-ESRGAN / RRDBNet (rrdb.hip)
  * The network behind RealESRGANer.enhance (elvis.py:2515): RRDBNet(3, 3, 64, num_block, 32, scale) on f16 NHWC tensors.
  * Channel counts are the padded ones the kernel runs: cin in {32, 64, 96, 128, 160, 192}, cout in {32, 64}. */
