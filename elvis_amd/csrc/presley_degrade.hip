@@ -190,6 +190,7 @@ extern "C" int elvis_degrade_scale_u8(const uint8_t* src, const int32_t* scales,
     hipLaunchKernelGGL(degrade_scale_kernel, dim3((unsigned)(n * by * bx)), dim3(ELVIS_WAVE), (size_t)ScaleLds(block, c).bytes,
                        (hipStream_t)stream, src, scales, dst, h, w, c, block, by, bx, tab_starts, tab_src, tab_w, tab_len);
     ELVIS_CHECK_LAUNCH("elvis_degrade_scale_u8");
+    elvis_note_launch("degrade_scale_kernel");
     return ELVIS_OK;
 }
 
@@ -206,5 +207,6 @@ extern "C" int elvis_degrade_gaussian_fx_u8(const uint8_t* src, const int32_t* r
     hipLaunchKernelGGL(degrade_gaussian_fx_kernel, dim3((unsigned)(n * by * bx)), dim3(ELVIS_WAVE), shmem, (hipStream_t)stream,
                        src, rounds, dst, h, w, c, block, by, bx, tap0, tap1, tap2);
     ELVIS_CHECK_LAUNCH("elvis_degrade_gaussian_fx_u8");
+    elvis_note_launch("degrade_gaussian_fx_kernel");
     return ELVIS_OK;
 }

@@ -240,6 +240,8 @@ extern "C" int elvis_resize_area_u8(const uint8_t* src, uint8_t* dst, int n, int
     else ELVIS_AREA_LAUNCH(false, false);
 #undef ELVIS_AREA_LAUNCH
     ELVIS_CHECK_LAUNCH(who);
+    elvis_note_launch(whole ? (direct ? "resize_area_kernel<whole,direct>" : "resize_area_kernel<whole,lds>")
+                            : (direct ? "resize_area_kernel<frac,direct>" : "resize_area_kernel<frac,lds>"));
     return ELVIS_OK;
 }
 
@@ -252,5 +254,6 @@ extern "C" int elvis_resize_nearest_u8(const uint8_t* src, uint8_t* dst, int n, 
     ELVIS_REQUIRE((long long)n * hd < (1LL << 31), "%s: too many rows", who);
     hipLaunchKernelGGL(resize_nearest_kernel, dim3((unsigned)(n * hd)), dim3(256), 0, (hipStream_t)stream, src, dst, hs, ws, hd, wd, c);
     ELVIS_CHECK_LAUNCH(who);
+    elvis_note_launch("resize_nearest_kernel");
     return ELVIS_OK;
 }

@@ -307,6 +307,7 @@ class _Pending:
     status_d: torch.Tensor        # i32 [nseg, 2]: code, MCUs done
     seg_frame: np.ndarray
     n: int
+    tables_d: Optional[torch.Tensor] = None   # u8 [n, 8, TABLE_BYTES], the derived code tables: kept for `_decode_clip` only
 
 
 def _guarded(nbytes: int, guard: int, dev, zero: bool = False):
@@ -319,11 +320,12 @@ def _guarded(nbytes: int, guard: int, dev, zero: bool = False):
 
 
 def _launch_decode(files: Sequence, infos: Sequence[JpegInfo], frames_out: torch.Tensor, order: str, channels: int, *,
-                   guard: int = 0, upload_offset: int = 0):
+                   guard: int = 0, upload_offset: int = 0, keep_tables: bool = False):
     """Code tables, entropy decode, IDCT, upsampling and colour of one clip into frames_out [n,H,W,channels] (resident,
     contiguous); nothing is downloaded.  `guard` bytes of 0xA5 go on either side of the coefficient and plane buffers, and
-    the uploaded bytes start `upload_offset` bytes past a dword (the tests' knobs).  Returns the _Pending, the
-    coefficient buffer and the plane buffer with their guards, and the plan."""
+    the uploaded bytes start `upload_offset` bytes past a dword; `keep_tables` leaves the derived code tables in the
+    _Pending (the tests' knobs).  Returns the _Pending, the coefficient buffer and the plane buffer with their guards,
+    and the plan."""
     dev = frames_out.device
     n = len(files)
     h, w = int(frames_out.shape[1]), int(frames_out.shape[2])
@@ -356,7 +358,7 @@ def _launch_decode(files: Sequence, infos: Sequence[JpegInfo], frames_out: torch
         check(lib().elvis_jpeg_colour(ptr(plane_d), plan.stride_blocks, ptr(fd_d), ptr(frames_out), n, h, w, channels, int(order == "bgr"), s), dev)
     # the work buffers are not kept: every launch above is on the current stream, and the allocator hands a freed block
     # only to later work on that stream
-    return _Pending(status_d, plan.seg_frame, n), coef_buf, plane_buf, plan
+    return _Pending(status_d, plan.seg_frame, n, tables_d if keep_tables else None), coef_buf, plane_buf, plan
 
 
 def _frame_codes(pending: _Pending, status: np.ndarray) -> List[int]:
@@ -387,11 +389,12 @@ def _decode_clip(files: Sequence, device, order: str, channels: int, names: Opti
     with torch.cuda.device(dev):
         frames_buf, payload = _guarded(n * h * w * channels, guard, dev)
         frames = payload.view(n, h, w, channels)
-        pending, coef_buf, plane_buf, plan = _launch_decode(files, infos, frames, order, channels, guard=guard, upload_offset=upload_offset)
+        pending, coef_buf, plane_buf, plan = _launch_decode(files, infos, frames, order, channels, guard=guard, upload_offset=upload_offset,
+                                                            keep_tables=True)
         # the one synchronisation of a clip: the status words
         status = pending.status_d.cpu().numpy().view(np.uint32).reshape(-1, 2)
     return {"frames": frames, "frames_buf": frames_buf, "coef_buf": coef_buf, "plane_buf": plane_buf, "plan": plan,
-            "status": status, "codes": _frame_codes(pending, status)}
+            "status": status, "codes": _frame_codes(pending, status), "tables": pending.tables_d}
 
 
 def decode_jpeg_device(files: Sequence, device="cuda:0", order: str = "bgr", channels: int = 3, names: Optional[Sequence] = None) -> torch.Tensor:

@@ -124,6 +124,7 @@ class Encoded:
     unstuffed: bytes            # the scan before FF 00, final fill included
     zrl: int                    # ZRL symbols in the scan
     last63: int                 # blocks whose coefficient 63 is not zero
+    block_bits: np.ndarray = None   # int64 [blocks]: the bits every block adds to the scan, before the final fill
 
 
 def _planes(frame: np.ndarray, order: str) -> List[np.ndarray]:
@@ -190,13 +191,15 @@ def _codes():
     return [inv(dc[0]), inv(dc[1])], [inv(ac[0]), inv(ac[1])]
 
 
-def entropy(blocks: np.ndarray, comp: np.ndarray, mutant: Optional[str] = None):
-    """(the stuffed and filled scan, the same before stuffing, ZRL count, blocks with a non-zero coefficient 63)."""
+def entropy(blocks: np.ndarray, comp: np.ndarray, mutant: Optional[str] = None, block_bits: Optional[List[int]] = None):
+    """(the stuffed and filled scan, the same before stuffing, ZRL count, blocks with a non-zero coefficient 63).
+    `block_bits`, when given, receives the number of bits of every block."""
     dcs, acs = _codes()
     bits: List[str] = []
     pred = [0, 0, 0]
     zrl = last63 = 0
     for blk, c in zip(blocks.tolist(), comp.tolist()):
+        before = len(bits)
         t = min(c, 1)
         k = 0 if mutant == "dc_prediction_shared" else c
         cat, extra = _magnitude(blk[0] - pred[k])
@@ -219,6 +222,8 @@ def entropy(blocks: np.ndarray, comp: np.ndarray, mutant: Optional[str] = None):
         if run:
             bits.append(acs[t][0x00])
         last63 += blk[63] != 0
+        if block_bits is not None:
+            block_bits.append(sum(map(len, bits[before:])))
     s = "".join(bits)
     s += ("0" if mutant == "final_fill_zero" else "1") * (-len(s) % 8)
     raw = int(s, 2).to_bytes(len(s) // 8, "big") if s else b""
@@ -246,9 +251,10 @@ def encode(frame: np.ndarray, quality: int = 95, subsampling: str = "420", order
     a = np.asarray(frame)
     channels = 1 if a.ndim == 2 else a.shape[2]
     blocks, dummy, comp, tables = quantised_blocks(a, quality, subsampling, order, mutant)
-    scan, raw, zrl, last63 = entropy(blocks, comp, mutant)
+    lengths: List[int] = []
+    scan, raw, zrl, last63 = entropy(blocks, comp, mutant, lengths)
     data = header(a.shape[1], a.shape[0], channels, subsampling, tables) + scan + b"\xff\xd9"
-    return Encoded(data, scan, blocks.astype(np.int16), dummy, tables, raw, zrl, last63)
+    return Encoded(data, scan, blocks.astype(np.int16), dummy, tables, raw, zrl, last63, np.asarray(lengths, np.int64))
 
 
 # ----------------------------------------------------------------------------- the corpus

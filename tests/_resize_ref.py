@@ -141,6 +141,21 @@ FRACTIONAL = {"7x10->3x4": (7, 10, 3, 4), "5x7->5x3": (5, 7, 5, 3), "12x10->4x4"
 # where the kernel takes another path: one destination column's share of a source row fills the LDS chunk on its own (one
 # row per chunk at C = 1) or does not fit it at all (C = 3, 4: the source is read in place), box rule and float rule; n = 1
 STEEP = {"2x45000->1x1": (2, 45000, 1, 1), "2x90001->1x2": (2, 90001, 1, 2)}
+# ... and where even one channel's share of a source row exceeds the LDS: the in-place kernels at C = 1 (run at C = 1 only)
+STEEP_C1 = {"2x65600->1x1": (2, 65600, 1, 1), "2x131203->1x2": (2, 131203, 1, 2)}
+
+# What elvis_last_launch reports after the two entry points, stated once: by (both ratios whole, the source is read in
+# place: row_stride 0 of the plan).  csrc/resize.hip notes these very strings.
+AREA_KERNELS = {(True, False): "resize_area_kernel<whole,lds>", (True, True): "resize_area_kernel<whole,direct>",
+                (False, False): "resize_area_kernel<frac,lds>", (False, True): "resize_area_kernel<frac,direct>"}
+NEAREST_KERNEL = "resize_nearest_kernel"
+
+
+def area_kernel(hs: int, ws: int, hd: int, wd: int, c: int) -> str:
+    """The instantiation `intake.resize_area_device` launches for this resize: the dispatch of elvis_resize_area_u8 on the
+    plan's row_stride and the two ratios."""
+    from elvis_amd.intake import _plan
+    return AREA_KERNELS[(hs % hd == 0 and ws % wd == 0, _plan(hs, ws, hd, wd, c)[3] == 0)]
 
 
 def tiling_cases(c: int) -> Dict[str, Tuple[int, int, int, int]]:
@@ -164,7 +179,7 @@ def tiling_cases(c: int) -> Dict[str, Tuple[int, int, int, int]]:
 
 
 def cases(c: int) -> Dict[str, Tuple[int, int, int, int]]:
-    return {**WHOLE, **FRACTIONAL, **STEEP, **tiling_cases(c)}
+    return {**WHOLE, **FRACTIONAL, **STEEP, **(STEEP_C1 if c == 1 else {}), **tiling_cases(c)}
 
 
 def frames(hs: int, ws: int, c: int, n: int, seed: int = 0) -> np.ndarray:

@@ -1,10 +1,16 @@
 """elvis_gn_partials_affine (csrc/gn_fused.hip) against the two launches it replaces, elvis_gn_partials_to_sums followed
-by elvis_groupnorm_affine: the bits of pa and pb are equal.  The partials have a large mean and mixed signs, so an fp64
-sum taken in another order differs in its last bits, and the tile counts sit on both sides of the 256 virtual lanes."""
+by elvis_groupnorm_affine: the bits of pa and pb are equal.  The tile counts sit on both sides of the 256 virtual lanes.
+
+The first matrix keeps its inputs: a large mean and mixed signs.  Such fp32 values add exactly in float64 in any order
+(tests/test_gn_fused_host.py shows it), so that matrix pins the arithmetic and the addressing, not the order of the sums.
+The second matrix has an oracle of its own, the bit-exact numpy model tests/_gn_fused_model.py, inputs on which every
+reordering of a sum moves pa and pb (the model's mutants), the spans, short last workgroups and tile counts the first one
+never ran, and a variance that rounds below zero."""
 import numpy as np
 import pytest
 import torch
 
+import _gn_fused_model as M
 from test_gpu_model_kernels_matrix import SENTINEL, _last_launch
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +44,7 @@ def _guarded(numel, dev):
     return t.to(dev)
 
 
-def _both(p, n, tiles, c, gam, bet, sc, sh, dev):
+def _both(p, n, tiles, c, gam, bet, sc, sh, dev, groups=GROUPS):
     from elvis_amd._lib import lib, check, ptr, stream_handle
     d = lambda t: None if t is None else t.to(dev)
     pd, keep = p.to(dev), [d(gam), d(bet), d(sc), d(sh)]
@@ -47,8 +53,8 @@ def _both(p, n, tiles, c, gam, bet, sc, sh, dev):
     sums = torch.full((n, c, 2), float("nan"), dtype=torch.float64, device=dev)
     pa0, pb0, pa1, pb1 = (_guarded(n * c, dev) for _ in range(4))
     check(lib().elvis_gn_partials_to_sums(ptr(pd), tiles, n, c, ptr(sums), c, 0, s), dev)
-    check(lib().elvis_groupnorm_affine(ptr(sums), *(ptr(t) for t in keep), ptr(pa0), ptr(pb0), n, hw, c, GROUPS, EPS, s), dev)
-    check(lib().elvis_gn_partials_affine(ptr(pd), tiles, *(ptr(t) for t in keep), ptr(pa1), ptr(pb1), n, hw, c, GROUPS, EPS, s), dev)
+    check(lib().elvis_groupnorm_affine(ptr(sums), *(ptr(t) for t in keep), ptr(pa0), ptr(pb0), n, hw, c, groups, EPS, s), dev)
+    check(lib().elvis_gn_partials_affine(ptr(pd), tiles, *(ptr(t) for t in keep), ptr(pa1), ptr(pb1), n, hw, c, groups, EPS, s), dev)
     name = _last_launch()
     torch.cuda.synchronize()
     out = [t.cpu().numpy() for t in (pa0, pb0, pa1, pb1)]
@@ -70,6 +76,51 @@ def test_one_launch_equals_the_two_it_replaces(gpu_device, tiles, c, n, affine):
     assert np.array_equal(pa0, pa1), f"pa: {int((pa0 != pa1).sum())} of {pa0.size} differ"
     assert np.array_equal(pb0, pb1), f"pb: {int((pb0 != pb1).sum())} of {pb0.size} differ"
     assert len(set(pa0.tolist())) > c // 2                     # the inputs were not degenerate
+
+
+def _first_difference(name, got, want):
+    bad = np.nonzero(got != want)[0]
+    return f"{name}: {bad.size} of {got.size} differ, first at (image, channel) {divmod(int(bad[0]), got.size // M.N_IMAGES)}: " \
+           f"{got[bad[0]]:#x} against {want[bad[0]]:#x}" if bad.size else ""
+
+
+def _model_and_both(p, c, groups, tiles, affine, dev):
+    """(kernel name, pa, pb of the two launches, of the one launch, of the model) as int32 words, for partials [n, tiles, c, 2]."""
+    n = p.shape[0]
+    gam, bet, sc, sh = M.params(c, affine)
+    t = lambda a: None if a is None else torch.from_numpy(a)
+    name, (pa0, pb0, pa1, pb1) = _both(torch.from_numpy(np.array(p)).reshape(n * tiles, c, 2), n, tiles, c, t(gam), t(bet), t(sc), t(sh),
+                                       dev, groups)
+    ma, mb = M.model(p, gam, bet, sc, sh, tiles * 256, groups, EPS)
+    return name, (pa0, pb0), (pa1, pb1), (ma.reshape(-1).view(np.int32), mb.reshape(-1).view(np.int32))
+
+
+@pytest.mark.parametrize("c,groups,tiles", M.gpu_cases(), ids=lambda v: str(v))
+def test_new_spans_equal_the_model_and_the_two_launches(gpu_device, c, groups, tiles):
+    from elvis_amd._lib import lib
+    assert EPS == M.EPS and lib().elvis_gn_partials_affine_span(c, groups) == M.SHAPES[(c, groups)] == M.span_of(c, groups)
+    p = M.partials(M.N_IMAGES, tiles, c, c // groups)
+    name, two, one, model = _model_and_both(p, c, groups, tiles, (c + tiles) % 2 == 0, gpu_device)
+    assert name == f"gn_partials_affine_kernel<{M.row_lanes(c, groups)}>"
+    for what, got, want in (("pa", one[0], model[0]), ("pb", one[1], model[1])):
+        assert np.array_equal(got, want), _first_difference(f"{what} against the model", got, want)
+    for what, got, want in (("pa", one[0], two[0]), ("pb", one[1], two[1])):
+        assert np.array_equal(got, want), _first_difference(f"{what} against the two launches", got, want)
+
+
+@pytest.mark.parametrize("c,groups,tiles", M.CLAMP_CASES)
+def test_a_variance_that_rounds_below_zero_is_clamped_the_same_way(gpu_device, c, groups, tiles):
+    """Every tile of a channel holds (256 v, 256 fl32(v^2)) with fl32(v^2) < v^2: the variance is negative before the clamp
+    (the host test asserts it on the model).  Both device paths and the model agree bit for bit."""
+    p = M.clamp_partials(M.N_IMAGES, tiles, c, groups)
+    info = {}
+    gam, bet, sc, sh = M.params(c, True)
+    M.model(p, gam, bet, sc, sh, tiles * 256, groups, EPS, info=info)
+    assert (info["var"] < 0).all()
+    name, two, one, model = _model_and_both(p, c, groups, tiles, True, gpu_device)
+    for k, what in enumerate(("pa", "pb")):
+        assert np.array_equal(one[k], model[k]), _first_difference(f"{what} against the model", one[k], model[k])
+        assert np.array_equal(one[k], two[k]), _first_difference(f"{what} against the two launches", one[k], two[k])
 
 
 def test_null_gamma_and_shift_without_scale(gpu_device):

@@ -29,6 +29,7 @@ def _check_clip(cases, got, order="rgb", channels=3, pil=True):
     host = got["frames"].cpu().numpy()
     plan = got["plan"]
     coef = got["coef_buf"].cpu().numpy()[GUARD:-GUARD].view(np.int16).reshape(len(cases), plan.stride_blocks, 64)
+    planes = got["plane_buf"].cpu().numpy()[GUARD:-GUARD].reshape(len(cases), plan.stride_blocks * 64)
     for i, fc in enumerate(cases):
         want = R.decoded(fc.name, order, channels)
         mine = got["status"][plan.seg_frame == i]
@@ -38,11 +39,46 @@ def _check_clip(cases, got, order="rgb", channels=3, pil=True):
         assert np.array_equal(coef[i, :blocks], want.coef), fc.name
         assert not coef[i, blocks:].any(), fc.name
         if want.status == R.OK:
+            # jpeg_idct_kernel's own output, the component planes, where the frame descriptor puts them
+            for c, ref in enumerate(R.planes_from_blocks(R.idct_blocks(want.coef), want.geometry)):
+                off, pitch = (int(v) for v in plan.fd[i, 8 + 8 * c + 3:8 + 8 * c + 5])
+                assert pitch == ref.shape[1], fc.name
+                assert np.array_equal(planes[i, off:off + ref.size].reshape(ref.shape), ref), f"{fc.name}: plane {c}"
             assert np.array_equal(host[i], want.pixels), fc.name
             if pil and R.have_turbo() and fc.name not in NOT_FOR_PIL:
                 assert np.array_equal(host[i], R.decode_with_pil(fc.data, order, channels)), fc.name
     for key in ("frames_buf", "coef_buf", "plane_buf"):
         assert _guards_intact(got[key]), key
+
+
+def _derived_table(spec: np.ndarray) -> bytes:
+    """jpeg_decode.h's jpeg_build_table on one (16 counts, 256 values) specification: the 512-entry lookup by the next 9
+    bits ((symbol << 4) | length, 0 = none), the counts as the canonical walk uses them, the values."""
+    fast, count = np.zeros(512, np.uint16), np.zeros(16, np.uint16)
+    code = k = 0
+    for length in range(1, 17):
+        n = max(0, min(int(spec[length - 1]), 256 - k, (1 << length) - code))
+        count[length - 1] = n
+        if length <= 9:
+            for j in range(n):
+                first = (code + j) << (9 - length)
+                fast[first:first + (1 << (9 - length))] = int(spec[16 + ((k + j) & 255)]) << 4 | length
+        code = (code + n) << 1
+        k += n
+    return fast.tobytes() + count.tobytes() + spec[16:272].tobytes()
+
+
+def test_derived_code_tables_equal_their_statement(gpu_device):
+    """jpeg_tables_kernel's only output: eight tables a frame, the undefined ones (all counts zero) included."""
+    seen = set()
+    for (h, w), group in list(_groups(R.files()).items())[:4]:
+        got = jpeg._decode_clip([fc.data for fc in group], gpu_device, "rgb", 3)
+        tables = got["tables"].cpu().numpy().reshape(len(group), 8, jpeg.TABLE_BYTES)
+        for i, fc in enumerate(group):
+            for t in range(8):
+                assert tables[i, t].tobytes() == _derived_table(got["plan"].huff[i, t]), (fc.name, t)
+                seen.add(bool(got["plan"].huff[i, t, :16].any()))
+    assert seen == {False, True}
 
 
 def _groups(cases):

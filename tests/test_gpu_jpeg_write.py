@@ -251,3 +251,42 @@ def test_exported(gpu_device):
     c = W.case("w16-h16-420-q100-checker255")
     clip = torch.from_numpy(c.frame()[None]).to(gpu_device)
     assert elvis_amd.encode_jpeg_device(clip, "rgb", 100, "420") == [W.encoded(c.name).data]
+
+
+def _payload(buf: torch.Tensor, dtype):
+    return buf.cpu().numpy()[GUARD:-GUARD].view(dtype)
+
+
+@pytest.mark.parametrize("fill", [0x00, 0xFF])
+@pytest.mark.parametrize("sampling,c", [("420", 3), ("422", 3), ("444", 3), ("gray", 1)])
+def test_prefix_sums_stream_words_and_sizes_equal_what_the_statement_implies(gpu_device, sampling, c, fill):
+    """The work buffers between the kernels, each against the statement: `bits_buf` holds every block's exclusive bit offset
+    and the total (jpeg_bits_kernel's lengths through jpeg_scan_kernel), `words_buf` the unstuffed stream most significant
+    byte first with zeros up to the dword (jpeg_pack_kernel into what jpeg_clear_kernel cleared - the buffers start from
+    0xFF in half of the runs), `ffc_buf` the exclusive FF counts of the 1024-byte chunks and their total (jpeg_ff_kernel
+    through jpeg_scan_kernel), `sizes_buf` the bytes of every finished scan with EOI (jpeg_sizes_kernel)."""
+    kinds = ("noise", "flat", "checker255", "white")
+    frames = np.stack([W.make_frame(k, 37, 53, c, 60 + i) for i, k in enumerate(kinds)])
+    sub = "420" if sampling == "gray" else sampling
+    files, got = _encode(frames, gpu_device, "rgb", 95, sub, fill=fill)
+    n, blocks, chunks = len(kinds), got["blocks"], got["chunks"]
+    bits = _payload(got["bits_buf"], np.uint32).reshape(n, blocks + 1).astype(np.int64)
+    ffc = _payload(got["ffc_buf"], np.uint32).reshape(n, chunks + 1).astype(np.int64)
+    sizes = _payload(got["sizes_buf"], np.uint32).astype(np.int64)
+    words = _payload(got["words_buf"], "<u4").astype(">u4").tobytes()
+    want = [W.encode(f, 95, sub) for f in frames]
+    assert chunks == max(-(-len(e.unstuffed) // STUFF_CHUNK) for e in want) and chunks >= 2
+    assert any(len(e.unstuffed) % 4 for e in want) and any(b"\xff" in e.unstuffed for e in want)
+    at = 0
+    for i, e in enumerate(want):
+        assert e.block_bits.size == blocks and (e.block_bits > 0).all()
+        assert np.array_equal(bits[i], np.concatenate([[0], np.cumsum(e.block_bits)])), f"{kinds[i]}: bit offsets"
+        assert len(e.unstuffed) == (int(bits[i, blocks]) + 7) // 8
+        padded = e.unstuffed + bytes(-len(e.unstuffed) % 4)
+        assert words[at:at + len(padded)] == padded, f"{kinds[i]}: stream words"
+        at += len(padded)
+        ff = [e.unstuffed[k:k + STUFF_CHUNK].count(b"\xff") for k in range(0, chunks * STUFF_CHUNK, STUFF_CHUNK)]
+        assert np.array_equal(ffc[i], np.concatenate([[0], np.cumsum(ff)])), f"{kinds[i]}: FF counts"
+        assert sizes[i] == len(e.unstuffed) + sum(ff) + 2 == len(e.scan) + 2, f"{kinds[i]}: size"
+        assert files[i] == e.data
+    assert at == len(words)

@@ -147,6 +147,36 @@ def test_distance_per_tap(model, gpu_device, tap):
     assert np.array_equal(view.cpu().numpy(), got + got) and guards_intact(full)
 
 
+def test_distance_partials_are_the_distance_kernels_own_output(model, gpu_device):
+    """elvis_lpips_distance_f64 with a workspace of the test's own: lpips_distance_kernel writes one float64 partial sum a
+    workgroup and nothing else, lpips_finish_kernel reads nothing else.  The partials of a frame add up to the float64
+    reference times the pixel count within test_distance_per_tap's bound, and the result is their sum in index order
+    divided by the pixel count, bit for bit."""
+    from elvis_amd._lib import check, lib, ptr, stream_handle
+    tap, (n, h, w) = 1, (2, 5, 27)
+    c = R.TAP_CHANNELS[tap]
+    g = torch.Generator().manual_seed(50)
+    x, y = torch.relu(torch.randn(n, h, w, c, generator=g)), torch.relu(torch.randn(n, h, w, c, generator=g))
+    lin = R.weights()[f"lin{tap}.model.1.weight"].reshape(-1)
+    blocks = lib().elvis_lpips_distance_workspace_bytes(n, h, w) // 8 // n
+    assert blocks == 3 and lib().elvis_lpips_distance_workspace_bytes(n, h, w) == n * blocks * 8
+    wfull, ws = guarded((n * blocks,), gpu_device, torch.float64)
+    ws.fill_(float("nan"))
+    ofull, out = guarded((n,), gpu_device, torch.float64)
+    xd_, yd_ = x.to(gpu_device), y.to(gpu_device)
+    check(lib().elvis_lpips_distance_f64(ptr(xd_), ptr(yd_), ptr(model.lin[tap]), ptr(ws), ptr(out), n, h, w, c, c, 0,
+                                         stream_handle(gpu_device)), gpu_device)
+    partial, got = ws.cpu().numpy().reshape(n, blocks), out.cpu().numpy()
+    xd, yd = x.permute(0, 3, 1, 2).double(), y.permute(0, 3, 1, 2).double()
+    want, tol = R.tap_distance(xd, yd, lin).numpy(), distance_tolerance(xd, yd, lin)
+    assert np.isfinite(partial).all() and (partial > 0).all()
+    assert (np.abs(partial.sum(1) / (h * w) - want) <= tol).all()
+    serial = np.zeros(n)
+    for b in range(blocks):
+        serial = serial + partial[:, b]
+    assert np.array_equal(got, serial / float(h * w)) and guards_intact(wfull) and guards_intact(ofull)
+
+
 # ----------------------------------------------------------------------------- end to end
 def run(case, model, device, **kw):
     a, b, m = R.inputs(case)

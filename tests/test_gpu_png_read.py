@@ -64,6 +64,32 @@ def test_inflate_malformed_streams_give_the_statements_status(gpu_device):
         png.inflate_device([good[0].stream, bad.stream], [good[0].cap, bad.cap], gpu_device)
 
 
+def test_gather_concatenates_the_idat_payloads(gpu_device):
+    """png_gather_kernel's only output, the zlib streams, through elvis_png_gather itself: every IDAT chunk's data land
+    where the chunk table says, in file order; files of one and of many IDAT chunks, uploaded 0..3 bytes past a dword."""
+    from elvis_amd._lib import check, lib, ptr, stream_handle
+    cases = [fc for fc in R.files() if (fc.h, fc.w) in ((17, 63), (33, 65))]
+    infos = [png.parse_png(fc.data, fc.name) for fc in cases]
+    assert {sum(1 for c in i.chunks if c[2]) for i in infos} >= {1, 2} and max(sum(1 for c in i.chunks if c[2]) for i in infos) >= 3
+    file_off = np.concatenate([[0], np.cumsum([len(fc.data) for fc in cases])])
+    rows, want = [], b""
+    for f, (fc, info) in enumerate(zip(cases, infos)):
+        for off, length, idat in info.chunks:
+            rows.append((int(file_off[f]) + off, length, len(want) if idat else -1))
+            if idat:
+                want += fc.data[off + 4:off + 4 + length]
+    for upload_offset in range(4):
+        host = np.concatenate([np.zeros(upload_offset, np.uint8)] + [np.frombuffer(fc.data, np.uint8) for fc in cases])
+        files_d = torch.from_numpy(host).to(gpu_device)[upload_offset:]
+        chunks_d = torch.from_numpy(np.asarray(rows, np.int64).reshape(-1)).to(gpu_device)
+        buf = torch.full((len(want) + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=gpu_device)
+        status_d = torch.full((len(rows),), 7, dtype=torch.int32, device=gpu_device)
+        check(lib().elvis_png_gather(ptr(files_d), int(file_off[-1]), ptr(chunks_d), len(rows), ptr(buf) + GUARD, len(want), ptr(status_d),
+                                     stream_handle(gpu_device)), gpu_device)
+        assert buf.cpu().numpy()[GUARD:GUARD + len(want)].tobytes() == want, upload_offset
+        assert _guards_intact(buf, len(want)) and not status_d.cpu().numpy().any()              # and every chunk's CRC holds
+
+
 def _groups(only_gray=False):
     """The files of the corpus by size: one call decodes files of one size, of any colour type."""
     groups = {}

@@ -27,14 +27,20 @@ def _dev(a, device):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device)
 
 
+def _launched():
+    from elvis_amd import _lib
+    return _lib.lib().elvis_last_launch().decode()
+
+
 def _check_device_form(fn, ref_fn, frames, maps, b, device):
     """With and without `out=`; the rows and columns past the last whole block: returned as the input's without `out`,
-    left as the caller put them with it."""
+    left as the caller put them with it.  The launch note names the form's one kernel."""
     n, h, w, _ = frames.shape
     by, bx = maps.shape[1:]
     ref = ref_fn(frames, maps, b)
     fd, md = _dev(frames, device), _dev(maps, device)
     got = fn(fd, md, b)
+    assert _launched() == {"degrade_scale_device": "degrade_scale_kernel", "degrade_gaussian_fx_device": "degrade_gaussian_fx_kernel"}[fn.__name__]
     assert got.data_ptr() != fd.data_ptr() and np.array_equal(fd.cpu().numpy(), frames)
     assert np.array_equal(got.cpu().numpy(), ref)
     assert np.array_equal(ref[:, by * b:], frames[:, by * b:]) and np.array_equal(ref[:, :, bx * b:], frames[:, :, bx * b:])
@@ -81,6 +87,25 @@ def test_degrade_gaussian_fx_device(gpu_device, b, c):
     maps[1, 1, 1] = 65
     with pytest.raises(ValueError, match="rounds"):
         D.degrade_gaussian_fx_device(_dev(frames, gpu_device), _dev(maps, gpu_device), b)
+
+
+@pytest.mark.parametrize("b", [2, 12, 32])
+def test_two_channels_through_both_kernels(gpu_device, b):
+    """c = 2 is inside check_block_maps' 1..4 and has a branch of its own in pixel_of (xc >> 1): every scale of a block
+    size, whole ratios and fractional ones, and 0, 1, 2 and 10 blur rounds, on a ragged frame."""
+    from elvis_amd import degrade as D
+    values = np.arange(-1, b + 2, dtype=np.int32)
+    bx = (len(values) + 1) // 2
+    grid = np.full(2 * bx, 3, np.int32)
+    grid[:len(values)] = values
+    maps = np.stack([grid.reshape(2, bx), grid[::-1].reshape(2, bx)])
+    frames = _frames(800 * b + 2, 2, 2 * b + _ragged(3, b), bx * b + _ragged(5, b), 2)
+    ref = _check_device_form(D.degrade_scale_device, R.scale_clip, frames, maps, b, gpu_device)
+    assert not np.array_equal(ref, frames)
+    maps = np.array([[[-1, 0, 1], [2, 10, 64]], [[64, 10, 2], [1, 0, -1]]], np.int32)
+    frames = _frames(900 * b + 2, 2, 2 * b + _ragged(3, b), 3 * b + _ragged(5, b), 2)
+    ref = _check_device_form(D.degrade_gaussian_fx_device, R.blur_clip, frames, maps, b, gpu_device)
+    assert not np.array_equal(ref[0, :b, 2 * b:3 * b], frames[0, :b, 2 * b:3 * b])
 
 
 @pytest.mark.parametrize("b", [2, 4, 8, 16])

@@ -1,6 +1,7 @@
 """The clip intake on the GPU (elvis_amd/intake.py, csrc/resize.hip): bit-exact against the numpy statement in
 tests/_resize_ref.py on its cases - whole ratios, fractional ones, tiles with remainders, a source row too wide for the
-LDS -, `out=` inside guard bytes, the nearest resize, the error conventions, and the file-to-clip intake."""
+LDS -, `out=` inside guard bytes, the nearest resize, the error conventions, and the file-to-clip intake.  After every
+resize the launch note is the instantiation `_resize_ref.area_kernel` derives from the plan and the two ratios."""
 import numpy as np
 import pytest
 import torch
@@ -16,11 +17,16 @@ def _up(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
 
 
+def _launched():
+    from elvis_amd import _lib
+    return _lib.lib().elvis_last_launch().decode()
+
+
 def _params():
     out = []
     for c in R.CHANNELS:
         for name, size in R.cases(c).items():
-            for n in ((1,) if name in R.STEEP else (1, 3)):
+            for n in ((1,) if name in R.STEEP or name in R.STEEP_C1 else (1, 3)):
                 out.append(pytest.param(size, c, n, id=f"{name if name.startswith('tiles') else name + f'_c{c}'}_n{n}"))
     return out
 
@@ -30,7 +36,9 @@ def test_area_resize_is_the_statement_bit_for_bit(size, c, n):
     from elvis_amd import intake
     hs, ws, hd, wd = size
     x = R.frames(hs, ws, c, n)
-    got = intake.resize_area_device(_up(x), hd, wd).cpu().numpy()
+    got = intake.resize_area_device(_up(x), hd, wd)
+    assert _launched() == R.area_kernel(hs, ws, hd, wd, c)
+    got = got.cpu().numpy()
     want = R.resize_area_u8(x, hd, wd)
     assert got.shape == want.shape and got.dtype == np.uint8
     assert np.array_equal(got, want), f"{int((got != want).sum())} of {want.size} bytes differ, first at {np.argwhere(got != want)[:3].tolist()}"
@@ -48,6 +56,7 @@ def test_out_buffer_inside_guards_whatever_it_held(name):
         big = torch.full((guard + want.size + guard,), fill, dtype=torch.uint8, device=DEV)
         out = big[guard:guard + want.size].view(n, hd, wd, c)
         assert intake.resize_area_device(_up(x), hd, wd, out=out) is out
+        assert _launched() == R.area_kernel(hs, ws, hd, wd, c)
         host = big.cpu().numpy()
         assert (host[:guard] == fill).all() and (host[-guard:] == fill).all(), "guard bytes were written"
         results.append(host[guard:-guard].reshape(want.shape))
@@ -66,6 +75,7 @@ def test_a_source_that_starts_off_a_dword_gives_the_same_bytes():
         view = big[off:].view(x.shape)
         view.copy_(_up(x))
         assert np.array_equal(intake.resize_area_device(view, hd, wd).cpu().numpy(), want), off
+        assert _launched() == R.area_kernel(hs, ws, hd, wd, 3)
 
 
 @pytest.mark.parametrize("src,dst", [((4, 6), (16, 24)), ((4, 6), (9, 13)), ((16, 24), (4, 6)), ((16, 24), (5, 7)), ((1, 1), (3, 5))])
@@ -75,7 +85,9 @@ def test_nearest_resize_is_the_statement_and_the_hosts(src, dst):
     rng = np.random.default_rng(7)
     for shape in ((3,) + src, (2,) + src + (3,), (1,) + src + (1,), (2,) + src + (4,)):
         x = rng.integers(0, 256, shape, dtype=np.uint8)
-        got = intake.resize_nearest_device(_up(x), *dst).cpu().numpy()
+        got = intake.resize_nearest_device(_up(x), *dst)
+        assert _launched() == R.NEAREST_KERNEL
+        got = got.cpu().numpy()
         assert np.array_equal(got, R.resize_nearest_u8(x, *dst)), shape
     masks = [rng.integers(0, 2, src, dtype=np.uint8), None, rng.integers(0, 2, src, dtype=np.uint8),
              rng.integers(0, 2, (src[0] + 1, src[1]), dtype=np.uint8)]

@@ -93,6 +93,21 @@ def test_device_equals_the_statement_byte_for_byte(gpu_device, name):
     assert isinstance(plain, torch.Tensor) and torch.equal(plain, masks)
 
 
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_strip_means_and_votes_equal_the_statement(gpu_device, name):
+    """The two work buffers STAGES leaves out: `means`, the border strips' mean colours (seg_strips_kernel's only output),
+    and `voted`, the masks after the temporal vote with `count`, their set pixels (seg_vote_kernel's)."""
+    frames, order, kw = CASES[name]
+    cfg = R.SegmentConfig(**kw)
+    _, ref = expected(name)
+    _, det = elvis_amd.foreground_masks_device(_dev(frames, gpu_device), order, segment.SegmentConfig(**kw), details=True)
+    m = frames.shape[0]
+    _same(f"{name} means", det["means"], np.stack([R.strip_means(ref["red"][e]) for e in range(m)]))
+    voted = np.stack([R.vote(ref["pre"], e, m) if cfg.temporal_vote else ref["pre"][e] for e in range(m)])
+    _same(f"{name} voted", det["voted"], voted)
+    _same(f"{name} count", det["count"], voted.reshape(m, -1).sum(axis=1))
+
+
 def _scene(n):
     pan, move, noise = R.SCENES["pan_4_8_obj_0_8"]
     frames, boxes = R.scene(pan, move, noise)

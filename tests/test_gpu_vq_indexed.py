@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _normref as R
+import _vq_grid_ref as V
 from test_gpu_model_kernels_matrix import SENTINEL, _last_launch, _out_buffer, _pitched
 
 pytestmark = pytest.mark.gpu
@@ -37,14 +38,14 @@ def _edges(index):
     return g, words[4:4 + 3 * 17].view(np.float32).reshape(3, 17)[:, :g + 1].copy()
 
 
-def _check(cb, z, dt, dev, what, index=None, cbd=None):
-    """Both entries on the same buffers: the indexed one equals vq_ref and equals the scan."""
+def _check(cb, z, dt, dev, what, index=None, cbd=None, pin=16, pout=16, want_idx=True):
+    """Both entries on the same buffers: the indexed one equals vq_ref and equals the scan.  `want_idx=False` gives the
+    indexed entry a null index buffer, what ops.vq_nearest(want_idx=False) passes; its codes are then read off zq."""
     from elvis_amd._lib import lib, check, ptr, stream_handle
     dtype, code = _dt(dt)
     pixels, n_embed = z.shape[0], cb.shape[0]
     cbd = cb.contiguous().to(dev) if cbd is None else cbd
     index = _index(cbd) if index is None else index
-    pin, pout = 16, 16
     zd = _pitched(z, pin, dtype, dev)                          # NaN in the input's pad channels: never read
     ridx, rzq = R.vq_ref(z.to(dtype).float().numpy(), cb.numpy())
     got = {}
@@ -52,8 +53,8 @@ def _check(cb, z, dt, dev, what, index=None, cbd=None):
         out = _out_buffer(pixels, 3, pout, dtype, dev)
         idx = torch.full((pixels + 8,), -7, dtype=torch.int32, device=dev)
         if name == "indexed":
-            check(lib().elvis_vq_nearest_indexed(ptr(zd), ptr(out), ptr(idx), code, pixels, 3, pin, pout, ptr(cbd), n_embed,
-                                                 ptr(index), stream_handle(dev)), dev)
+            check(lib().elvis_vq_nearest_indexed(ptr(zd), ptr(out), ptr(idx) if want_idx else 0, code, pixels, 3, pin, pout, ptr(cbd),
+                                                 n_embed, ptr(index), stream_handle(dev)), dev)
             assert _last_launch() == f"vq_grid_nearest_kernel<{'half' if dt == 'f16' else 'float'}>"
         else:
             check(lib().elvis_vq_nearest(ptr(zd), ptr(out), ptr(idx), code, pixels, 3, pin, pout, ptr(cbd), n_embed,
@@ -63,6 +64,9 @@ def _check(cb, z, dt, dev, what, index=None, cbd=None):
         assert bool((o[:pixels, 3:] == 0).all()), f"{what} / {name}: pad channels not zeroed"
         assert bool((o[pixels] == SENTINEL).all()) and (i[pixels:] == -7).all(), f"{what} / {name}: written past the end"
         got[name] = (i[:pixels], o[:pixels, :3].numpy())
+    if not want_idx:
+        assert (got["indexed"][0] == -7).all(), f"{what}: an index was written without an index buffer"
+        got["indexed"] = (got["scan"][0], got["indexed"][1])               # zq below is compared on its own
     for name, (i, o) in got.items():
         bad = np.nonzero(i != ridx)[0]
         assert bad.size == 0, f"{what} / {name}: pixel {bad[0]} ({z[bad[0]].tolist()}) index {i[bad[0]]}, reference {ridx[bad[0]]}"
@@ -188,6 +192,48 @@ def test_signed_zeros_and_denormals(gpu_device, dt):
     ridx = _check(cb, z, dt, gpu_device, "zeros and denormals")
     assert 3 in ridx                                               # (+-0, +-0, +-0) ties codes 3 and 9 at distance 0: 3 wins
     assert 9 not in ridx
+
+
+@pytest.mark.parametrize("dt", ["f16", "f32"])
+@pytest.mark.parametrize("case_id", [c.id for c in V.CASES])
+def test_the_cases_of_the_host_model(gpu_device, case_id, dt):
+    """tests/_vq_grid_ref.py: grids of one and two cells, the grid capped at 16, codebooks constant on one, two and three
+    axes with pixels below, on and above the value, pixel counts around a workgroup, the mutants' cases - among them ties
+    whose winner is visited after its rival (tests/test_vq_grid_host.py shows what each case contains)."""
+    cb, z = V.BY_ID[case_id].arrays()
+    assert cb.shape[0] <= V.MAX_CODES and z.shape[0] <= V.MAX_PIXELS
+    ridx = _check(torch.from_numpy(cb.copy()), torch.from_numpy(z.copy()), dt, gpu_device, case_id)
+    if case_id == "mirrored_winner_seen_later":
+        assert (ridx % 2 == 0).all()
+
+
+@pytest.mark.parametrize("dt", ["f16", "f32"])
+@pytest.mark.parametrize("pin,pout", [(3, 3), (3, 16), (16, 3)])
+def test_tight_pitches(gpu_device, pin, pout, dt):
+    """Pitch 3 in: nothing pads z[px * 3 + d].  Pitch 3 out: the zero-fill loop runs no iteration, and the guard row behind
+    the last pixel shows that nothing is written past it."""
+    for case_id in ("p255", "p257", "k7_two_cells", "constant_yz"):
+        cb, z = V.BY_ID[case_id].arrays()
+        _check(torch.from_numpy(cb.copy()), torch.from_numpy(z.copy()), dt, gpu_device, f"{case_id} pitch {pin}/{pout}", pin=pin, pout=pout)
+
+
+@pytest.mark.parametrize("dt", ["f16", "f32"])
+@pytest.mark.parametrize("pin,pout", [(16, 16), (3, 3)])
+def test_without_an_index_buffer(gpu_device, pin, pout, dt):
+    for case_id in ("p256", "p257", "random_2000"):
+        cb, z = V.BY_ID[case_id].arrays()
+        _check(torch.from_numpy(cb.copy()), torch.from_numpy(z.copy()), dt, gpu_device, f"{case_id} no idx", pin=pin, pout=pout,
+               want_idx=False)
+    # and through the wrapper that passes the null pointer
+    from elvis_amd import ops
+    cb, z = V.BY_ID["p257"].arrays()
+    dtype, _ = _dt(dt)
+    cbd = torch.from_numpy(cb.copy()).to(gpu_device)
+    zt = torch.from_numpy(z.copy()).reshape(1, 1, 257, 3)
+    out = ops.vq_nearest(ops.Act(_pitched(zt, 8, dtype, gpu_device), 3), cbd, want_idx=False, index=_index(cbd))
+    assert _last_launch() == f"vq_grid_nearest_kernel<{'half' if dt == 'f16' else 'float'}>"
+    ridx, rzq = R.vq_ref(z, cb)
+    assert R.bits_equal(out.t.cpu().numpy().reshape(-1, out.pitch)[:, :3], R.np_store(rzq, dt == "f16"))
 
 
 def test_four_channels_fall_back_to_the_scan(gpu_device):

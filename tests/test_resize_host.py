@@ -40,7 +40,7 @@ def test_at_whole_ratios_the_statement_is_the_glue_oracle(factor):
 
 
 def _all_sizes():
-    return sorted({size for c in R.CHANNELS for size in R.cases(c).values() if size not in R.STEEP.values()})
+    return sorted({size for c in R.CHANNELS for size in R.cases(c).values() if size not in R.STEEP.values() and size not in R.STEEP_C1.values()})
 
 
 @pytest.mark.parametrize("value", [0, 1, 127, 128, 254, 255])
@@ -101,6 +101,28 @@ def test_the_plan_stays_within_the_lds(ratio, c):
 def test_a_row_no_lds_holds_is_read_in_place():
     assert intake.resize_area_plan(2, 90001, 1, 2, 4) == (1, 1, 0)
     assert intake.resize_area_plan(2, 90001, 1, 2, 1)[2] > 0
+
+
+def test_every_area_instantiation_is_reached_by_a_gpu_case_at_every_channel_count():
+    """elvis_resize_area_u8 dispatches on (both ratios whole, row_stride == 0).  The GPU cases reach all four kernels at
+    C = 1, where only a destination column that reads more than 64 KiB of one source row goes in place (STEEP_C1), and
+    at C = 3 and C = 4, where the STEEP cases do: no instantiation is out of `_plan`'s reach at any channel count.  The
+    steep cases stay at two source rows (and, in tests/test_gpu_resize.py, at n = 1)."""
+    assert set(R.AREA_KERNELS.values()) == {f"resize_area_kernel<{a},{b}>" for a in ("whole", "frac") for b in ("lds", "direct")}
+    src = open(os.path.join(ROOT, "elvis_amd", "csrc", "resize.hip")).read()
+    assert all(f'"{k}"' in src for k in R.AREA_KERNELS.values()) and f'elvis_note_launch("{R.NEAREST_KERNEL}")' in src
+    assert "const bool direct = row_stride == 0;" in src and "const bool whole = hs % hd == 0 && ws % wd == 0;" in src
+    for c in R.CHANNELS:
+        reached = {}
+        for name, size in R.cases(c).items():
+            reached.setdefault(R.area_kernel(*size, c), []).append(name)
+        assert set(reached) == set(R.AREA_KERNELS.values()), (c, sorted(reached))
+        steep = set(R.STEEP) | (set(R.STEEP_C1) if c == 1 else set())
+        assert set(reached["resize_area_kernel<whole,direct>"] + reached["resize_area_kernel<frac,direct>"]) <= steep
+    assert all(size[0] == 2 for size in list(R.STEEP.values()) + list(R.STEEP_C1.values()))
+    assert not set(R.STEEP_C1) & set(R.cases(3)) and set(R.STEEP_C1) <= set(R.cases(1))
+    # at C = 1 the STEEP cases themselves still fit the LDS: that is why STEEP_C1 exists
+    assert {R.area_kernel(*size, 1) for size in R.STEEP.values()} == {"resize_area_kernel<whole,lds>", "resize_area_kernel<frac,lds>"}
 
 
 def test_the_header_declares_both_entry_points_and_the_source_is_built():
