@@ -7,7 +7,8 @@
 // undefined-behaviour sanitizers.  tests/_jpeg_write_ref.py states what it computes.
 //
 // Rules kept here: every pixel read goes through a clamp to the frame; every table index goes through a mask; every
-// stream word written is checked against the frame's own word count; a block's code is at most 1658 bits.
+// stream word written is checked against the word count of its own segment (a frame, or one restart interval of it); a
+// block's code is at most 1658 bits.
 #pragma once
 #include <stdint.h>
 
@@ -43,6 +44,11 @@ struct JpegEncGeom {
     int wib, hib;          // luma blocks that count: ceil(w / 8), ceil(h / 8)
     int bpm;               // blocks per MCU
     int blocks;            // blocks of a frame: mcux * mcuy * bpm
+    // Restart intervals (T.81 B.2.4.4, E.1.4; libjpeg's restart_interval).  An interval is a segment of the scan that
+    // starts on a byte boundary with every DC predictor at 0 and ends in a 1-fill: without an interval the frame is one.
+    int restart_mcus;      // MCUs of an interval, 0: none
+    int segs;              // intervals of a frame: ceil(mcux * mcuy / restart_mcus), 1 without an interval
+    int segb;              // blocks of every interval but a frame's last, which may hold fewer: restart_mcus * bpm
 };
 
 JPGE_HD JpegEncGeom jpeg_enc_geometry(int h, int w, int channels, int bgr, int sampling) {
@@ -59,8 +65,35 @@ JPGE_HD JpegEncGeom jpeg_enc_geometry(int h, int w, int channels, int bgr, int s
     g.hib = (h + 7) / 8;
     g.bpm = channels == 3 ? g.hmax * g.vmax + 2 : 1;
     g.blocks = g.mcux * g.mcuy * g.bpm;
+    g.restart_mcus = 0;
+    g.segs = 1;
+    g.segb = g.blocks;
     return g;
 }
+
+// The geometry with a restart interval of `restart_mcus` MCUs (0 .. 65535, 0: none).  An interval that holds the whole
+// scan leaves one segment: the file gets its DRI segment and no marker.
+JPGE_HD JpegEncGeom jpeg_enc_restart(JpegEncGeom g, int restart_mcus) {
+    const int mcus = g.mcux * g.mcuy;
+    g.restart_mcus = restart_mcus > 0 ? restart_mcus : 0;
+    if (g.restart_mcus > 0 && g.restart_mcus < mcus) {
+        g.segs = (mcus + g.restart_mcus - 1) / g.restart_mcus;
+        g.segb = g.restart_mcus * g.bpm;
+    } else {
+        g.segs = 1;
+        g.segb = g.blocks;
+    }
+    return g;
+}
+
+// Blocks of interval s of a frame, 0 <= s < g.segs.
+JPGE_HD int jpeg_enc_seg_blocks(const JpegEncGeom& g, int s) {
+    const int left = g.blocks - s * g.segb;
+    return left < g.segb ? left : g.segb;
+}
+
+// The second byte of what ends interval s: RSTm, m = s mod 8, in front of the next interval, EOI behind a frame's last.
+JPGE_HD int jpeg_enc_seg_marker(const JpegEncGeom& g, int s) { return s == g.segs - 1 ? 0xd9 : 0xd0 + (s & 7); }
 
 // Where block b of a frame lies: component, block row and column in the component's grid.  A dummy block - one that only
 // completes an MCU, past the luma blocks that count - is placed at the block whose DC it repeats: the one before it in
@@ -97,15 +130,17 @@ JPGE_HD JpegEncPlace jpeg_enc_place(const JpegEncGeom& g, int b) {
     }
 }
 
-// The block before b among its component's blocks in scan order, whose DC is b's prediction; -1 for a component's first.
+// The block before b among its component's blocks in scan order, whose DC is b's prediction; -1 for a component's first
+// of the frame and of every restart interval (a dummy block still repeats the block before it in its own MCU).
 JPGE_HD int jpeg_enc_pred_block(const JpegEncGeom& g, int b) {
-    if (g.channels == 1) return b - 1;
     const int m = b / g.bpm, k = b - m * g.bpm, ny = g.hmax * g.vmax;
+    const bool first = m == 0 || (g.restart_mcus > 0 && m % g.restart_mcus == 0);     // the MCU opens a segment
+    if (g.channels == 1) return first ? -1 : b - 1;
     if (k < ny) {
         if (k > 0) return b - 1;
-        return m > 0 ? (m - 1) * g.bpm + ny - 1 : -1;
+        return first ? -1 : (m - 1) * g.bpm + ny - 1;
     }
-    return m > 0 ? b - g.bpm : -1;
+    return first ? -1 : b - g.bpm;
 }
 
 JPGE_HD int jpeg_enc_table_class(const JpegEncGeom& g, int b) { return g.channels == 3 && b % g.bpm >= g.hmax * g.vmax ? 1 : 0; }

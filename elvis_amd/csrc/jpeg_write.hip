@@ -11,7 +11,7 @@
 //                        lane stores 16 contiguous bytes.  Blocks are in MCU scan order; a dummy block is transformed as
 //                        the block whose DC it repeats and keeps the DC only.  int32 throughout.
 //   jpeg_bits_kernel     a lane per block: the bit length of its code from the DC difference and the AC symbols.
-//   jpeg_scan_kernel     a workgroup per frame: exclusive prefix sum in place, kScanChunk values a step with a carry;
+//   jpeg_scan_kernel     a workgroup per segment: exclusive prefix sum in place, kScanChunk values a step with a carry;
 //                        the total goes behind the last value.  Used for the block bit offsets and the FF counts.
 //   jpeg_clear_kernel    zeroes the stream words the pack kernel ORs into: no result depends on what the buffer held.
 //   jpeg_pack_kernel     a lane per block: the same symbol walk, writing at the block's bit offset.  Words a block covers
@@ -21,7 +21,14 @@
 //   jpeg_sizes_kernel    per frame: stream bytes + FF bytes + 2 (EOI).
 //   jpeg_stuff_kernel    every stream byte to its place in the output, a 00 behind every FF, EOI at the end.
 //
-// No kernel waits on another wave's progress.  Every global write is checked against its frame's own span.
+// Restart intervals (elvis_jpeg_*_rst): a segment is what a frame is without them - a run of blocks that starts on a byte
+// boundary with zeroed DC predictors and ends in a 1-fill - so everything behind the transform works per segment q = f *
+// segs + s instead of per frame: bits is [n * segs, segb + 1] (a frame's last segment is filled up with zero lengths),
+// word_off / ffc / sizes / out_off have a row or an element per segment, and the stuffing pass ends a segment with RSTm,
+// m = s mod 8, or, behind a frame's last, EOI.  Without an interval segs = 1, segb = blocks: the layouts of above.
+// Segments lie on grid.y, and on grid.z once there are more than 65535 of them.
+//
+// No kernel waits on another wave's progress.  Every global write is checked against its segment's own span.
 #include <algorithm>
 #include "common.h"
 #include "jpeg_encode.h"
@@ -74,6 +81,9 @@ __global__ __launch_bounds__(kFdctThreads) void jpeg_fdct_kernel(const uint8_t* 
     if (live) *reinterpret_cast<int4*>(coef + (f * (size_t)g.blocks + (size_t)b) * 64 + lane * 8) = *reinterpret_cast<const int4*>(&zz[blk][lane * 8]);
 }
 
+// The segment a workgroup works on: grid.y, continued on grid.z.  The same for every lane of a workgroup.
+__device__ __forceinline__ size_t segment_index() { return (size_t)blockIdx.z * gridDim.y + blockIdx.y; }
+
 // The tables of both classes into LDS; every lane of the workgroup calls it.
 __device__ __forceinline__ void stage_tables(uint32_t* tab, const uint32_t* __restrict__ ehuff) {
     for (int i = threadIdx.x; i < 2 * JPGE_HUFF_WORDS; i += kBlockThreads) tab[i] = ehuff[i];
@@ -95,14 +105,21 @@ __device__ __forceinline__ void load_block(const int16_t* __restrict__ src, int1
     }
 }
 
-// coef -> bits u32 [n, blocks + 1]: element b of a frame is block b's bit length (the scan makes offsets of them).
+// coef -> bits u32 [nseg, segb + 1]: element i of a segment is the bit length of its block i (the scan makes offsets of
+// them), 0 past the blocks of a frame's last segment.  grid (segb / 256, segments).
 __global__ __launch_bounds__(kBlockThreads) void jpeg_bits_kernel(const int16_t* __restrict__ coef, JpegEncGeom g,
-                                                                  const uint32_t* __restrict__ ehuff, uint32_t* __restrict__ bits) {
+                                                                  const uint32_t* __restrict__ ehuff, uint32_t* __restrict__ bits, int nseg) {
     __shared__ uint32_t tab[2 * JPGE_HUFF_WORDS];
     stage_tables(tab, ehuff);
-    const size_t f = blockIdx.y;
-    const int b = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (b >= g.blocks) return;
+    const size_t q = segment_index();
+    const int i = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (q >= (size_t)nseg || i >= g.segb) return;
+    const size_t f = q / (size_t)g.segs;
+    const int b = (int)(q - f * (size_t)g.segs) * g.segb + i;
+    if (b >= g.blocks) {
+        bits[q * ((size_t)g.segb + 1) + i] = 0u;
+        return;
+    }
     const int16_t* base = coef + f * (size_t)g.blocks * 64;
     int16_t zz[64];
     load_block(base + (size_t)b * 64, zz);
@@ -110,7 +127,7 @@ __global__ __launch_bounds__(kBlockThreads) void jpeg_bits_kernel(const int16_t*
     const int pred = pb >= 0 ? base[(size_t)pb * 64] : 0;
     JpegBitCounter count;
     jpeg_encode_block(zz, pred, tab + JPGE_HUFF_WORDS * jpeg_enc_table_class(g, b), count);
-    bits[f * ((size_t)g.blocks + 1) + b] = count.bits;
+    bits[q * ((size_t)g.segb + 1) + i] = count.bits;
 }
 
 // Inclusive scan over the workgroup's kScanChunk lanes; `total` is the sum.  lds: 4 words.
@@ -135,8 +152,8 @@ __device__ __forceinline__ uint32_t workgroup_scan(uint32_t v, uint32_t* lds, ui
     return v + before;
 }
 
-// vals u32 [n, count + 1]: the first `count` values of a frame become their exclusive prefix sums, element `count`
-// the total.  grid n.
+// vals u32 [rows, count + 1]: the first `count` values of a row (a segment) become their exclusive prefix sums, element
+// `count` the total.  grid rows.
 __global__ __launch_bounds__(kScanChunk) void jpeg_scan_kernel(uint32_t* __restrict__ vals, int count) {
     __shared__ uint32_t lds[kScanChunk / 64];
     uint32_t* p = vals + (size_t)blockIdx.x * ((size_t)count + 1);
@@ -156,30 +173,33 @@ __global__ __launch_bounds__(256) void jpeg_clear_kernel(uint32_t* __restrict__ 
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total_words; i += (long long)gridDim.x * 256) words[i] = 0u;
 }
 
-// Whether frame f's span of the stream, words word_off[f] .. word_off[f + 1], lies inside the buffer.
+// Whether segment f's span of the stream, words word_off[f] .. word_off[f + 1], lies inside the buffer.
 __device__ __forceinline__ bool span_ok(const long long* __restrict__ off, size_t f, long long total) {
     return off[f] >= 0 && off[f] <= off[f + 1] && off[f + 1] <= total && off[f + 1] - off[f] < 0x40000000LL;
 }
 
-// coef, bits (offsets) -> the frame's unstuffed stream in words[word_off[f] ..]; grid (blocks / 256, n).
+// coef, bits (offsets) -> segment q's unstuffed stream in words[word_off[q] ..]; grid (segb / 256, segments).
 __global__ __launch_bounds__(kBlockThreads) void jpeg_pack_kernel(const int16_t* __restrict__ coef, JpegEncGeom g,
                                                                   const uint32_t* __restrict__ ehuff, const uint32_t* __restrict__ bits,
                                                                   const long long* __restrict__ word_off, uint32_t* __restrict__ words,
-                                                                  long long total_words) {
+                                                                  long long total_words, int nseg) {
     __shared__ uint32_t tab[2 * JPGE_HUFF_WORDS];
     stage_tables(tab, ehuff);
-    const size_t f = blockIdx.y;
-    const int b = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (b >= g.blocks || !span_ok(word_off, f, total_words)) return;
+    const size_t q = segment_index();
+    const int i = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (q >= (size_t)nseg || i >= g.segb) return;
+    const size_t f = q / (size_t)g.segs;
+    const int b = (int)(q - f * (size_t)g.segs) * g.segb + i;
+    if (b >= g.blocks || !span_ok(word_off, q, total_words)) return;
     const int16_t* base = coef + f * (size_t)g.blocks * 64;
     int16_t zz[64];
     load_block(base + (size_t)b * 64, zz);
     const int pb = jpeg_enc_pred_block(g, b);
     const int pred = pb >= 0 ? base[(size_t)pb * 64] : 0;
-    JpegBitWriter out(words + word_off[f], (uint32_t)(word_off[f + 1] - word_off[f]), bits[f * ((size_t)g.blocks + 1) + b]);
+    JpegBitWriter out(words + word_off[q], (uint32_t)(word_off[q + 1] - word_off[q]), bits[q * ((size_t)g.segb + 1) + i]);
     jpeg_encode_block(zz, pred, tab + JPGE_HUFF_WORDS * jpeg_enc_table_class(g, b), out);
-    if (b == g.blocks - 1) {
-        const int pad = (8 - (out.n & 7)) & 7;      // the final fill: 1 bits to the byte boundary
+    if (i == g.segb - 1 || b == g.blocks - 1) {
+        const int pad = (8 - (out.n & 7)) & 7;      // the segment's final fill: 1 bits to the byte boundary
         out.put((1u << pad) - 1u, pad);
     }
     out.flush();
@@ -206,12 +226,14 @@ __device__ __forceinline__ uint32_t count_ff(uint32_t word, int valid) {
     return c;
 }
 
-// ffc u32 [n, chunks + 1]: FF bytes of every chunk of kStuffChunk stream bytes; grid (chunks, n).
+// ffc u32 [nseg, chunks + 1]: FF bytes of every chunk of kStuffChunk stream bytes of a segment (`blocks`: the blocks of
+// a row of bits); grid (chunks, segments).
 __global__ __launch_bounds__(kScanChunk) void jpeg_ff_kernel(const uint32_t* __restrict__ bits, int blocks, const long long* __restrict__ word_off,
                                                              const uint32_t* __restrict__ words, long long total_words,
-                                                             uint32_t* __restrict__ ffc, int chunks) {
+                                                             uint32_t* __restrict__ ffc, int chunks, int nseg) {
     __shared__ uint32_t lds[kScanChunk / 64];
-    const size_t f = blockIdx.y;
+    const size_t f = segment_index();
+    if (f >= (size_t)nseg) return;      // the whole workgroup
     uint32_t word, total;
     const int valid = lane_bytes(words, word_off, f, total_words, stream_bytes(bits, f, blocks), word);
     workgroup_scan(count_ff(word, valid), lds, total);
@@ -224,14 +246,16 @@ __global__ __launch_bounds__(256) void jpeg_sizes_kernel(const uint32_t* __restr
     if (f < n) sizes[f] = stream_bytes(bits, f, blocks) + ffc[(size_t)f * ((size_t)chunks + 1) + chunks] + 2u;
 }
 
-// The stream bytes to out[out_off[f] ..], a 00 behind every FF, then FF D9; grid (chunks, n).
+// The stream bytes of segment f to out[out_off[f] ..], a 00 behind every FF, then what ends the segment: FF and RSTm
+// (m = s mod 8 for a frame's segment s) or, behind the last of its `segs`, EOI; grid (chunks, segments).
 __global__ __launch_bounds__(kScanChunk) void jpeg_stuff_kernel(const uint32_t* __restrict__ bits, int blocks, const long long* __restrict__ word_off,
                                                                 const uint32_t* __restrict__ words, long long total_words,
                                                                 const uint32_t* __restrict__ ffc, int chunks,
                                                                 const long long* __restrict__ out_off, uint8_t* __restrict__ out,
-                                                                long long out_bytes) {
+                                                                long long out_bytes, JpegEncGeom g, int nseg) {
     __shared__ uint32_t lds[kScanChunk / 64];
-    const size_t f = blockIdx.y;
+    const size_t f = segment_index();
+    if (f >= (size_t)nseg) return;      // the whole workgroup
     const uint32_t nbytes = stream_bytes(bits, f, blocks);
     uint32_t word, total;
     const int valid = lane_bytes(words, word_off, f, total_words, nbytes, word);
@@ -254,7 +278,7 @@ __global__ __launch_bounds__(kScanChunk) void jpeg_stuff_kernel(const uint32_t* 
         const long long eoi = first + nbytes + fc[chunks];
         if (eoi >= first && eoi + 2 <= end) {
             out[eoi] = 0xff;
-            out[eoi + 1] = 0xd9;
+            out[eoi + 1] = (uint8_t)jpeg_enc_seg_marker(g, (int)(f % (size_t)g.segs));
         }
     }
 }
@@ -267,6 +291,95 @@ int check_shape(const char* who, int n, int h, int w, int channels, int sampling
     ELVIS_REQUIRE(n >= 0 && n <= 65535 && h >= 1 && w >= 1 && h <= 65535 && w <= 65535, "%s: bad shape n=%d h=%d w=%d", who, n, h, w);
     ELVIS_REQUIRE(((long long)((w + 7) / 8 + 1) * ((h + 7) / 8 + 1)) * 3 <= JPGE_MAX_BLOCKS, "%s: a %d x %d frame has more than 2^20 blocks", who, h, w);
     g = jpeg_enc_geometry(h, w, channels, 0, sampling);
+    return ELVIS_OK;
+}
+
+// The interval of the restart forms: the geometry gets its segments, `nseg` the segments of the clip.
+int check_restart(const char* who, int n, int restart_mcus, JpegEncGeom& g, int& nseg) {
+    ELVIS_REQUIRE(restart_mcus >= 0 && restart_mcus <= 65535, "%s: restart_mcus must be in [0, 65535], got %d", who, restart_mcus);
+    g = jpeg_enc_restart(g, restart_mcus);
+    ELVIS_REQUIRE((long long)n * g.segs <= ELVIS_JPEG_MAX_SEGMENTS, "%s: %d frames of %d restart intervals are more than %d segments", who, n, g.segs,
+                  ELVIS_JPEG_MAX_SEGMENTS);
+    nseg = n * g.segs;
+    return ELVIS_OK;
+}
+
+// Segments on grid.y and, past 65535 of them, on grid.z: every kernel drops the segments at and past nseg.
+dim3 segment_grid(int x, int nseg) {
+    const int gy = std::min(nseg, 65535);
+    return dim3((unsigned)x, (unsigned)gy, (unsigned)cdiv(nseg, gy));
+}
+
+// The three calls behind the transform; the entry points without an interval are their restart_mcus = 0.
+int bits_call(const char* who, const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
+              int restart_mcus, elvis_stream_t stream) {
+    JpegEncGeom g;
+    int nseg = 0;
+    if (int rc = check_shape(who, n, h, w, channels, sampling, g)) return rc;
+    if (int rc = check_restart(who, n, restart_mcus, g, nseg)) return rc;
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(coef && ehuff && bits, "%s: null pointer", who);
+    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)bits & 3) == 0 && ((uintptr_t)ehuff & 3) == 0,
+                  "%s: coef must be 16-byte aligned, ehuff and bits 4-byte aligned", who);
+    hipLaunchKernelGGL(jpeg_bits_kernel, segment_grid(cdiv(g.segb, kBlockThreads), nseg), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g, ehuff, bits,
+                       nseg);
+    ELVIS_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)nseg), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.segb);
+    ELVIS_CHECK_LAUNCH(who);
+    elvis_note_launch("jpeg_bits_kernel");
+    return ELVIS_OK;
+}
+
+int pack_call(const char* who, const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,
+              int64_t total_words, uint32_t* ffc, int chunks, uint32_t* sizes, int n, int h, int w, int channels, int sampling, int restart_mcus,
+              elvis_stream_t stream) {
+    JpegEncGeom g;
+    int nseg = 0;
+    if (int rc = check_shape(who, n, h, w, channels, sampling, g)) return rc;
+    if (int rc = check_restart(who, n, restart_mcus, g, nseg)) return rc;
+    ELVIS_REQUIRE(total_words >= 0 && total_words < (1LL << 38), "%s: total_words must be in [0, 2^38)", who);
+    ELVIS_REQUIRE(chunks >= 1 && chunks <= 65535 * 32, "%s: chunks must be in [1, 2^21), got %d", who, chunks);
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(coef && ehuff && bits && word_off && words && ffc && sizes, "%s: null pointer", who);
+    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0 && (((uintptr_t)bits | (uintptr_t)ehuff | (uintptr_t)words | (uintptr_t)ffc | (uintptr_t)sizes) & 3) == 0 &&
+                      ((uintptr_t)word_off & 7) == 0,
+                  "%s: coef must be 16-byte, word_off 8-byte, the other buffers 4-byte aligned", who);
+    hipLaunchKernelGGL(jpeg_clear_kernel, dim3((unsigned)std::max(1, std::min(4096, cdiv(total_words, 256)))), dim3(256), 0, (hipStream_t)stream, words,
+                       (long long)total_words);
+    ELVIS_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(jpeg_pack_kernel, segment_grid(cdiv(g.segb, kBlockThreads), nseg), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g, ehuff, bits,
+                       (const long long*)word_off, words, (long long)total_words, nseg);
+    ELVIS_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(jpeg_ff_kernel, segment_grid(chunks, nseg), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.segb, (const long long*)word_off,
+                       (const uint32_t*)words, (long long)total_words, ffc, chunks, nseg);
+    ELVIS_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)nseg), dim3(kScanChunk), 0, (hipStream_t)stream, ffc, chunks);
+    ELVIS_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(jpeg_sizes_kernel, dim3((unsigned)cdiv(nseg, 256)), dim3(256), 0, (hipStream_t)stream, bits, g.segb, (const uint32_t*)ffc, chunks,
+                       sizes, nseg);
+    ELVIS_CHECK_LAUNCH(who);
+    elvis_note_launch("jpeg_pack_kernel");
+    return ELVIS_OK;
+}
+
+int stuff_call(const char* who, const uint32_t* bits, const int64_t* word_off, const uint32_t* words, int64_t total_words, const uint32_t* ffc, int chunks,
+               const int64_t* out_off, uint8_t* out, int64_t out_bytes, int n, int h, int w, int channels, int sampling, int restart_mcus,
+               elvis_stream_t stream) {
+    JpegEncGeom g;
+    int nseg = 0;
+    if (int rc = check_shape(who, n, h, w, channels, sampling, g)) return rc;
+    if (int rc = check_restart(who, n, restart_mcus, g, nseg)) return rc;
+    ELVIS_REQUIRE(total_words >= 0 && total_words < (1LL << 38), "%s: total_words must be in [0, 2^38)", who);
+    ELVIS_REQUIRE(out_bytes >= 0 && out_bytes < (1LL << 40), "%s: out_bytes must be in [0, 2^40)", who);
+    ELVIS_REQUIRE(chunks >= 1 && chunks <= 65535 * 32, "%s: chunks must be in [1, 2^21), got %d", who, chunks);
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(bits && word_off && words && ffc && out_off && out, "%s: null pointer", who);
+    ELVIS_REQUIRE((((uintptr_t)bits | (uintptr_t)words | (uintptr_t)ffc) & 3) == 0 && (((uintptr_t)word_off | (uintptr_t)out_off) & 7) == 0,
+                  "%s: word_off and out_off must be 8-byte, bits, words and ffc 4-byte aligned", who);
+    hipLaunchKernelGGL(jpeg_stuff_kernel, segment_grid(chunks, nseg), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.segb, (const long long*)word_off,
+                       words, (long long)total_words, ffc, chunks, (const long long*)out_off, out, (long long)out_bytes, g, nseg);
+    ELVIS_CHECK_LAUNCH(who);
+    elvis_note_launch("jpeg_stuff_kernel");
     return ELVIS_OK;
 }
 
@@ -295,68 +408,46 @@ extern "C" int elvis_jpeg_fdct(const uint8_t* frames, int16_t* coef, int n, int 
     return ELVIS_OK;
 }
 
+extern "C" int elvis_jpeg_segments(int h, int w, int channels, int sampling, int restart_mcus) {
+    JpegEncGeom g;
+    int nseg = 0;
+    if (check_shape("elvis_jpeg_segments", 0, h, w, channels, sampling, g) != ELVIS_OK) return 0;
+    if (check_restart("elvis_jpeg_segments", 0, restart_mcus, g, nseg) != ELVIS_OK) return 0;
+    return g.segs;
+}
+
 extern "C" int elvis_jpeg_bits(const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
                                elvis_stream_t stream) {
-    JpegEncGeom g;
-    if (int rc = check_shape("elvis_jpeg_bits", n, h, w, channels, sampling, g)) return rc;
-    if (n == 0) return ELVIS_OK;
-    ELVIS_REQUIRE(coef && ehuff && bits, "elvis_jpeg_bits: null pointer");
-    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)bits & 3) == 0 && ((uintptr_t)ehuff & 3) == 0,
-                  "elvis_jpeg_bits: coef must be 16-byte aligned, ehuff and bits 4-byte aligned");
-    hipLaunchKernelGGL(jpeg_bits_kernel, dim3((unsigned)cdiv(g.blocks, kBlockThreads), (unsigned)n), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g,
-                       ehuff, bits);
-    ELVIS_CHECK_LAUNCH("elvis_jpeg_bits");
-    hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)n), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.blocks);
-    ELVIS_CHECK_LAUNCH("elvis_jpeg_bits");
-    elvis_note_launch("jpeg_bits_kernel");
-    return ELVIS_OK;
+    return bits_call("elvis_jpeg_bits", coef, ehuff, bits, n, h, w, channels, sampling, 0, stream);
+}
+
+extern "C" int elvis_jpeg_bits_rst(const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
+                                   int restart_mcus, elvis_stream_t stream) {
+    return bits_call("elvis_jpeg_bits_rst", coef, ehuff, bits, n, h, w, channels, sampling, restart_mcus, stream);
 }
 
 extern "C" int elvis_jpeg_pack(const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,
                                int64_t total_words, uint32_t* ffc, int chunks, uint32_t* sizes, int n, int h, int w, int channels, int sampling,
                                elvis_stream_t stream) {
-    JpegEncGeom g;
-    if (int rc = check_shape("elvis_jpeg_pack", n, h, w, channels, sampling, g)) return rc;
-    ELVIS_REQUIRE(total_words >= 0 && total_words < (1LL << 38), "elvis_jpeg_pack: total_words must be in [0, 2^38)");
-    ELVIS_REQUIRE(chunks >= 1 && chunks <= 65535 * 32, "elvis_jpeg_pack: chunks must be in [1, 2^21), got %d", chunks);
-    if (n == 0) return ELVIS_OK;
-    ELVIS_REQUIRE(coef && ehuff && bits && word_off && words && ffc && sizes, "elvis_jpeg_pack: null pointer");
-    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0 && (((uintptr_t)bits | (uintptr_t)ehuff | (uintptr_t)words | (uintptr_t)ffc | (uintptr_t)sizes) & 3) == 0 &&
-                      ((uintptr_t)word_off & 7) == 0,
-                  "elvis_jpeg_pack: coef must be 16-byte, word_off 8-byte, the other buffers 4-byte aligned");
-    hipLaunchKernelGGL(jpeg_clear_kernel, dim3((unsigned)std::max(1, std::min(4096, cdiv(total_words, 256)))), dim3(256), 0, (hipStream_t)stream, words,
-                       (long long)total_words);
-    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
-    hipLaunchKernelGGL(jpeg_pack_kernel, dim3((unsigned)cdiv(g.blocks, kBlockThreads), (unsigned)n), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g,
-                       ehuff, bits, (const long long*)word_off, words, (long long)total_words);
-    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
-    hipLaunchKernelGGL(jpeg_ff_kernel, dim3((unsigned)chunks, (unsigned)n), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.blocks,
-                       (const long long*)word_off, (const uint32_t*)words, (long long)total_words, ffc, chunks);
-    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
-    hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)n), dim3(kScanChunk), 0, (hipStream_t)stream, ffc, chunks);
-    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
-    hipLaunchKernelGGL(jpeg_sizes_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, bits, g.blocks, (const uint32_t*)ffc, chunks,
-                       sizes, n);
-    ELVIS_CHECK_LAUNCH("elvis_jpeg_pack");
-    elvis_note_launch("jpeg_pack_kernel");
-    return ELVIS_OK;
+    return pack_call("elvis_jpeg_pack", coef, ehuff, bits, word_off, words, total_words, ffc, chunks, sizes, n, h, w, channels, sampling, 0, stream);
+}
+
+extern "C" int elvis_jpeg_pack_rst(const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,
+                                   int64_t total_words, uint32_t* ffc, int chunks, uint32_t* sizes, int n, int h, int w, int channels, int sampling,
+                                   int restart_mcus, elvis_stream_t stream) {
+    return pack_call("elvis_jpeg_pack_rst", coef, ehuff, bits, word_off, words, total_words, ffc, chunks, sizes, n, h, w, channels, sampling, restart_mcus,
+                     stream);
 }
 
 extern "C" int elvis_jpeg_stuff(const uint32_t* bits, const int64_t* word_off, const uint32_t* words, int64_t total_words, const uint32_t* ffc,
                                 int chunks, const int64_t* out_off, uint8_t* out, int64_t out_bytes, int n, int h, int w, int channels,
                                 int sampling, elvis_stream_t stream) {
-    JpegEncGeom g;
-    if (int rc = check_shape("elvis_jpeg_stuff", n, h, w, channels, sampling, g)) return rc;
-    ELVIS_REQUIRE(total_words >= 0 && total_words < (1LL << 38), "elvis_jpeg_stuff: total_words must be in [0, 2^38)");
-    ELVIS_REQUIRE(out_bytes >= 0 && out_bytes < (1LL << 40), "elvis_jpeg_stuff: out_bytes must be in [0, 2^40)");
-    ELVIS_REQUIRE(chunks >= 1 && chunks <= 65535 * 32, "elvis_jpeg_stuff: chunks must be in [1, 2^21), got %d", chunks);
-    if (n == 0) return ELVIS_OK;
-    ELVIS_REQUIRE(bits && word_off && words && ffc && out_off && out, "elvis_jpeg_stuff: null pointer");
-    ELVIS_REQUIRE((((uintptr_t)bits | (uintptr_t)words | (uintptr_t)ffc) & 3) == 0 && (((uintptr_t)word_off | (uintptr_t)out_off) & 7) == 0,
-                  "elvis_jpeg_stuff: word_off and out_off must be 8-byte, bits, words and ffc 4-byte aligned");
-    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3((unsigned)chunks, (unsigned)n), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.blocks,
-                       (const long long*)word_off, words, (long long)total_words, ffc, chunks, (const long long*)out_off, out, (long long)out_bytes);
-    ELVIS_CHECK_LAUNCH("elvis_jpeg_stuff");
-    elvis_note_launch("jpeg_stuff_kernel");
-    return ELVIS_OK;
+    return stuff_call("elvis_jpeg_stuff", bits, word_off, words, total_words, ffc, chunks, out_off, out, out_bytes, n, h, w, channels, sampling, 0, stream);
+}
+
+extern "C" int elvis_jpeg_stuff_rst(const uint32_t* bits, const int64_t* word_off, const uint32_t* words, int64_t total_words, const uint32_t* ffc,
+                                    int chunks, const int64_t* out_off, uint8_t* out, int64_t out_bytes, int n, int h, int w, int channels,
+                                    int sampling, int restart_mcus, elvis_stream_t stream) {
+    return stuff_call("elvis_jpeg_stuff_rst", bits, word_off, words, total_words, ffc, chunks, out_off, out, out_bytes, n, h, w, channels, sampling,
+                      restart_mcus, stream);
 }

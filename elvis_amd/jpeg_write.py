@@ -9,17 +9,31 @@ path for those suffixes, the writer half of jpeg.py:
   jpeg_roundtrip_device(frames_d, quality)     encode, then jpeg.decode_jpeg_device: (decoded resident clip, bytes per frame)
   jpeg_quant_tables(quality)                   host: the two quantisation tables
   jpeg_file_header(width, height, ...)         host: everything in front of the entropy-coded bytes
+  jpeg_restart_interval(width, height, ...)    host: the restart interval in MCUs that `restart_rows=` / `restart_mcus=` ask for
 
 Colour conversion, edge replication, chroma downsampling, the forward DCT, the quantiser, the Huffman coding, the bit
 packing and the byte stuffing run as HIP kernels; the host plans the layout from two small downloads (a frame's bit
 count, then its byte count), writes the headers and downloads the finished scans.  Pixels and coefficients never visit
 the host.  The arithmetic is libjpeg's (jccolor.c, jcsample.c, jfdctint.c, jcdctmgr.c, jchuff.c with the Annex K tables,
-one interleaved scan, no restart interval): against a libjpeg-turbo PIL at the same quality and sampling with
-`optimize=False`, the quantisation tables, the SOF0 / SOS contents and the entropy-coded bytes are equal bit for bit;
+one interleaved scan): against a libjpeg-turbo PIL at the same quality and sampling with `optimize=False`, the
+quantisation tables, the SOF0 / SOS contents and the entropy-coded bytes are equal bit for bit;
 tests/_jpeg_write_ref.py states them.  Equality of whole files is not claimed (the JFIF header's density fields are the
 writer's own), and PARITY WITH cv2 IS UNPINNED: quality 95 and 4:2:0, the defaults here, are what `cv2.imwrite` asks its
 libjpeg for, but no cv2 is at hand to compare with.  Opt-in: `frameio.save_frame` stays PIL, and the directory drivers
 write `.jpg` names through PIL unless called with `jpeg_writer="device"`.
+
+Restart intervals.  By default a file has none, as `cv2.imwrite` writes it, and its scan is one entropy-coded segment:
+the device reader (jpeg.py) decodes a segment per lane, so such a frame keeps one lane busy.  `restart_rows=r` (libjpeg's
+`restart_in_rows`: an interval of min(r * MCUs per row, 65535) MCUs) or `restart_mcus=k` (`restart_interval = k`) on
+every form above cuts the scan into intervals: the header gets a DRI segment in front of SOS, every interval starts on a
+byte boundary with the DC predictors at 0 and ends in the 1-fill, and RSTm markers (m = 0..7 in turn) stand between
+them (jchuff.c `emit_restart`).  Turn it on - `restart_rows=1` - whenever the device reader will read the files: what
+`jpeg_roundtrip_device` decodes itself, a directory the next driver loads with `png_reader="device"`.  It costs the
+markers, the fill bits and the DC resets in bytes, and any decoder reads the files.  The kernels are the same: behind
+the transform they work per (frame, interval) instead of per frame, an interval being what a frame is without them.
+The bit-for-bit claim extends to it: against PIL with `restart_marker_rows=` / `restart_marker_blocks=` the DRI
+segment's place and content and the entropy-coded bytes, markers included, are equal; tests/_jpeg_restart_ref.py
+states the rule.
 """
 from __future__ import annotations
 
@@ -42,6 +56,7 @@ STUFF_CHUNK_BYTES = 1024        # ELVIS_JPEG_STUFF_CHUNK: stream bytes of one wo
 HUFF_WORDS = 272                # per table class: 16 DC entries by category, 256 AC entries by symbol
 MAX_BLOCKS = 1 << 20            # blocks of a frame
 MAX_FRAMES = 65535              # frames of one launch
+MAX_SEGMENTS = 1 << 24          # ELVIS_JPEG_MAX_SEGMENTS: (frame, restart interval) pairs of one launch
 UPLOAD_CHUNK_BYTES = 32 << 20
 # ITU-T T.81 Annex K.1, K.2: the quantisation tables in natural order
 BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87,
@@ -85,6 +100,35 @@ def _check_subsampling(subsampling, who: str) -> int:
     return SUBSAMPLINGS.index(subsampling)
 
 
+def _check_restart(restart_rows, restart_mcus, who: str) -> Tuple[int, int]:
+    for name, v in (("restart_rows", restart_rows), ("restart_mcus", restart_mcus)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+            raise ValueError(f"{who}: {name} must be a non-negative integer, got {v!r}")
+    if restart_rows and restart_mcus:
+        raise ValueError(f"{who}: restart_rows={restart_rows} and restart_mcus={restart_mcus}: give one of them")
+    if int(restart_mcus) > 65535:
+        raise ValueError(f"{who}: restart_mcus must be in 1..65535 (0: no interval), got {restart_mcus}")
+    return int(restart_rows), int(restart_mcus)
+
+
+def jpeg_restart_interval(width: int, height: int, channels: int = 3, subsampling: str = "420", restart_rows: int = 0,
+                          restart_mcus: int = 0) -> int:
+    """Host only: the restart interval in MCUs of a width x height frame, 0 for none.  `restart_mcus=k`, 1..65535, is
+    libjpeg's `restart_interval = k`; `restart_rows=r` is its `restart_in_rows`: min(r * MCUs per row, 65535), an MCU
+    being 8 x 8 pixels of a gray frame and 8 * hmax x 8 * vmax of a colour one.  Giving both is a ValueError."""
+    who = "jpeg_restart_interval"
+    rows, mcus = _check_restart(restart_rows, restart_mcus, who)
+    _check_subsampling(subsampling, who)
+    if isinstance(channels, bool) or channels not in (1, 3):
+        raise ValueError(f"{who}: channels must be 1 or 3, got {channels!r}")
+    if not 1 <= int(width) <= 65535 or not 1 <= int(height) <= 65535:
+        raise ValueError(f"{who}: width and height must be in 1..65535, got {width} x {height}")
+    if mcus:
+        return mcus
+    hmax = _FACTORS[subsampling][0] if channels == 3 else 1
+    return min(rows * -(-int(width) // (8 * hmax)), 65535)
+
+
 def jpeg_quant_tables(quality: int = 95) -> Tuple[np.ndarray, np.ndarray]:
     """Host only: (luma, chroma) quantisation tables, uint16 [64] in natural order, as libjpeg's
     `jpeg_set_quality(quality, force_baseline=TRUE)` scales the Annex K tables: (base * scale + 50) // 100 clamped to
@@ -122,12 +166,17 @@ def _segment(marker: int, body: bytes) -> bytes:
     return bytes([0xFF, marker]) + struct.pack(">H", len(body) + 2) + body
 
 
-def jpeg_file_header(width: int, height: int, channels: int = 3, quality: int = 95, subsampling: str = "420") -> bytes:
+def jpeg_file_header(width: int, height: int, channels: int = 3, quality: int = 95, subsampling: str = "420",
+                     restart_interval: int = 0) -> bytes:
     """Host only: everything of a file in front of its entropy-coded bytes - SOI, the JFIF APP0 segment, one DQT segment per
-    table, SOF0, the DHT segments (DC 0, AC 0, and DC 1, AC 1 for colour) and SOS; the device's scan, which ends with
-    EOI, follows it.  Components 1 (Y: table 0, Huffman tables 0) and, for colour, 2 and 3 (Cb, Cr: table 1, Huffman
-    tables 1)."""
+    table, SOF0, the DHT segments (DC 0, AC 0, and DC 1, AC 1 for colour), for a `restart_interval` (in MCUs) other than
+    0 the DRI segment FF DD 00 04 <interval, big-endian>, where libjpeg's `write_scan_header` puts it, and SOS; the
+    device's scan, which ends with EOI, follows it.  Components 1 (Y: table 0, Huffman tables 0) and, for colour, 2 and
+    3 (Cb, Cr: table 1, Huffman tables 1)."""
     who = "jpeg_file_header"
+    ri = restart_interval
+    if isinstance(ri, bool) or not isinstance(ri, (int, np.integer)) or not 0 <= int(ri) <= 65535:
+        raise ValueError(f"{who}: restart_interval must be an integer in 0..65535, got {ri!r}")
     q = _check_quality(quality, who)
     _check_subsampling(subsampling, who)
     if isinstance(channels, bool) or channels not in (1, 3):
@@ -145,6 +194,8 @@ def jpeg_file_header(width: int, height: int, channels: int = 3, quality: int = 
     for t in range(ntab):
         out += _segment(0xC4, bytes([t]) + bytes(STD_DC[t][0]) + bytes(STD_DC[t][1]))
         out += _segment(0xC4, bytes([0x10 | t]) + bytes(STD_AC[t][0]) + bytes(STD_AC[t][1]))
+    if int(ri):
+        out += _segment(0xDD, struct.pack(">H", int(ri)))
     out += _segment(0xDA, bytes([len(comps)]) + b"".join(bytes([cid, tq * 0x11]) for cid, _, _, tq in comps) + bytes([0, 63, 0]))
     return bytes(out)
 
@@ -177,6 +228,18 @@ def _check_clip(frames_d, order, quality, subsampling, who: str):
     return n, h, w, c, int(order == "bgr"), q, scode
 
 
+def _check_segments(n: int, h: int, w: int, c: int, subsampling: str, ri: int, who: str) -> Tuple[int, int]:
+    """(the restart intervals of a frame, 1 without an interval or with one that holds the whole scan; its MCUs).  A clip
+    with more (frame, interval) pairs than one launch takes is refused here, before the library is touched."""
+    hmax, vmax = _FACTORS[subsampling] if c == 3 else (1, 1)
+    mcus = -(-w // (8 * hmax)) * -(-h // (8 * vmax))
+    segs = -(-mcus // ri) if 0 < ri < mcus else 1
+    if n * segs > MAX_SEGMENTS:
+        raise ValueError(f"{who}: {n} frames of {segs} restart intervals are more than {MAX_SEGMENTS} segments in one launch; encode the clip "
+                         f"in parts or widen the interval")
+    return segs, mcus
+
+
 def _guarded(nbytes: int, guard: int, dev, fill: int = 0):
     """(a uint8 buffer of nbytes holding `fill` with `guard` bytes of 0xA5 on either side, the payload's view).  Every
     byte the kernels read from a work buffer they wrote before; `fill` is the tests' knob to show it."""
@@ -187,12 +250,24 @@ def _guarded(nbytes: int, guard: int, dev, fill: int = 0):
     return buf, buf[guard:guard + nbytes]
 
 
-def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, guard: int = 0, fill: int = 0):
+def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, guard: int = 0, fill: int = 0, restart=(0, 0)):
     """The four calls and the two small downloads between them.  Returns None for an empty clip, else a dict: `out_buf`
     (the finished scans on the device with `guard` bytes of 0xA5 on either side), `out_off` (int64 [n + 1], frame f's scan
     is bytes out_off[f] .. out_off[f + 1] of the payload), `header`, and the work buffers with their guards (`coef_buf`,
-    `bits_buf`, `words_buf`, `ffc_buf`, `sizes_buf`) with `blocks` and `chunks`; `out` is the payload of `out_buf`."""
+    `bits_buf`, `words_buf`, `ffc_buf`, `sizes_buf`) with `blocks` and `chunks`; `out` is the payload of `out_buf`.
+
+    `restart` = (restart_rows, restart_mcus).  Without an interval the layouts are: bits u32 [n, blocks + 1], words as
+    `word_off` of the frames' byte counts says, ffc u32 [n, chunks + 1], sizes u32 [n].  With one the library's restart
+    entry points run and everything behind the coefficients is per segment q = f * segments + s: bits u32 [n * segments,
+    segment_blocks + 1] (a frame's last segment may hold fewer blocks; the elements past them repeat its bit count), a
+    span of whole words for every segment in words_buf (no two segments share a word, however short they are), ffc u32
+    [n * segments, chunks + 1] with `chunks` those of the longest segment, sizes u32 [n * segments] (each with the 2
+    bytes of its RSTm or EOI).  A frame's finished scan is its segments back to back, so `out_off` stays per frame; the
+    dict gains `restart_interval`, `segments`, `segment_blocks` and `seg_off` (int64 [n * segments + 1])."""
+    rows, mcus = _check_restart(*restart, who)
     n, h, w, c, ocode, q, scode = _check_clip(frames_d, order, quality, subsampling, who)
+    ri = jpeg_restart_interval(w, h, c, subsampling, rows, mcus)
+    segs, mcus_of_frame = _check_segments(n, h, w, c, subsampling, ri, who)
     if n == 0:
         return None
     if guard % 16:
@@ -201,40 +276,52 @@ def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, 
     blocks = int(lib().elvis_jpeg_frame_blocks(h, w, c, scode))      # the kernels' own count sizes the buffers
     if blocks < 1:
         raise ValueError(f"{who}: the library refuses a {h} x {w} frame of {c} channel(s)")
-    header = jpeg_file_header(w, h, c, q, subsampling)
+    segb = blocks
+    if ri:
+        if int(lib().elvis_jpeg_segments(h, w, c, scode, ri)) != segs:
+            raise ValueError(f"{who}: the library counts other than {segs} restart intervals of {ri} MCUs in a {h} x {w} frame")
+        segb = blocks if segs == 1 else ri * (blocks // mcus_of_frame)
+    nseg = n * segs
+    tail = (ri,) if ri else ()          # the restart entry points take the interval behind `sampling`
+    bits_fn, pack_fn, stuff_fn = ((lib().elvis_jpeg_bits_rst, lib().elvis_jpeg_pack_rst, lib().elvis_jpeg_stuff_rst) if ri else
+                                  (lib().elvis_jpeg_bits, lib().elvis_jpeg_pack, lib().elvis_jpeg_stuff))
+    header = jpeg_file_header(w, h, c, q, subsampling, ri)
     s = _s(frames_d)
     with torch.cuda.device(dev):
         ehuff_d = torch.from_numpy(encode_tables().view(np.int32)).to(dev)
         coef_buf, coef_d = _guarded(n * blocks * 128, guard, dev, fill)
-        bits_buf, bits_d = _guarded(n * (blocks + 1) * 4, guard, dev, fill)
+        bits_buf, bits_d = _guarded(nseg * (segb + 1) * 4, guard, dev, fill)
         check(lib().elvis_jpeg_fdct(ptr(frames_d), ptr(coef_d), n, h, w, c, ocode, q, scode, s), dev)
-        check(lib().elvis_jpeg_bits(ptr(coef_d), ptr(ehuff_d), ptr(bits_d), n, h, w, c, scode, s), dev)
-        # the first synchronisation of a clip: every frame's bit count
-        total_bits = bits_d.view(torch.int32).view(n, blocks + 1)[:, blocks].cpu().numpy().view(np.uint32).astype(np.int64)
+        check(bits_fn(ptr(coef_d), ptr(ehuff_d), ptr(bits_d), n, h, w, c, scode, *tail, s), dev)
+        # the first synchronisation of a clip: every segment's bit count (a frame is one segment without an interval)
+        total_bits = bits_d.view(torch.int32).view(nseg, segb + 1)[:, segb].cpu().numpy().view(np.uint32).astype(np.int64)
         stream_bytes = (total_bits + 7) // 8
         word_off = np.concatenate([[0], np.cumsum((stream_bytes + 3) // 4)]).astype(np.int64)
         total_words = int(word_off[-1])
         chunks = max(1, int(-(-int(stream_bytes.max()) // STUFF_CHUNK_BYTES)))
         word_off_d = torch.from_numpy(word_off).to(dev)
         words_buf, words_d = _guarded(total_words * 4, guard, dev, fill)
-        ffc_buf, ffc_d = _guarded(n * (chunks + 1) * 4, guard, dev, fill)
-        sizes_buf, sizes_d = _guarded(n * 4, guard, dev, fill)
-        check(lib().elvis_jpeg_pack(ptr(coef_d), ptr(ehuff_d), ptr(bits_d), ptr(word_off_d), ptr(words_d), total_words, ptr(ffc_d), chunks,
-                                    ptr(sizes_d), n, h, w, c, scode, s), dev)
-        # the second: every frame's byte count with the stuffed zeros and EOI
+        ffc_buf, ffc_d = _guarded(nseg * (chunks + 1) * 4, guard, dev, fill)
+        sizes_buf, sizes_d = _guarded(nseg * 4, guard, dev, fill)
+        check(pack_fn(ptr(coef_d), ptr(ehuff_d), ptr(bits_d), ptr(word_off_d), ptr(words_d), total_words, ptr(ffc_d), chunks, ptr(sizes_d), n, h, w, c,
+                      scode, *tail, s), dev)
+        # the second: every segment's byte count with the stuffed zeros and its marker or EOI
         sizes = sizes_d.cpu().numpy().view(np.uint32).astype(np.int64)
-        out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        total = int(out_off[-1])
-        out_off_d = torch.from_numpy(out_off).to(dev)
+        seg_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        total = int(seg_off[-1])
+        seg_off_d = torch.from_numpy(seg_off).to(dev)
         out_buf, out_d = _guarded(total, guard, dev, fill)
-        check(lib().elvis_jpeg_stuff(ptr(bits_d), ptr(word_off_d), ptr(words_d), total_words, ptr(ffc_d), chunks, ptr(out_off_d), ptr(out_d),
-                                     total, n, h, w, c, scode, s), dev)
-    return {"out_buf": out_buf, "out": out_d, "out_off": out_off, "header": header, "coef_buf": coef_buf, "bits_buf": bits_buf,
-            "words_buf": words_buf, "ffc_buf": ffc_buf, "sizes_buf": sizes_buf, "blocks": blocks, "chunks": chunks}
+        check(stuff_fn(ptr(bits_d), ptr(word_off_d), ptr(words_d), total_words, ptr(ffc_d), chunks, ptr(seg_off_d), ptr(out_d), total, n, h, w, c, scode,
+                       *tail, s), dev)
+    got = {"out_buf": out_buf, "out": out_d, "out_off": np.ascontiguousarray(seg_off[::segs]), "header": header, "coef_buf": coef_buf,
+           "bits_buf": bits_buf, "words_buf": words_buf, "ffc_buf": ffc_buf, "sizes_buf": sizes_buf, "blocks": blocks, "chunks": chunks}
+    if ri:
+        got.update(restart_interval=ri, segments=segs, segment_blocks=segb, seg_off=seg_off)
+    return got
 
 
-def _encode_to_host(frames_d, order, quality, subsampling, who: str) -> List[bytes]:
-    got = _encode_clip(frames_d, order, quality, subsampling, who)
+def _encode_to_host(frames_d, order, quality, subsampling, who: str, restart=(0, 0)) -> List[bytes]:
+    got = _encode_clip(frames_d, order, quality, subsampling, who, restart=restart)
     if got is None:
         return []
     host = got["out"].cpu().numpy()
@@ -242,31 +329,37 @@ def _encode_to_host(frames_d, order, quality, subsampling, who: str) -> List[byt
     return [got["header"] + host[int(off[f]):int(off[f + 1])].tobytes() for f in range(off.size - 1)]
 
 
-def encode_jpeg_device(frames_d: torch.Tensor, order: str = "bgr", quality: int = 95, subsampling: str = "420") -> List[bytes]:
+def encode_jpeg_device(frames_d: torch.Tensor, order: str = "bgr", quality: int = 95, subsampling: str = "420", *, restart_rows: int = 0,
+                       restart_mcus: int = 0) -> List[bytes]:
     """One complete baseline JPEG file per frame of a resident contiguous uint8 clip [n,H,W,3], [n,H,W,1] or [n,H,W].
     `order` is the channel order of a 3-channel clip ("bgr", what `save_frame` takes, or "rgb"); `quality` 1..100 and
     `subsampling` "444" | "422" | "420" are libjpeg's; quality 95 and 4:2:0, the defaults, are what `cv2.imwrite` uses.
-    A gray clip is one component and `subsampling` is ignored.  A frame's bytes do not depend on the frames it is
-    encoded with.  ValueError before any launch for a bad argument; an empty clip gives []."""
-    return _encode_to_host(frames_d, order, quality, subsampling, "encode_jpeg_device")
+    A gray clip is one component and `subsampling` is ignored.  `restart_rows=r` (an interval of r MCU rows, at most
+    65535 MCUs) or `restart_mcus=k` (an interval of k MCUs, 1..65535), one of them, writes restart intervals: DRI in the
+    header, RSTm between the intervals; the default is none.  Turn it on where the device reader will read the files.
+    A frame's bytes do not depend on the frames it is encoded with.  ValueError before any launch for a bad argument;
+    an empty clip gives []."""
+    return _encode_to_host(frames_d, order, quality, subsampling, "encode_jpeg_device", (restart_rows, restart_mcus))
 
 
-def save_jpeg_frames_device(frames_d: torch.Tensor, paths: Sequence, order: str = "bgr", quality: int = 95, subsampling: str = "420") -> None:
+def save_jpeg_frames_device(frames_d: torch.Tensor, paths: Sequence, order: str = "bgr", quality: int = 95, subsampling: str = "420", *,
+                            restart_rows: int = 0, restart_mcus: int = 0) -> None:
     """`encode_jpeg_device`, and frame i written to paths[i]; directories are created as `save_frame` does."""
     paths = list(paths)
     if not isinstance(frames_d, torch.Tensor) or frames_d.dim() < 1 or len(paths) != frames_d.shape[0]:
         raise ValueError(f"save_jpeg_frames_device: {len(paths)} path(s) for the clip {tuple(getattr(frames_d, 'shape', ()))}")
-    for path, data in zip(paths, _encode_to_host(frames_d, order, quality, subsampling, "save_jpeg_frames_device")):
+    for path, data in zip(paths, _encode_to_host(frames_d, order, quality, subsampling, "save_jpeg_frames_device", (restart_rows, restart_mcus))):
         os.makedirs(os.path.dirname(os.fspath(path)) or ".", exist_ok=True)
         with open(path, "wb") as f:
             f.write(data)
 
 
 def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=None, order: str = "bgr", quality: int = 95,
-                     subsampling: str = "420") -> None:
+                     subsampling: str = "420", restart_rows: int = 0, restart_mcus: int = 0) -> None:
     """Host frames - uint8 (H,W,3), (H,W,1) or (H,W) arrays, a list or one [n,...] array - written as JPEGs to `paths`
     through the device.  Uploaded and encoded `chunk_frames` frames at a time, by default as many as make 32 MB (5 at
-    1080p); a run of equal shapes is one clip.  The files do not depend on the chunk size."""
+    1080p); a run of equal shapes is one clip.  The files do not depend on the chunk size.  `restart_rows` / `restart_mcus`:
+    as `encode_jpeg_device` takes them."""
     who = "save_jpeg_frames"
     paths = list(paths)
     if len(frames) != len(paths):
@@ -277,6 +370,7 @@ def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=N
         raise ValueError(f"{who}: order must be 'bgr' or 'rgb', got {order!r}")
     _check_quality(quality, who)
     _check_subsampling(subsampling, who)
+    _check_restart(restart_rows, restart_mcus, who)
     arrays = [np.asarray(f) for f in frames]
     for a in arrays:
         if a.dtype != np.uint8 or a.ndim not in (2, 3):
@@ -291,16 +385,18 @@ def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=N
             while end < len(arrays) and end - at < step and arrays[end].shape == shape:
                 end += 1
             clip = torch.from_numpy(np.ascontiguousarray(np.stack(arrays[at:end], axis=0))).to(dev)
-            save_jpeg_frames_device(clip, paths[at:end], order, quality, subsampling)
+            save_jpeg_frames_device(clip, paths[at:end], order, quality, subsampling, restart_rows=restart_rows, restart_mcus=restart_mcus)
             at = end
 
 
-def jpeg_roundtrip_device(frames_d: torch.Tensor, quality: int = 95, subsampling: str = "420", order: str = "bgr"):
+def jpeg_roundtrip_device(frames_d: torch.Tensor, quality: int = 95, subsampling: str = "420", order: str = "bgr", *, restart_rows: int = 0,
+                          restart_mcus: int = 0):
     """An intra codec in the loop: `encode_jpeg_device` at `quality`, then `jpeg.decode_jpeg_device` of those files.
     Returns (the decoded resident clip, uint8 [n,H,W,C] in the clip's own channel count and `order`; the bytes of every
-    frame's file, int64 [n]) - the pixels a client would see and the rate they cost."""
+    frame's file, int64 [n]) - the pixels a client would see and the rate they cost.  `restart_rows=1` gives the reader a
+    segment per MCU row to decode side by side: the same pixels, sooner, for a few more bytes."""
     from .jpeg import decode_jpeg_device
-    files = _encode_to_host(frames_d, order, quality, subsampling, "jpeg_roundtrip_device")
+    files = _encode_to_host(frames_d, order, quality, subsampling, "jpeg_roundtrip_device", (restart_rows, restart_mcus))
     if not files:
         raise ValueError("jpeg_roundtrip_device: no frames")
     c = int(frames_d.shape[3]) if frames_d.dim() == 4 else 1

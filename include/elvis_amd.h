@@ -955,7 +955,7 @@ int elvis_jpeg_colour(const uint8_t* planes, int64_t stride_blocks, const int32_
  * libjpeg-turbo at the same quality and sampling without optimised tables the quantisation tables and the entropy-coded
  * bytes are equal bit for bit; tests/_jpeg_write_ref.py states them.  frames u8 [n, h, w, channels], channels 1 (gray,
  * one component, sampling ignored) or 3 (order 0 = RGB, 1 = BGR; sampling 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 of Y, Cb,
- * Cr).  One interleaved scan, no restart interval, the Annex K Huffman tables.  The host plans the layout between the
+ * Cr).  One interleaved scan, no restart interval (the restart forms are below), the Annex K Huffman tables.  The host plans the layout between the
  * calls from two small downloads - a frame's bit count, then its byte count - writes the headers and downloads the
  * finished scans; pixels and coefficients never visit it (the caller synchronises, no entry point does):
  *   blocks   elvis_jpeg_frame_blocks: the blocks of a frame in MCU scan order (gray: ceil(w/8) * ceil(h/8); colour:
@@ -986,9 +986,29 @@ int elvis_jpeg_colour(const uint8_t* planes, int64_t stride_blocks, const int32_
  * bytes, alone or in a batch, whatever the buffers held.
  * ELVIS_E_INVALID before any launch: channels outside {1, 3}, a bad order or sampling, quality outside [1, 100], n
  * outside [0, 65535], h or w outside [1, 65535], more than 2^20 blocks a frame, chunks under 1, a negative size, a null
- * pointer, a misaligned buffer (coef 16, the offset tables 8, the others 4 bytes).  n == 0 is a no-op. */
+ * pointer, a misaligned buffer (coef 16, the offset tables 8, the others 4 bytes).  n == 0 is a no-op.
+ *
+ * Restart intervals (T.81 B.2.4.4, E.1.4; libjpeg's restart_interval, jchuff.c emit_restart): elvis_jpeg_bits_rst, _pack_rst
+ * and _stuff_rst are calls 2 - 4 with restart_mcus in [0, 65535], the MCUs of an interval; elvis_jpeg_fdct is the same for
+ * both forms.  A frame of M MCUs is segs = ceil(M / restart_mcus) segments (elvis_jpeg_segments; 1 for restart_mcus = 0 or
+ * >= M, 0 for arguments that are refused), segment s holding MCUs [s * restart_mcus, min((s + 1) * restart_mcus, M)),
+ * segb = restart_mcus * blocks per MCU blocks in all but the last (segb = blocks when segs = 1).  A segment starts on a
+ * byte boundary with the DC predictor of every component at 0 (a dummy block still repeats the block before it in its
+ * own MCU), ends in the 1-fill to the byte boundary, which is stuffed like any other byte, and is followed by FF D0+(s &
+ * 7), which is not stuffed, or, behind a frame's last segment, by FF D9.  Everything that is per frame above is per
+ * segment q = f * segs + s here, nseg = n * segs of them:
+ *   bits u32 [nseg, segb + 1]: the bit offset of the segment's block i in the segment's stream, the segment's bit
+ *      count in element segb; the elements past the blocks of a frame's last segment hold that count as well.
+ *   word_off i64 [nseg + 1]: every segment has its own span of words, so that no two segments share a word; ffc u32
+ *      [nseg, chunks + 1] (chunks >= the chunks of the longest segment); sizes u32 [nseg]: stream bytes + FF bytes + 2.
+ *   out_off i64 [nseg + 1]: a frame's finished scan is its segments back to back, out[out_off[f * segs] .. out_off[(f +
+ *      1) * segs]), each with its marker, the last with EOI.
+ * restart_mcus = 0 is calls 2 - 4 themselves: the same code, the same layouts, the same bytes.  The file's DRI segment
+ * is the caller's.  ELVIS_E_INVALID before any launch for what the calls above refuse, restart_mcus outside [0, 65535]
+ * and n * segs above ELVIS_JPEG_MAX_SEGMENTS (encode the clip in parts). */
 #define ELVIS_JPEG_SCAN_CHUNK 256
 #define ELVIS_JPEG_STUFF_CHUNK 1024
+#define ELVIS_JPEG_MAX_SEGMENTS 16777216
 int elvis_jpeg_frame_blocks(int h, int w, int channels, int sampling);
 int elvis_jpeg_fdct(const uint8_t* frames, int16_t* coef, int n, int h, int w, int channels, int order, int quality, int sampling,
                     elvis_stream_t stream);
@@ -1000,6 +1020,15 @@ int elvis_jpeg_pack(const int16_t* coef, const uint32_t* ehuff, const uint32_t* 
 int elvis_jpeg_stuff(const uint32_t* bits, const int64_t* word_off, const uint32_t* words, int64_t total_words, const uint32_t* ffc,
                      int chunks, const int64_t* out_off, uint8_t* out, int64_t out_bytes, int n, int h, int w, int channels, int sampling,
                      elvis_stream_t stream);
+int elvis_jpeg_segments(int h, int w, int channels, int sampling, int restart_mcus);
+int elvis_jpeg_bits_rst(const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
+                        int restart_mcus, elvis_stream_t stream);
+int elvis_jpeg_pack_rst(const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,
+                        int64_t total_words, uint32_t* ffc, int chunks, uint32_t* sizes, int n, int h, int w, int channels, int sampling,
+                        int restart_mcus, elvis_stream_t stream);
+int elvis_jpeg_stuff_rst(const uint32_t* bits, const int64_t* word_off, const uint32_t* words, int64_t total_words, const uint32_t* ffc,
+                         int chunks, const int64_t* out_off, uint8_t* out, int64_t out_bytes, int n, int h, int w, int channels,
+                         int sampling, int restart_mcus, elvis_stream_t stream);
 
 /* ------------------------------------------------------------------ Real-ESRGAN / RRDBNet (rrdb.hip)
  * The network behind RealESRGANer.enhance (elvis.py:2515): RRDBNet(3, 3, 64, num_block, 32, scale) on f16 NHWC tensors.
