@@ -20,6 +20,7 @@ from .degrade import (blur_block, degrade_adaptive_blur, degrade_adaptive_downsa
 from .handoff import (calculate_importance_scores, convert_frames_to_yuv420p, create_kvazaar_roi_file,  # noqa: F401
                       create_svtav1_roi_file, kvazaar_delta_qp, rgb_to_i420_device, svtav1_delta_qp, write_y4m)
 from .handoff import (Y4MInfo, i420_to_rgb_device, load_y4m_device, load_yuv420p_device, parse_y4m, read_y4m)  # noqa: F401
+from .handoff import encode_with_roi_device, roi_levels_from_importance  # noqa: F401
 from .classical import (lanczos_restore_device, restore_blur_opencv_unsharp_mask,  # noqa: F401
                         restore_downsample_opencv_lanczos, restore_with_opencv_lanczos, restore_with_opencv_unsharp,
                         temporal_blend_device, unsharp_restore_device)
@@ -44,8 +45,9 @@ from .fvmd import (FvmdConfig, FvmdNoTrajectories, calculate_fvmd, calculate_fvm
                    fvmd_device, motion_features_device, track_keypoints_device)
 from .png import decode_png_device, encode_png_device, load_frames_device, save_frames, save_frames_device  # noqa: F401
 from .jpeg import decode_jpeg_device, load_images_device, load_jpeg_frames_device, parse_jpeg  # noqa: F401
-from .jpeg_write import (encode_jpeg_device, jpeg_file_header, jpeg_quant_tables, jpeg_restart_interval, jpeg_roundtrip_device,  # noqa: F401
-                         save_jpeg_frames, save_jpeg_frames_device)
+from .jpeg_write import (JPEG_ROI_MAX_LEVEL, encode_jpeg_device, jpeg_encoded_sizes_device, jpeg_file_header, jpeg_quality_for_bytes,  # noqa: F401
+                         jpeg_quant_tables, jpeg_restart_interval, jpeg_roi_levels, jpeg_roi_scale16, jpeg_roundtrip_at_bytes_device,
+                         jpeg_roundtrip_device, save_jpeg_frames, save_jpeg_frames_device)
 from .segment import SegmentConfig, foreground_masks_device, save_foreground_masks, segment_frames  # noqa: F401
 from .drivers import calculate_removability_scores_device  # noqa: F401
 from .drivers import (calculate_removability_scores_from_frames, restore_blur_adaptive, restore_dct_adaptive,  # noqa: F401

@@ -137,6 +137,7 @@ SIGNATURES = {
     "elvis_jpeg_colour": [vp, i64, vp, vp, i32, i32, i32, i32, i32, vp],
     "elvis_jpeg_frame_blocks": [i32, i32, i32, i32],
     "elvis_jpeg_fdct": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_jpeg_fdct_roi": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp],
     "elvis_jpeg_bits": [vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "elvis_jpeg_pack": [vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, vp],
     "elvis_jpeg_stuff": [vp, vp, vp, i64, vp, i32, vp, vp, i64, i32, i32, i32, i32, i32, vp],

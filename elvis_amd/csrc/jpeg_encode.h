@@ -213,6 +213,51 @@ JPGE_HD int jpeg_quantise(int coef, int table) {
     return coef < 0 ? -q : q;
 }
 
+// ----------------------------------------------------------------------------- per-block rate allocation (ROI)
+// A map of coarsening levels, uint8 [By, Bx] on a grid of B x B luma pixels, in HEVC QP units: the quantiser step doubles
+// every 6 levels.  A coefficient that the quantiser of the file's own table coarsened by the block's level would round to
+// zero is zeroed; every other one keeps the file's own quantiser, and DC is never touched - a dead zone, not a coarser
+// step, so the file stays a baseline JPEG with the tables of its header.  Integers only.
+#define JPGE_ROI_MAX_LEVEL 48
+
+// round(16 * 2^(level / 6)) for level 0 .. 48; a level above 48 counts as 48.
+JPGE_HD int jpeg_roi_scale16(int level) {
+    const uint16_t scale[JPGE_ROI_MAX_LEVEL + 1] = {16,  18,  20,  23,  25,  29,  32,  36,  40,   45,   51,   57,   64,   72,   81,   91,  102,
+                                                    114, 128, 144, 161, 181, 203, 228, 256, 287,  323,  362,  406,  456,  512,  575,  645, 724,
+                                                    813, 912, 1024, 1149, 1290, 1448, 1625, 1825, 2048, 2299, 2580, 2896, 3251, 3649, 4096};
+    return scale[level < 0 ? 0 : (level > JPGE_ROI_MAX_LEVEL ? JPGE_ROI_MAX_LEVEL : level)];
+}
+
+// The level of the block at `p`: the minimum over the cells its footprint touches - a luma or gray block covers 8 x 8
+// luma pixels, a chroma block 8 * hmax x 8 * vmax; both ends of the footprint are clamped to the frame, a cell index to
+// the grid (which may be the floored one, h / B x w / B).  B is a multiple of 8, so the footprint touches at most 2 x 2
+// cells, its corners: at most 4 bytes are read, every index clamped.
+JPGE_HD int jpeg_roi_block_level(const JpegEncGeom& g, const JpegEncPlace& p, const uint8_t* levels, int By, int Bx, int B) {
+    const int fx = p.c ? g.hmax : 1, fy = p.c ? g.vmax : 1;
+    int x0 = p.bx * 8 * fx, x1 = x0 + 8 * fx - 1, y0 = p.by * 8 * fy, y1 = y0 + 8 * fy - 1;
+    x0 = x0 > g.w - 1 ? g.w - 1 : x0;
+    x1 = x1 > g.w - 1 ? g.w - 1 : x1;
+    y0 = y0 > g.h - 1 ? g.h - 1 : y0;
+    y1 = y1 > g.h - 1 ? g.h - 1 : y1;
+    int cx0 = x0 / B, cx1 = x1 / B, cy0 = y0 / B, cy1 = y1 / B;
+    cx0 = cx0 > Bx - 1 ? Bx - 1 : cx0;
+    cx1 = cx1 > Bx - 1 ? Bx - 1 : cx1;
+    cy0 = cy0 > By - 1 ? By - 1 : cy0;
+    cy1 = cy1 > By - 1 ? By - 1 : cy1;
+    const int a = levels[(size_t)cy0 * Bx + cx0], b = levels[(size_t)cy0 * Bx + cx1];
+    const int c = levels[(size_t)cy1 * Bx + cx0], d = levels[(size_t)cy1 * Bx + cx1];
+    const int top = a < b ? a : b, bottom = c < d ? c : d, level = top < bottom ? top : bottom;
+    return level > JPGE_ROI_MAX_LEVEL ? JPGE_ROI_MAX_LEVEL : level;
+}
+
+// The quantiser of an AC coefficient of a block whose level has the scale `scale16`: 0 where the step scale16 / 16 times
+// the table's would round to 0, else jpeg_quantise.  scale16 = 16 is jpeg_quantise for every input (d = 16 * q8 and q8 is
+// a multiple of 8, so the test is "the quotient is 0").  16 * a <= 2^19 and d <= 4096 * 255 * 8 < 2^23: int32.
+JPGE_HD int jpeg_quantise_roi(int coef, int table, int scale16) {
+    const int a = coef < 0 ? -coef : coef, d = scale16 * (table << 3);
+    return 16 * a + (d >> 1) < d ? 0 : jpeg_quantise(coef, table);
+}
+
 // natural index -> zig-zag position
 JPGE_HD int jpeg_zigzag_of(int natural) {
     const uint8_t pos[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,

@@ -10,6 +10,8 @@
 //                        its column, quantises, and the zig-zag order is made by a second trip through LDS, so that a
 //                        lane stores 16 contiguous bytes.  Blocks are in MCU scan order; a dummy block is transformed as
 //                        the block whose DC it repeats and keeps the DC only.  int32 throughout.
+//                        With a map of ROI levels (elvis_jpeg_fdct_roi) an AC coefficient that the block's coarsened
+//                        step would round to zero is zeroed (jpeg_quantise_roi): one branch, uniform over the launch.
 //   jpeg_bits_kernel     a lane per block: the bit length of its code from the DC difference and the AC symbols.
 //   jpeg_scan_kernel     a workgroup per segment: exclusive prefix sum in place, kScanChunk values a step with a carry;
 //                        the total goes behind the last value.  Used for the block bit offsets and the FF counts.
@@ -41,9 +43,12 @@ constexpr int kScanChunk = 256;        // values of one step of the prefix sum
 constexpr int kStuffChunk = 1024;      // stream bytes of one workgroup of the stuffing pass: a dword a lane
 static_assert(kScanChunk == ELVIS_JPEG_SCAN_CHUNK && kStuffChunk == ELVIS_JPEG_STUFF_CHUNK, "the header names the chunks");
 
-// frames u8 [n, h, w, channels] -> coef i16 [n, blocks, 64]; grid (blocks / 32, n).
+// frames u8 [n, h, w, channels] -> coef i16 [n, blocks, 64]; grid (blocks / 32, n).  levels: null, or the ROI map u8 [n, By,
+// Bx] on a grid of B x B luma pixels, frame f's at levels + f * map_stride: the 8 lanes of a block read its level and an
+// AC coefficient goes through jpeg_quantise_roi.  The branch is the same for every lane of the launch.
 __global__ __launch_bounds__(kFdctThreads) void jpeg_fdct_kernel(const uint8_t* __restrict__ frames, JpegEncGeom g, int quality,
-                                                                 int16_t* __restrict__ coef) {
+                                                                 int16_t* __restrict__ coef, const uint8_t* __restrict__ levels, int By, int Bx,
+                                                                 int B, long long map_stride) {
     __shared__ int ws[kFdctBlocks][72];
     __shared__ __attribute__((aligned(16))) int16_t zz[kFdctBlocks][64];
     __shared__ uint16_t qt[128];
@@ -70,11 +75,21 @@ __global__ __launch_bounds__(kFdctThreads) void jpeg_fdct_kernel(const uint8_t* 
         for (int i = 0; i < 8; ++i) d[i] = ws[blk][i * 9 + lane];
         jpeg_fdct_pass<false>(d, o);
         const uint16_t* table = qt + (p.c ? 64 : 0);
+        if (levels == nullptr) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int nat = i * 8 + lane;
-            const int q = jpeg_quantise(o[i], table[nat]);
-            zz[blk][jpeg_zigzag_of(nat)] = (int16_t)((p.dummy && nat) ? 0 : q);
+            for (int i = 0; i < 8; ++i) {
+                const int nat = i * 8 + lane;
+                const int q = jpeg_quantise(o[i], table[nat]);
+                zz[blk][jpeg_zigzag_of(nat)] = (int16_t)((p.dummy && nat) ? 0 : q);
+            }
+        } else {
+            const int scale16 = jpeg_roi_scale16(jpeg_roi_block_level(g, p, levels + f * (size_t)map_stride, By, Bx, B));
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int nat = i * 8 + lane;
+                const int q = nat ? jpeg_quantise_roi(o[i], table[nat], scale16) : jpeg_quantise(o[i], table[nat]);
+                zz[blk][jpeg_zigzag_of(nat)] = (int16_t)((p.dummy && nat) ? 0 : q);
+            }
         }
     }
     __syncthreads();
@@ -383,6 +398,37 @@ int stuff_call(const char* who, const uint32_t* bits, const int64_t* word_off, c
     return ELVIS_OK;
 }
 
+// The transform: without a map (levels null, by = bx = block_size = 0) the path of elvis_jpeg_fdct.  With one, the grid
+// must be one of the two a frame has - floored, max(1, h / B) x max(1, w / B), or full, ceil(h / B) x ceil(w / B) - in
+// each axis on its own, so that no cell index the kernel clamps to lies outside the map.
+int fdct_call(const char* who, const uint8_t* frames, int16_t* coef, int n, int h, int w, int channels, int order, int quality, int sampling,
+              const uint8_t* levels, int by, int bx, int block_size, elvis_stream_t stream) {
+    JpegEncGeom g;
+    if (int rc = check_shape(who, n, h, w, channels, sampling, g)) return rc;
+    ELVIS_REQUIRE(order == 0 || order == 1, "%s: order must be 0 (rgb) or 1 (bgr), got %d", who, order);
+    ELVIS_REQUIRE(quality >= 1 && quality <= 100, "%s: quality must be in [1, 100], got %d", who, quality);
+    if (levels == nullptr) {
+        ELVIS_REQUIRE(by == 0 && bx == 0 && block_size == 0, "%s: null map with by=%d bx=%d block_size=%d (all 0 without a map)", who, by, bx, block_size);
+    } else {
+        ELVIS_REQUIRE(block_size >= 8 && block_size % 8 == 0, "%s: block_size must be a positive multiple of 8, got %d", who, block_size);
+        ELVIS_REQUIRE(by == std::max(1, h / block_size) || by == cdiv(h, block_size),
+                      "%s: a map of %d rows is not the grid of a frame of %d rows in blocks of %d (%d or %d)", who, by, h, block_size,
+                      std::max(1, h / block_size), cdiv(h, block_size));
+        ELVIS_REQUIRE(bx == std::max(1, w / block_size) || bx == cdiv(w, block_size),
+                      "%s: a map of %d columns is not the grid of a frame of %d columns in blocks of %d (%d or %d)", who, bx, w, block_size,
+                      std::max(1, w / block_size), cdiv(w, block_size));
+    }
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(frames && coef, "%s: null pointer", who);
+    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0, "%s: coef must be 16-byte aligned", who);
+    g.bgr = order;
+    hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)cdiv(g.blocks, kFdctBlocks), (unsigned)n), dim3(kFdctThreads), 0, (hipStream_t)stream, frames, g,
+                       quality, coef, levels, by, bx, block_size, (long long)by * bx);
+    ELVIS_CHECK_LAUNCH(who);
+    elvis_note_launch("jpeg_fdct_kernel");
+    return ELVIS_OK;
+}
+
 }  // namespace
 
 extern "C" int elvis_jpeg_frame_blocks(int h, int w, int channels, int sampling) {
@@ -393,19 +439,12 @@ extern "C" int elvis_jpeg_frame_blocks(int h, int w, int channels, int sampling)
 
 extern "C" int elvis_jpeg_fdct(const uint8_t* frames, int16_t* coef, int n, int h, int w, int channels, int order, int quality, int sampling,
                                elvis_stream_t stream) {
-    JpegEncGeom g;
-    if (int rc = check_shape("elvis_jpeg_fdct", n, h, w, channels, sampling, g)) return rc;
-    ELVIS_REQUIRE(order == 0 || order == 1, "elvis_jpeg_fdct: order must be 0 (rgb) or 1 (bgr), got %d", order);
-    ELVIS_REQUIRE(quality >= 1 && quality <= 100, "elvis_jpeg_fdct: quality must be in [1, 100], got %d", quality);
-    if (n == 0) return ELVIS_OK;
-    ELVIS_REQUIRE(frames && coef, "elvis_jpeg_fdct: null pointer");
-    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0, "elvis_jpeg_fdct: coef must be 16-byte aligned");
-    g.bgr = order;
-    hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)cdiv(g.blocks, kFdctBlocks), (unsigned)n), dim3(kFdctThreads), 0, (hipStream_t)stream, frames, g,
-                       quality, coef);
-    ELVIS_CHECK_LAUNCH("elvis_jpeg_fdct");
-    elvis_note_launch("jpeg_fdct_kernel");
-    return ELVIS_OK;
+    return fdct_call("elvis_jpeg_fdct", frames, coef, n, h, w, channels, order, quality, sampling, nullptr, 0, 0, 0, stream);
+}
+
+extern "C" int elvis_jpeg_fdct_roi(const uint8_t* frames, int16_t* coef, int n, int h, int w, int channels, int order, int quality, int sampling,
+                                   const uint8_t* levels, int by, int bx, int block_size, elvis_stream_t stream) {
+    return fdct_call("elvis_jpeg_fdct_roi", frames, coef, n, h, w, channels, order, quality, sampling, levels, by, bx, block_size, stream);
 }
 
 extern "C" int elvis_jpeg_segments(int h, int w, int channels, int sampling, int restart_mcus) {

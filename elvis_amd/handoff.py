@@ -479,3 +479,40 @@ def create_svtav1_roi_file(importance_scores: List[np.ndarray], roi_path: str, b
         for index, importance in enumerate(importance_scores):
             offsets = svtav1_delta_qp(importance, base_crf, qp_range, width, height).flatten()
             f.write(f"{index} " + " ".join(map(str, offsets)) + "\n")
+
+
+# ----------------------------------------------------------------------------- the ROI approach with the project's own codec
+def roi_levels_from_importance(importance_scores, qp_range: int = 15, base_qp: int = 25) -> np.ndarray:
+    """Importance scores ([By,Bx] per frame, 0..1, as `calculate_importance_scores` gives them) to the levels the device
+    JPEG writer's `roi_levels=` takes: uint8 [n,By,Bx].  HOST numpy.  Per frame `kvazaar_delta_qp(importance, base_qp,
+    qp_range)` - the offsets `create_kvazaar_roi_file` would write - less the fixed floor max(-min(qp_range, 14),
+    -base_qp), the offset of importance 1: importance 1 is level 0, the file's own quality, and every QP above it is a
+    level.  The floor is fixed, not the clip's minimum, so a frame's levels do not depend on what else is in the clip.
+    With the reference's Kvazaar default, base_qp = 48, the offsets are clipped at 51 - 48 = +3 and the levels end at 3
+    plus the floor's 14; the default here, 25, leaves the whole +-14.  elvis.py's removability maps (high: removable)
+    go in as 1 - removability."""
+    floor = max(-min(int(qp_range), KVAZAAR_DELTA_LIMIT), -int(base_qp))
+    from .jpeg_write import jpeg_roi_levels
+    frames = [jpeg_roi_levels(kvazaar_delta_qp(importance, base_qp, qp_range), floor) for importance in importance_scores]
+    if not frames:
+        return np.zeros((0, 1, 1), np.uint8)
+    return np.stack(frames, axis=0)
+
+
+def encode_with_roi_device(frames_d: torch.Tensor, importance_scores, block_size: int, *, quality: int = 95, target_bytes: Optional[int] = None,
+                           qp_range: int = 15, base_qp: int = 25, subsampling: str = "420", order: str = "bgr", restart_rows: int = 1):
+    """The reference's ROI approach end to end on a resident clip, with the project's intra codec in the encoder's place
+    (`encode_with_roi`, elvis.py:2013-2118; `create_kvazaar_roi_file` + `encode_kvazaar`, utils.py:1026-1053): the
+    importance scores become levels (`roi_levels_from_importance`), with `target_bytes` (the clip's budget, bitrate * n /
+    fps / 8) `jpeg_write.jpeg_quality_for_bytes` finds the quality inside 1..`quality` whose files fit it, and
+    `jpeg_write.jpeg_roundtrip_device` encodes and decodes at that quality with the map.  `block_size`: the luma pixels
+    of a cell of the importance grid, a multiple of 8.  Returns (the decoded resident clip, the bytes of every frame's
+    file, int64 [n]; the quality used; the levels, uint8 [n,By,Bx]).  The files are baseline JPEG with a dead zone per
+    block: nothing is claimed about what x265, Kvazaar or SVT-AV1 would make of the same maps."""
+    from . import jpeg_write
+    levels = roi_levels_from_importance(importance_scores, qp_range, base_qp)
+    kw = dict(restart_rows=restart_rows, roi_levels=levels, roi_block_size=block_size)
+    if target_bytes is not None:
+        quality = jpeg_write.jpeg_quality_for_bytes(frames_d, target_bytes, quality, subsampling, order, **kw)[0]
+    decoded, nbytes = jpeg_write.jpeg_roundtrip_device(frames_d, quality, subsampling, order, **kw)
+    return decoded, nbytes, quality, levels

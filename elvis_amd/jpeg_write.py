@@ -10,6 +10,10 @@ path for those suffixes, the writer half of jpeg.py:
   jpeg_quant_tables(quality)                   host: the two quantisation tables
   jpeg_file_header(width, height, ...)         host: everything in front of the entropy-coded bytes
   jpeg_restart_interval(width, height, ...)    host: the restart interval in MCUs that `restart_rows=` / `restart_mcus=` ask for
+  jpeg_encoded_sizes_device(frames_d, quality) the length of every file `encode_jpeg_device` would return, without producing it
+  jpeg_quality_for_bytes(frames_d, target)     the bisect over the quality for a byte budget of the whole clip
+  jpeg_roundtrip_at_bytes_device(frames_d, t)  that search, then the round trip at the quality found
+  jpeg_roi_levels(delta_qp), jpeg_roi_scale16  host: delta QPs to the levels of `roi_levels=`, and the table behind a level
 
 Colour conversion, edge replication, chroma downsampling, the forward DCT, the quantiser, the Huffman coding, the bit
 packing and the byte stuffing run as HIP kernels; the host plans the layout from two small downloads (a frame's bit
@@ -34,6 +38,21 @@ the transform they work per (frame, interval) instead of per frame, an interval 
 The bit-for-bit claim extends to it: against PIL with `restart_marker_rows=` / `restart_marker_blocks=` the DRI
 segment's place and content and the entropy-coded bytes, markers included, are equal; tests/_jpeg_restart_ref.py
 states the rule.
+
+Per-block rate allocation.  `roi_levels=` (uint8 [n, By, Bx], a level 0..48 per cell of `roi_block_size` x `roi_block_size`
+luma pixels) on every form above decides per DCT block which coefficients survive.  A level is in HEVC QP units - the
+step doubles every 6 - and comes from the same importance scores the reference turns into ROI files for its encoders
+(`handoff.roi_levels_from_importance`).  It is A DEAD ZONE, NOT A RE-QUANTISATION: an AC coefficient that the file's
+quantiser coarsened by the block's level would round to zero is zeroed, every other coefficient keeps the file's own
+quantiser, DC is never touched, and the file keeps the tables of its header - baseline JPEG that any decoder reads.
+(Quantising with a coarser step m * Q and writing k * m does not work with the Annex K Huffman tables: every surviving
+coefficient pays log2 m more magnitude bits, which is what the coarser step saved.)  With scale16(L) = round(16 *
+2^(L / 6)), a table of 49 integers, a = |c| of the FDCT's output and d = scale16(L) * (Q << 3), the coefficient is zeroed
+when 16 * a + (d >> 1) < d; level 0 is the writer without a map for every input.  A block's level is the minimum over
+the cells its footprint touches (8 x 8 luma pixels for a luma block, 8 hmax x 8 vmax for a chroma block, clamped to the
+frame; cell indices clamped to the grid, which is the floored h // B x w // B or the full one).  Bytes are not monotone
+in the level: a zeroed coefficient can turn two short symbols into a longer run.  tests/_jpeg_roi_ref.py states the
+rule.  `jpeg_quality_for_bytes` finds the quality for a byte budget from the pack call's sizes alone.
 """
 from __future__ import annotations
 
@@ -58,6 +77,10 @@ MAX_BLOCKS = 1 << 20            # blocks of a frame
 MAX_FRAMES = 65535              # frames of one launch
 MAX_SEGMENTS = 1 << 24          # ELVIS_JPEG_MAX_SEGMENTS: (frame, restart interval) pairs of one launch
 UPLOAD_CHUNK_BYTES = 32 << 20
+JPEG_ROI_MAX_LEVEL = 48         # JPGE_ROI_MAX_LEVEL: levels are HEVC QP units, the step doubles every 6
+# round(16 * 2^(L / 6)) for L = 0..48, as csrc/jpeg_encode.h `jpeg_roi_scale16` has it
+ROI_SCALE16 = (16, 18, 20, 23, 25, 29, 32, 36, 40, 45, 51, 57, 64, 72, 81, 91, 102, 114, 128, 144, 161, 181, 203, 228, 256, 287, 323, 362, 406,
+               456, 512, 575, 645, 724, 813, 912, 1024, 1149, 1290, 1448, 1625, 1825, 2048, 2299, 2580, 2896, 3251, 3649, 4096)
 # ITU-T T.81 Annex K.1, K.2: the quantisation tables in natural order
 BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87,
              80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92,
@@ -127,6 +150,61 @@ def jpeg_restart_interval(width: int, height: int, channels: int = 3, subsamplin
         return mcus
     hmax = _FACTORS[subsampling][0] if channels == 3 else 1
     return min(rows * -(-int(width) // (8 * hmax)), 65535)
+
+
+def jpeg_roi_scale16(level: int) -> int:
+    """Host only: 16 times the factor by which ROI level `level` (0..48, HEVC QP units) coarsens the step that decides
+    whether a coefficient survives: round(16 * 2^(level / 6)), from the table the kernel has."""
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= int(level) <= JPEG_ROI_MAX_LEVEL:
+        raise ValueError(f"jpeg_roi_scale16: level must be an integer in 0..{JPEG_ROI_MAX_LEVEL}, got {level!r}")
+    return ROI_SCALE16[int(level)]
+
+
+def jpeg_roi_levels(delta_qp, floor=None) -> np.ndarray:
+    """Host only: delta QPs (an integer array of any shape, as `handoff.kvazaar_delta_qp` gives them) to the levels
+    `roi_levels=` takes: uint8 clip(delta_qp - floor, 0, 48).  `floor` is the delta QP that stands for the file's own
+    quality, by default the array's minimum; a float dtype or a floor above the minimum is a ValueError."""
+    a = np.asarray(delta_qp)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"jpeg_roi_levels: delta_qp must be an integer array, got {a.dtype}")
+    low = int(a.min()) if a.size else 0
+    if floor is None:
+        floor = low
+    if isinstance(floor, bool) or not isinstance(floor, (int, np.integer)):
+        raise ValueError(f"jpeg_roi_levels: floor must be an integer, got {floor!r}")
+    if a.size and int(floor) > low:
+        raise ValueError(f"jpeg_roi_levels: floor {int(floor)} is above the smallest delta QP, {low}")
+    return np.clip(a.astype(np.int64) - int(floor), 0, JPEG_ROI_MAX_LEVEL).astype(np.uint8)
+
+
+def _check_roi(roi_levels, roi_block_size, n: int, h: int, w: int, who: str):
+    """The checks of `roi_levels=` / `roi_block_size=` that need no device: None without a map, else (the map - a host
+    array, or a tensor that is resident - and its By, Bx, B)."""
+    b = roi_block_size
+    if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or int(b) < 0:
+        raise ValueError(f"{who}: roi_block_size must be a non-negative integer, got {b!r}")
+    b = int(b)
+    if roi_levels is None:
+        if b:
+            raise ValueError(f"{who}: roi_block_size={b} without roi_levels")
+        return None
+    if isinstance(roi_levels, torch.Tensor):
+        levels = roi_levels if roi_levels.is_cuda else roi_levels.numpy()
+    else:
+        levels = np.asarray(roi_levels)
+    if levels.dtype != (torch.uint8 if isinstance(levels, torch.Tensor) else np.uint8):
+        raise ValueError(f"{who}: roi_levels must be uint8, got {levels.dtype}")
+    if b < 8 or b % 8:
+        raise ValueError(f"{who}: roi_block_size must be a positive multiple of 8, got {b}")
+    if levels.ndim != 3 or int(levels.shape[0]) != n:
+        raise ValueError(f"{who}: roi_levels must be [n, By, Bx] with n = {n}, got {tuple(levels.shape)}")
+    by, bx = int(levels.shape[1]), int(levels.shape[2])
+    if by not in (max(1, h // b), -(-h // b)) or bx not in (max(1, w // b), -(-w // b)):
+        raise ValueError(f"{who}: roi_levels of {by} x {bx} cells are not the grid of a {h} x {w} frame in blocks of {b}: "
+                         f"{max(1, h // b)} or {-(-h // b)} rows, {max(1, w // b)} or {-(-w // b)} columns")
+    if n and int(levels.max()) > JPEG_ROI_MAX_LEVEL:
+        raise ValueError(f"{who}: roi_levels holds {int(levels.max())}, above {JPEG_ROI_MAX_LEVEL}")
+    return levels, by, bx, b
 
 
 def jpeg_quant_tables(quality: int = 95) -> Tuple[np.ndarray, np.ndarray]:
@@ -201,8 +279,9 @@ def jpeg_file_header(width: int, height: int, channels: int = 3, quality: int = 
 
 
 # ----------------------------------------------------------------------------- the device forms
-def _check_clip(frames_d, order, quality, subsampling, who: str):
-    """Every argument check, before the library is touched: (n, h, w, c, order code, quality, sampling code)."""
+def _check_clip(frames_d, order, quality, subsampling, who: str, roi_levels=None, roi_block_size=0):
+    """Every argument check, before the library is touched: (n, h, w, c, order code, quality, sampling code, the ROI map
+    as `_check_roi` gives it)."""
     if order not in ("bgr", "rgb"):
         raise ValueError(f"{who}: order must be 'bgr' or 'rgb', got {order!r}")
     q = _check_quality(quality, who)
@@ -221,11 +300,14 @@ def _check_clip(frames_d, order, quality, subsampling, who: str):
         raise ValueError(f"{who}: a {h} x {w} frame is too large (sides up to 65535, 3 * (W/8 + 1) * (H/8 + 1) up to 2^20)")
     if n > MAX_FRAMES:
         raise ValueError(f"{who}: {n} frames in one launch (at most {MAX_FRAMES}); encode the clip in parts")
+    roi = _check_roi(roi_levels, roi_block_size, n, h, w, who)
     if not frames_d.is_cuda:
         raise ValueError(f"{who}: frames must be resident on the device (got a '{frames_d.device}' tensor)")
     if not frames_d.is_contiguous():
         raise ValueError(f"{who}: frames must be contiguous")
-    return n, h, w, c, int(order == "bgr"), q, scode
+    if roi is not None and isinstance(roi[0], torch.Tensor) and (roi[0].device != frames_d.device or not roi[0].is_contiguous()):
+        raise ValueError(f"{who}: a resident roi_levels must be contiguous and on the clip's device, {frames_d.device} (got '{roi[0].device}')")
+    return n, h, w, c, int(order == "bgr"), q, scode, roi
 
 
 def _check_segments(n: int, h: int, w: int, c: int, subsampling: str, ri: int, who: str) -> Tuple[int, int]:
@@ -250,7 +332,8 @@ def _guarded(nbytes: int, guard: int, dev, fill: int = 0):
     return buf, buf[guard:guard + nbytes]
 
 
-def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, guard: int = 0, fill: int = 0, restart=(0, 0)):
+def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, guard: int = 0, fill: int = 0, restart=(0, 0), roi_levels=None,
+                 roi_block_size: int = 0, sizes_only: bool = False):
     """The four calls and the two small downloads between them.  Returns None for an empty clip, else a dict: `out_buf`
     (the finished scans on the device with `guard` bytes of 0xA5 on either side), `out_off` (int64 [n + 1], frame f's scan
     is bytes out_off[f] .. out_off[f + 1] of the payload), `header`, and the work buffers with their guards (`coef_buf`,
@@ -263,9 +346,14 @@ def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, 
     span of whole words for every segment in words_buf (no two segments share a word, however short they are), ffc u32
     [n * segments, chunks + 1] with `chunks` those of the longest segment, sizes u32 [n * segments] (each with the 2
     bytes of its RSTm or EOI).  A frame's finished scan is its segments back to back, so `out_off` stays per frame; the
-    dict gains `restart_interval`, `segments`, `segment_blocks` and `seg_off` (int64 [n * segments + 1])."""
+    dict gains `restart_interval`, `segments`, `segment_blocks` and `seg_off` (int64 [n * segments + 1]).
+
+    `roi_levels` / `roi_block_size`: the map of the module docstring; a host array is uploaded, and the transform runs
+    through `elvis_jpeg_fdct_roi`.  `sizes_only=True` stops behind the second download: no stuffing pass, no output
+    buffer; the dict has `file_bytes` (int64 [n], header and markers included) instead of `out_buf`, `out` and
+    `out_off`."""
     rows, mcus = _check_restart(*restart, who)
-    n, h, w, c, ocode, q, scode = _check_clip(frames_d, order, quality, subsampling, who)
+    n, h, w, c, ocode, q, scode, roi = _check_clip(frames_d, order, quality, subsampling, who, roi_levels, roi_block_size)
     ri = jpeg_restart_interval(w, h, c, subsampling, rows, mcus)
     segs, mcus_of_frame = _check_segments(n, h, w, c, subsampling, ri, who)
     if n == 0:
@@ -291,7 +379,12 @@ def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, 
         ehuff_d = torch.from_numpy(encode_tables().view(np.int32)).to(dev)
         coef_buf, coef_d = _guarded(n * blocks * 128, guard, dev, fill)
         bits_buf, bits_d = _guarded(nseg * (segb + 1) * 4, guard, dev, fill)
-        check(lib().elvis_jpeg_fdct(ptr(frames_d), ptr(coef_d), n, h, w, c, ocode, q, scode, s), dev)
+        if roi is None:
+            check(lib().elvis_jpeg_fdct(ptr(frames_d), ptr(coef_d), n, h, w, c, ocode, q, scode, s), dev)
+        else:
+            levels, by, bx, b = roi
+            levels_d = levels if isinstance(levels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(levels)).to(dev)
+            check(lib().elvis_jpeg_fdct_roi(ptr(frames_d), ptr(coef_d), n, h, w, c, ocode, q, scode, ptr(levels_d), by, bx, b, s), dev)
         check(bits_fn(ptr(coef_d), ptr(ehuff_d), ptr(bits_d), n, h, w, c, scode, *tail, s), dev)
         # the first synchronisation of a clip: every segment's bit count (a frame is one segment without an interval)
         total_bits = bits_d.view(torch.int32).view(nseg, segb + 1)[:, segb].cpu().numpy().view(np.uint32).astype(np.int64)
@@ -308,6 +401,12 @@ def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, 
         # the second: every segment's byte count with the stuffed zeros and its marker or EOI
         sizes = sizes_d.cpu().numpy().view(np.uint32).astype(np.int64)
         seg_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        if sizes_only:
+            got = {"file_bytes": len(header) + np.diff(seg_off[::segs]), "header": header, "coef_buf": coef_buf, "bits_buf": bits_buf,
+                   "words_buf": words_buf, "ffc_buf": ffc_buf, "sizes_buf": sizes_buf, "blocks": blocks, "chunks": chunks}
+            if ri:
+                got.update(restart_interval=ri, segments=segs, segment_blocks=segb, seg_off=seg_off)
+            return got
         total = int(seg_off[-1])
         seg_off_d = torch.from_numpy(seg_off).to(dev)
         out_buf, out_d = _guarded(total, guard, dev, fill)
@@ -320,8 +419,8 @@ def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, 
     return got
 
 
-def _encode_to_host(frames_d, order, quality, subsampling, who: str, restart=(0, 0)) -> List[bytes]:
-    got = _encode_clip(frames_d, order, quality, subsampling, who, restart=restart)
+def _encode_to_host(frames_d, order, quality, subsampling, who: str, restart=(0, 0), roi_levels=None, roi_block_size=0) -> List[bytes]:
+    got = _encode_clip(frames_d, order, quality, subsampling, who, restart=restart, roi_levels=roi_levels, roi_block_size=roi_block_size)
     if got is None:
         return []
     host = got["out"].cpu().numpy()
@@ -330,36 +429,42 @@ def _encode_to_host(frames_d, order, quality, subsampling, who: str, restart=(0,
 
 
 def encode_jpeg_device(frames_d: torch.Tensor, order: str = "bgr", quality: int = 95, subsampling: str = "420", *, restart_rows: int = 0,
-                       restart_mcus: int = 0) -> List[bytes]:
+                       restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0) -> List[bytes]:
     """One complete baseline JPEG file per frame of a resident contiguous uint8 clip [n,H,W,3], [n,H,W,1] or [n,H,W].
     `order` is the channel order of a 3-channel clip ("bgr", what `save_frame` takes, or "rgb"); `quality` 1..100 and
     `subsampling` "444" | "422" | "420" are libjpeg's; quality 95 and 4:2:0, the defaults, are what `cv2.imwrite` uses.
     A gray clip is one component and `subsampling` is ignored.  `restart_rows=r` (an interval of r MCU rows, at most
     65535 MCUs) or `restart_mcus=k` (an interval of k MCUs, 1..65535), one of them, writes restart intervals: DRI in the
     header, RSTm between the intervals; the default is none.  Turn it on where the device reader will read the files.
-    A frame's bytes do not depend on the frames it is encoded with.  ValueError before any launch for a bad argument;
-    an empty clip gives []."""
-    return _encode_to_host(frames_d, order, quality, subsampling, "encode_jpeg_device", (restart_rows, restart_mcus))
+    `roi_levels=` (uint8 [n, By, Bx], a numpy array, which is uploaded, or a contiguous tensor on the clip's device; a
+    level 0..48 per cell of `roi_block_size` x `roi_block_size` luma pixels, a multiple of 8; By is H // B or ceil(H / B),
+    at least 1, Bx likewise) zeroes the AC coefficients a step coarsened by the block's level would round to zero - the
+    module docstring has the rule; None writes what the writer always wrote, and so does a map of zeros.
+    A frame's bytes depend on that frame and its own map only, not on the frames it is encoded with.  ValueError before
+    any launch for a bad argument; an empty clip gives []."""
+    return _encode_to_host(frames_d, order, quality, subsampling, "encode_jpeg_device", (restart_rows, restart_mcus), roi_levels, roi_block_size)
 
 
 def save_jpeg_frames_device(frames_d: torch.Tensor, paths: Sequence, order: str = "bgr", quality: int = 95, subsampling: str = "420", *,
-                            restart_rows: int = 0, restart_mcus: int = 0) -> None:
+                            restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0) -> None:
     """`encode_jpeg_device`, and frame i written to paths[i]; directories are created as `save_frame` does."""
     paths = list(paths)
     if not isinstance(frames_d, torch.Tensor) or frames_d.dim() < 1 or len(paths) != frames_d.shape[0]:
         raise ValueError(f"save_jpeg_frames_device: {len(paths)} path(s) for the clip {tuple(getattr(frames_d, 'shape', ()))}")
-    for path, data in zip(paths, _encode_to_host(frames_d, order, quality, subsampling, "save_jpeg_frames_device", (restart_rows, restart_mcus))):
+    for path, data in zip(paths, _encode_to_host(frames_d, order, quality, subsampling, "save_jpeg_frames_device", (restart_rows, restart_mcus),
+                                                 roi_levels, roi_block_size)):
         os.makedirs(os.path.dirname(os.fspath(path)) or ".", exist_ok=True)
         with open(path, "wb") as f:
             f.write(data)
 
 
 def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=None, order: str = "bgr", quality: int = 95,
-                     subsampling: str = "420", restart_rows: int = 0, restart_mcus: int = 0) -> None:
+                     subsampling: str = "420", restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0) -> None:
     """Host frames - uint8 (H,W,3), (H,W,1) or (H,W) arrays, a list or one [n,...] array - written as JPEGs to `paths`
     through the device.  Uploaded and encoded `chunk_frames` frames at a time, by default as many as make 32 MB (5 at
     1080p); a run of equal shapes is one clip.  The files do not depend on the chunk size.  `restart_rows` / `restart_mcus`:
-    as `encode_jpeg_device` takes them."""
+    as `encode_jpeg_device` takes them.  `roi_levels` / `roi_block_size`: the same, [len(frames), By, Bx] for frames of
+    one shape; every chunk takes its frames' part of the map."""
     who = "save_jpeg_frames"
     paths = list(paths)
     if len(frames) != len(paths):
@@ -375,6 +480,12 @@ def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=N
     for a in arrays:
         if a.dtype != np.uint8 or a.ndim not in (2, 3):
             raise ValueError(f"{who}: frames are uint8 (H,W,3), (H,W,1) or (H,W) arrays, got {a.dtype} {a.shape}")
+    if roi_levels is not None or roi_block_size:
+        if len({a.shape for a in arrays}) > 1:
+            raise ValueError(f"{who}: roi_levels needs frames of one shape")
+        if arrays:
+            roi = _check_roi(roi_levels, roi_block_size, len(arrays), int(arrays[0].shape[0]), int(arrays[0].shape[1]), who)
+            roi_levels = None if roi is None else roi[0]
     dev = L.resolve_device(device)
     at = 0
     with torch.cuda.device(dev):
@@ -385,20 +496,75 @@ def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=N
             while end < len(arrays) and end - at < step and arrays[end].shape == shape:
                 end += 1
             clip = torch.from_numpy(np.ascontiguousarray(np.stack(arrays[at:end], axis=0))).to(dev)
-            save_jpeg_frames_device(clip, paths[at:end], order, quality, subsampling, restart_rows=restart_rows, restart_mcus=restart_mcus)
+            roi_kw = {} if roi_levels is None else {"roi_levels": roi_levels[at:end], "roi_block_size": roi_block_size}
+            save_jpeg_frames_device(clip, paths[at:end], order, quality, subsampling, restart_rows=restart_rows, restart_mcus=restart_mcus, **roi_kw)
             at = end
 
 
 def jpeg_roundtrip_device(frames_d: torch.Tensor, quality: int = 95, subsampling: str = "420", order: str = "bgr", *, restart_rows: int = 0,
-                          restart_mcus: int = 0):
+                          restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0):
     """An intra codec in the loop: `encode_jpeg_device` at `quality`, then `jpeg.decode_jpeg_device` of those files.
     Returns (the decoded resident clip, uint8 [n,H,W,C] in the clip's own channel count and `order`; the bytes of every
     frame's file, int64 [n]) - the pixels a client would see and the rate they cost.  `restart_rows=1` gives the reader a
-    segment per MCU row to decode side by side: the same pixels, sooner, for a few more bytes."""
+    segment per MCU row to decode side by side: the same pixels, sooner, for a few more bytes.  `roi_levels` /
+    `roi_block_size`: as `encode_jpeg_device` takes them."""
     from .jpeg import decode_jpeg_device
-    files = _encode_to_host(frames_d, order, quality, subsampling, "jpeg_roundtrip_device", (restart_rows, restart_mcus))
+    files = _encode_to_host(frames_d, order, quality, subsampling, "jpeg_roundtrip_device", (restart_rows, restart_mcus), roi_levels, roi_block_size)
     if not files:
         raise ValueError("jpeg_roundtrip_device: no frames")
     c = int(frames_d.shape[3]) if frames_d.dim() == 4 else 1
     decoded = decode_jpeg_device(files, frames_d.device, order, c)
     return decoded, np.asarray([len(f) for f in files], dtype=np.int64)
+
+
+def jpeg_encoded_sizes_device(frames_d: torch.Tensor, quality: int = 95, subsampling: str = "420", order: str = "bgr", *, restart_rows: int = 0,
+                              restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0) -> np.ndarray:
+    """int64 [n]: the length of every file `encode_jpeg_device` would return with the same arguments - header, entropy-coded
+    bytes with their stuffed zeros, restart markers and EOI - without producing the files: the transform, the bit lengths
+    and the pack call run, and the second small download, the pack call's sizes, ends it.  No stuffing pass, no output
+    buffer, no download of a scan.  An empty clip gives an empty array."""
+    got = _encode_clip(frames_d, order, quality, subsampling, "jpeg_encoded_sizes_device", restart=(restart_rows, restart_mcus),
+                       roi_levels=roi_levels, roi_block_size=roi_block_size, sizes_only=True)
+    return np.zeros(0, np.int64) if got is None else got["file_bytes"].astype(np.int64)
+
+
+def jpeg_quality_for_bytes(frames_d: torch.Tensor, target_bytes: int, quality_max: int = 100, subsampling: str = "420", order: str = "bgr", *,
+                           restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0):
+    """The quality whose files fit `target_bytes`, the budget of the whole clip (bitrate * n / fps / 8): (quality, the
+    sizes at that quality as `jpeg_encoded_sizes_device` gives them, int64 [n]; whether they fit).  The search: quality
+    1 is probed, and if the clip's bytes exceed the target the answer is (1, sizes, False); else lo = 1, hi =
+    `quality_max`, and while lo < hi, mid = (lo + hi + 1) // 2 is probed: lo = mid where it fits, hi = mid - 1 where it
+    does not; (lo, sizes(lo), True).  At most 8 probes, each a `jpeg_encoded_sizes_device`.  The quality returned always
+    fits.  Sizes are not strictly monotone in the quality, so it need not be the largest one that does."""
+    who = "jpeg_quality_for_bytes"
+    if isinstance(target_bytes, bool) or not isinstance(target_bytes, (int, np.integer)) or int(target_bytes) < 0:
+        raise ValueError(f"{who}: target_bytes must be a non-negative integer, got {target_bytes!r}")
+    top = _check_quality(quality_max, who)
+    kw = dict(restart_rows=restart_rows, restart_mcus=restart_mcus, roi_levels=roi_levels, roi_block_size=roi_block_size)
+    probed = {}
+
+    def fits(q: int) -> bool:
+        probed[q] = jpeg_encoded_sizes_device(frames_d, q, subsampling, order, **kw)
+        return int(probed[q].sum()) <= int(target_bytes)
+
+    if not fits(1):
+        return 1, probed[1], False
+    lo, hi = 1, top
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if fits(mid):
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo, probed[lo], True
+
+
+def jpeg_roundtrip_at_bytes_device(frames_d: torch.Tensor, target_bytes: int, quality_max: int = 95, subsampling: str = "420", order: str = "bgr", *,
+                                   restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0):
+    """An intra codec at a rate: `jpeg_quality_for_bytes` inside 1..`quality_max`, then `jpeg_roundtrip_device` at the
+    quality found (quality 1 where even that does not fit).  Returns (the decoded resident clip, the bytes of every
+    frame's file, int64 [n]; the quality; whether the files fit `target_bytes`)."""
+    kw = dict(restart_rows=restart_rows, restart_mcus=restart_mcus, roi_levels=roi_levels, roi_block_size=roi_block_size)
+    quality, _, fits = jpeg_quality_for_bytes(frames_d, target_bytes, quality_max, subsampling, order, **kw)
+    decoded, sizes = jpeg_roundtrip_device(frames_d, quality, subsampling, order, **kw)
+    return decoded, sizes, quality, fits

@@ -1005,13 +1005,31 @@ int elvis_jpeg_colour(const uint8_t* planes, int64_t stride_blocks, const int32_
  *      1) * segs]), each with its marker, the last with EOI.
  * restart_mcus = 0 is calls 2 - 4 themselves: the same code, the same layouts, the same bytes.  The file's DRI segment
  * is the caller's.  ELVIS_E_INVALID before any launch for what the calls above refuse, restart_mcus outside [0, 65535]
- * and n * segs above ELVIS_JPEG_MAX_SEGMENTS (encode the clip in parts). */
+ * and n * segs above ELVIS_JPEG_MAX_SEGMENTS (encode the clip in parts).
+ *
+ * Per-block rate allocation (elvis_jpeg_fdct_roi): call 1 with a map of coarsening levels, in the place of the ROI files
+ * the reference hands its encoders (create_kvazaar_roi_file, utils.py:1026-1053; encode_with_roi's x265 qpfile,
+ * elvis.py:2013-2118).  levels u8 [n, by, bx] on a grid of block_size x block_size luma pixels, a level 0 .. 48 (above:
+ * 48) in HEVC QP units: the step doubles every 6, scale16(L) = round(16 * 2^(L / 6)), a table of 49 constants.  A dead
+ * zone, not a coarser step: for an AC coefficient c (the FDCT's output, scaled by 8) and its table entry Q, a = |c|, d =
+ * scale16(L) * (Q << 3), the result is 0 when 16 * a + (d >> 1) < d - the quantiser of the step coarsened by L would round
+ * it to 0 - and the quantiser of call 1 otherwise; DC is never touched, and level 0 is call 1 for every input.  The
+ * file keeps the tables of its header and stays baseline JPEG.  The level of a DCT block is the minimum over the cells
+ * its footprint touches, then min(., 48): the footprint is 8 x 8 luma pixels for a luma or gray block and 8 hmax x 8
+ * vmax for a chroma block, both ends clamped to the frame; a cell index is min(p / block_size, bx - 1) and min(p /
+ * block_size, by - 1).  by is max(1, h / block_size) or ceil(h / block_size), bx likewise: the reference's floored grids
+ * and full grids.  A dummy block keeps its DC only, as in call 1.  levels = NULL with by = bx = block_size = 0 is call 1
+ * itself.  Calls 2 - 4 and their restart forms follow unchanged.  ELVIS_E_INVALID before any launch for what call 1
+ * refuses, a block_size that is not a positive multiple of 8, a by or bx that is neither of its two values, and a null
+ * map with a non-zero by, bx or block_size. */
 #define ELVIS_JPEG_SCAN_CHUNK 256
 #define ELVIS_JPEG_STUFF_CHUNK 1024
 #define ELVIS_JPEG_MAX_SEGMENTS 16777216
 int elvis_jpeg_frame_blocks(int h, int w, int channels, int sampling);
 int elvis_jpeg_fdct(const uint8_t* frames, int16_t* coef, int n, int h, int w, int channels, int order, int quality, int sampling,
                     elvis_stream_t stream);
+int elvis_jpeg_fdct_roi(const uint8_t* frames, int16_t* coef, int n, int h, int w, int channels, int order, int quality, int sampling,
+                        const uint8_t* levels, int by, int bx, int block_size, elvis_stream_t stream);
 int elvis_jpeg_bits(const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
                     elvis_stream_t stream);
 int elvis_jpeg_pack(const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,

@@ -1,10 +1,12 @@
 """The device JPEG writer (csrc/jpeg_write.hip, elvis_amd/jpeg_write.py) on a resident 1080p clip.
 
     python tools/jpeg_write_bench.py [--frames 30] [--reps 10] [--height 1080] [--width 1920] [--out DIR]
-                                     [--restart-rows R | --restart-mcus K] [--measure encode,roundtrip,writers,sizes]
+                                     [--restart-rows R | --restart-mcus K] [--roi-levels none|zero|random] [--roi-block-size B]
+                                     [--measure encode,roundtrip,writers,sizes,search,roi_table]
 
 The clip is `synth.synth_clip`.  `--restart-rows` / `--restart-mcus` give the device writer a restart interval (PIL's
-files of the comparison get the same one).  `ELVIS_AMD_LIB` names another build of the library, for a comparison in one
+files of the comparison get the same one).  `--roi-levels zero|random` gives the `encode` and `search` measurements a map of
+ROI levels on a grid of `--roi-block-size` (16) luma pixels: all 0, or uniform in 0..48.  `ELVIS_AMD_LIB` names another build of the library, for a comparison in one
 session.  Prints one JSON line per measurement:
 
   encode      device time between events on the stream around `jpeg_write._encode_clip` - the four calls with their two
@@ -18,6 +20,12 @@ session.  Prints one JSON line per measurement:
               per frame (PIL at its own quality 75); and PIL asked for the device writer's settings, quality 95 and
               4:2:0, for the like-for-like cost
   sizes       bytes per frame of the three
+  search      `jpeg_write.jpeg_quality_for_bytes` for the bytes the clip has at quality 75: a host clock around the search and
+              a final synchronise, the probes it made, and the same clock around one `encode_jpeg_device` at quality 95
+  roi_table   bytes per frame and PSNR against the source of the round trip at quality 95 with a map of levels 0 / 12 / 24 on
+              the 8-pixel grid, drawn as `synth.synth_level_maps` draws the benchmark's maps (shares 0.35 / 0.25 / 0.40 - its
+              two deepest levels are one here - then the 5 x 5 majority filter), and of the uniform quality that the
+              search finds for the same bytes
 """
 import argparse
 import json
@@ -97,6 +105,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--restart-rows", type=int, default=0)
     ap.add_argument("--restart-mcus", type=int, default=0)
+    ap.add_argument("--roi-levels", choices=("none", "zero", "random"), default="none")
+    ap.add_argument("--roi-block-size", type=int, default=16)
     ap.add_argument("--measure", default="encode,roundtrip,writers,sizes")
     args = ap.parse_args()
     measure = set(args.measure.split(","))
@@ -115,8 +125,19 @@ def main():
         os.makedirs(d, exist_ok=True)
     paths = {k: [os.path.join(d, f"{i + 1:05d}.jpg") for i in range(n)] for k, d in dirs.items()}
 
-    encode = (lambda: jpeg_write._encode_clip(clip, "bgr", 95, "420", "bench", restart=restart)) if any(restart) else \
-        (lambda: jpeg_write._encode_clip(clip, "bgr", 95, "420", "bench"))
+    roi_kw = {}
+    if args.roi_levels != "none":
+        B = args.roi_block_size
+        grid = (n, -(-h // B), -(-w // B))
+        levels = np.zeros(grid, np.uint8) if args.roi_levels == "zero" else np.random.default_rng(11).integers(0, 49, size=grid).astype(np.uint8)
+        roi_kw = dict(roi_levels=torch.from_numpy(levels).to(dev), roi_block_size=B)
+        setting.update(roi_levels=args.roi_levels, roi_block_size=B)
+    if roi_kw:
+        encode = lambda: jpeg_write._encode_clip(clip, "bgr", 95, "420", "bench", restart=restart, **roi_kw)
+    elif any(restart):
+        encode = lambda: jpeg_write._encode_clip(clip, "bgr", 95, "420", "bench", restart=restart)
+    else:
+        encode = lambda: jpeg_write._encode_clip(clip, "bgr", 95, "420", "bench")
     if "encode" in measure:
         times = []
         encode()
@@ -145,6 +166,45 @@ def main():
                encode_calls_ms=round(sum(v for k, v in calls.items() if k in ("elvis_jpeg_fdct", "elvis_jpeg_bits", "elvis_jpeg_pack", "elvis_jpeg_stuff",
                                                                              "elvis_jpeg_bits_rst", "elvis_jpeg_pack_rst", "elvis_jpeg_stuff_rst")), 3),
                reader_entropy_ms=calls.get("elvis_jpeg_entropy"), bytes_per_frame=round(float(roundtrip()[1].mean())))
+
+    if "search" in measure:
+        kw = dict(restart_kw, **roi_kw)
+        target = int(jpeg_write.jpeg_encoded_sizes_device(clip, 75, **kw).sum())
+        probes = []
+        real = jpeg_write.jpeg_encoded_sizes_device
+
+        def counted(frames_d, quality, *a, **k):
+            probes.append(int(quality))
+            return real(frames_d, quality, *a, **k)
+
+        jpeg_write.jpeg_encoded_sizes_device = counted
+        try:
+            quality, sizes, fits = jpeg_write.jpeg_quality_for_bytes(clip, target, **kw)
+            count = len(probes)
+            search = host_ms(lambda: jpeg_write.jpeg_quality_for_bytes(clip, target, **kw), args.reps)
+        finally:
+            jpeg_write.jpeg_encoded_sizes_device = real
+        one = host_ms(lambda: jpeg_write.encode_jpeg_device(clip, **kw), args.reps)
+        probe = host_ms(lambda: jpeg_write.jpeg_encoded_sizes_device(clip, 95, **kw), args.reps)
+        report(measurement="search", **setting, frames=n, target_bytes=target, quality=quality, fits=fits, clip_bytes=int(sizes.sum()), probes=count,
+               probed=probes[:count], search_ms=round(search[0], 2), search_ms_min=round(search[1], 2), search_ms_max=round(search[2], 2),
+               one_encode_ms=round(one[0], 2), one_sizes_probe_ms=round(probe[0], 2), search_over_one_encode=round(search[0] / one[0], 2))
+
+    if "roi_table" in measure:
+        def psnr(decoded):
+            err = (decoded.to(torch.float32) - clip.to(torch.float32)).pow(2).mean().item()
+            return round(10 * np.log10(255.0 ** 2 / err), 2) if err else float("inf")
+
+        B, shares = 8, (0.35, 0.25, 0.40)
+        levels = (synth.synth_level_maps(20260502, n, -(-h // B), -(-w // B), shares) * 12).astype(np.uint8)
+        plain, plain_bytes = jpeg_write.jpeg_roundtrip_device(clip, 95, restart_rows=1)
+        mapped, mapped_bytes = jpeg_write.jpeg_roundtrip_device(clip, 95, restart_rows=1, roi_levels=levels, roi_block_size=B)
+        equal, equal_bytes, quality, fits = jpeg_write.jpeg_roundtrip_at_bytes_device(clip, int(mapped_bytes.sum()), restart_rows=1)
+        report(measurement="roi_table", frames=n, height=h, width=w, roi_block_size=B, level_shares_drawn=dict(zip(("0", "12", "24"), shares)),
+               level_shares_of_cells={str(v): round(float((levels == v).mean()), 3) for v in (0, 12, 24)},
+               q95_bytes_per_frame=round(float(plain_bytes.mean())), q95_psnr=psnr(plain),
+               q95_roi_bytes_per_frame=round(float(mapped_bytes.mean())), q95_roi_psnr=psnr(mapped),
+               uniform_quality_at_equal_bytes=quality, uniform_fits=fits, uniform_bytes_per_frame=round(float(equal_bytes.mean())), uniform_psnr=psnr(equal))
 
     if not measure & {"writers", "sizes"}:
         return
