@@ -46,7 +46,7 @@ from .fvmd import (FvmdConfig, FvmdNoTrajectories, calculate_fvmd, calculate_fvm
 from .png import decode_png_device, encode_png_device, load_frames_device, save_frames, save_frames_device  # noqa: F401
 from .jpeg import decode_jpeg_device, load_images_device, load_jpeg_frames_device, parse_jpeg  # noqa: F401
 from .jpeg_write import (JPEG_ROI_MAX_LEVEL, encode_jpeg_device, jpeg_encoded_sizes_device, jpeg_file_header, jpeg_quality_for_bytes,  # noqa: F401
-                         jpeg_quant_tables, jpeg_restart_interval, jpeg_roi_levels, jpeg_roi_scale16, jpeg_roundtrip_at_bytes_device,
+                         jpeg_optimal_tables, jpeg_quant_tables, jpeg_restart_interval, jpeg_roi_levels, jpeg_roi_scale16, jpeg_roundtrip_at_bytes_device,
                          jpeg_roundtrip_device, save_jpeg_frames, save_jpeg_frames_device)
 from .segment import SegmentConfig, foreground_masks_device, save_foreground_masks, segment_frames  # noqa: F401
 from .drivers import calculate_removability_scores_device  # noqa: F401

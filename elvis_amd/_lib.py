@@ -145,6 +145,10 @@ SIGNATURES = {
     "elvis_jpeg_bits_rst": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_jpeg_pack_rst": [vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_jpeg_stuff_rst": [vp, vp, vp, i64, vp, i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_jpeg_tally": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_jpeg_optimal_tables": [vp, i32, i32, vp, vp, vp, vp],
+    "elvis_jpeg_bits_ftab": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "elvis_jpeg_pack_ftab": [vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp],
     "elvis_rrdb_packed_weight_bytes": [i32, i32],
     "elvis_rrdb_pack_weights": [vp, i32, i32, i32, i32, vp],
     "elvis_rrdb_conv3x3": [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, i32, vp],

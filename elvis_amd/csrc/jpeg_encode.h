@@ -1,10 +1,11 @@
 // The baseline JPEG encoder of csrc/jpeg_write.hip, host and device: the geometry of a frame's blocks in MCU scan order,
 // the sample a component has at a plane position (colour conversion, edge replication and downsampling in libjpeg's
 // order), the two passes of jfdctint.c, the quantiser, the quantisation tables of jpeg_set_quality, and the symbol rule
-// of one block (ITU-T T.81 F.1.2) over a sink that either counts bits or writes them at a bit offset - written once.  On
-// the device a lane takes a row, a column or a block; on the host the same text is plain C++, so that
-// tools/jpeg_encode_check.cpp walks the very code of the kernels over exact-size buffers under the address and
-// undefined-behaviour sanitizers.  tests/_jpeg_write_ref.py states what it computes.
+// of one block (ITU-T T.81 F.1.2) over a sink that counts bits, writes them at a bit offset or tallies the symbols, and
+// the optimal-table rule of jchuff.c for the host - written once.  On the device a lane takes a row, a column or a
+// block; on the host the same text is plain C++, so that tools/jpeg_encode_check.cpp walks the very code of the kernels
+// over exact-size buffers under the address and undefined-behaviour sanitizers.  tests/_jpeg_write_ref.py states what it
+// computes, tests/_jpeg_opt_ref.py the tally and the tables.
 //
 // Rules kept here: every pixel read goes through a clamp to the frame; every table index goes through a mask; every
 // stream word written is checked against the word count of its own segment (a frame, or one restart interval of it); a
@@ -281,10 +282,12 @@ JPGE_HD int jpeg_quant_value(int quality, int which, int i) {
 }
 
 // ----------------------------------------------------------------------------- the symbol rule of a block
-// A sink that counts.
+// A sink takes a block's symbols as indices into its table class's JPGE_HUFF_WORDS entries (`symbol`) and the magnitude
+// bits behind them (`put`).  A sink that counts:
 struct JpegBitCounter {
     uint32_t bits = 0;
     JPGE_HDM void put(uint32_t, int len) { bits += (uint32_t)len; }
+    JPGE_HDM void symbol(const uint32_t* tab, int index) { bits += tab[index] & 31u; }
 };
 
 // A sink that writes at a bit offset into a frame's stream of 32-bit words, the first bit of the stream in bit 31 of
@@ -313,9 +316,27 @@ struct JpegBitWriter {
             acc &= (1ull << n) - 1ull;
         }
     }
+    JPGE_HDM void symbol(const uint32_t* tab, int index) {
+        const uint32_t e = tab[index];
+        put(e >> 5, (int)(e & 31));
+    }
     JPGE_HDM void flush() {
         if (n > 0 && at < nwords) JPGE_OR(words + at, (uint32_t)(acc << (32 - n)));
     }
+};
+
+// A sink that tallies: entry `index` of the histogram the block is handed in the table's place goes up by one, the
+// magnitude bits count for nothing.  On the device the histogram is the workgroup's, in LDS, and its blocks are other
+// lanes (a vector atomic); on the host they are earlier iterations.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define JPGE_INC(p) atomicAdd((p), 1u)
+#else
+#define JPGE_INC(p) (++*(p))
+#endif
+struct JpegSymbolTally {
+    uint32_t* hist;            // JPGE_HUFF_WORDS entries of the block's table class
+    JPGE_HDM void put(uint32_t, int) {}
+    JPGE_HDM void symbol(const uint32_t*, int index) { JPGE_INC(hist + index); }
 };
 
 JPGE_HD int jpeg_category(int v) {
@@ -326,12 +347,11 @@ JPGE_HD int jpeg_category(int v) {
 // One block's symbols (T.81 F.1.2): the DC difference's category and bits, then per non-zero AC coefficient ZRLs for
 // runs above 15, the (run, category) symbol and the bits; EOB unless coefficient 63 is not zero.  zz: the block in zig-zag
 // order; tab: JPGE_HUFF_WORDS entries of the block's table class, (code << 5) | length, length 0 for a symbol the table
-// does not have (nothing goes out for it).
+// does not have (nothing goes out for it).  A symbol's index is its category (DC) or 16 + its value (AC).
 template <class Sink>
 JPGE_HD void jpeg_encode_block(const int16_t* zz, int pred, const uint32_t* tab, Sink& sink) {
     int v = (int)zz[0] - pred, cat = jpeg_category(v);
-    uint32_t e = tab[cat & 15];
-    sink.put(e >> 5, (int)(e & 31));
+    sink.symbol(tab, cat & 15);
     if (cat) sink.put((uint32_t)(v < 0 ? v + (1 << cat) - 1 : v), cat);
     int run = 0;
 #pragma unroll
@@ -342,18 +362,143 @@ JPGE_HD void jpeg_encode_block(const int16_t* zz, int pred, const uint32_t* tab,
             continue;
         }
         while (run > 15) {
-            e = tab[16 + 0xF0];
-            sink.put(e >> 5, (int)(e & 31));
+            sink.symbol(tab, 16 + 0xF0);
             run -= 16;
         }
         cat = jpeg_category(v);
-        e = tab[16 + (((run << 4) | cat) & 255)];
-        sink.put(e >> 5, (int)(e & 31));
+        sink.symbol(tab, 16 + (((run << 4) | cat) & 255));
         sink.put((uint32_t)(v < 0 ? v + (1 << cat) - 1 : v), cat & 15);
         run = 0;
     }
-    if (run) {
-        e = tab[16];
-        sink.put(e >> 5, (int)(e & 31));
+    if (run) sink.symbol(tab, 16);
+}
+
+// ----------------------------------------------------------------------------- optimal tables (host planning work)
+// jpeg_gen_optimal_table of libjpeg's jchuff.c (T.81 K.2) in plain C++: from the counts of a table's symbols to the
+// DHT contents - the codes of each length 1..16 and the symbols in code order.  freq: `nsym` counts by symbol value (16
+// for a DC table, 256 for an AC one), each below 2^26.  A reserved symbol 256 of frequency 1 keeps every real code from
+// being all ones.  The two least frequent entries are merged until one is left, ties to the largest index; lengths
+// above 16 are shortened by the rule of K.2 (figure K.3); the reserved symbol leaves the longest length; the symbols are
+// listed by the length the merge gave them, by value within a length.  Returns the number of symbols, 0 for a histogram
+// without one or for one whose longest code would pass 32 bits before limiting (libjpeg's JERR_HUFF_CLEN_OVERFLOW):
+// nothing is written then.  `prelimit`, when not null, receives the longest length before limiting.
+#define JPGE_OPT_MAX_CLEN 32
+inline int jpeg_gen_optimal_table(const uint32_t* freq_in, int nsym, uint8_t* counts16, uint8_t* symbols, int* prelimit) {
+    int64_t freq[257];
+    int codesize[257], others[257], bits[JPGE_OPT_MAX_CLEN + 1];
+    nsym = nsym < 0 ? 0 : (nsym > 256 ? 256 : nsym);
+    bool any = false;
+    for (int i = 0; i < 257; ++i) {
+        freq[i] = i < nsym ? (int64_t)freq_in[i] : 0;
+        any = any || freq[i] != 0;
+        codesize[i] = 0;
+        others[i] = -1;
     }
+    if (!any) return 0;
+    freq[256] = 1;
+    int live[257], m = 0;       // the entries whose frequency is not zero, in ascending order: only they are searched
+    for (int i = 0; i <= 256; ++i)
+        if (freq[i]) live[m++] = i;
+    for (;;) {
+        int p1 = -1, p2 = -1;
+        int64_t v = INT64_MAX;
+        for (int k = 0; k < m; ++k) {
+            if (freq[live[k]] <= v) {
+                v = freq[live[k]];
+                p1 = k;
+            }
+        }
+        v = INT64_MAX;
+        for (int k = 0; k < m; ++k) {
+            if (freq[live[k]] <= v && k != p1) {
+                v = freq[live[k]];
+                p2 = k;
+            }
+        }
+        if (p2 < 0) break;
+        int c1 = live[p1], c2 = live[p2];
+        freq[c1] += freq[c2];
+        freq[c2] = 0;
+        --m;
+        for (int k = p2; k < m; ++k) live[k] = live[k + 1];
+        ++codesize[c1];
+        while (others[c1] >= 0) {
+            c1 = others[c1];
+            ++codesize[c1];
+        }
+        others[c1] = c2;
+        ++codesize[c2];
+        while (others[c2] >= 0) {
+            c2 = others[c2];
+            ++codesize[c2];
+        }
+    }
+    for (int i = 0; i <= JPGE_OPT_MAX_CLEN; ++i) bits[i] = 0;
+    int longest = 0;
+    for (int i = 0; i <= 256; ++i) {
+        if (codesize[i] > JPGE_OPT_MAX_CLEN) return 0;
+        if (codesize[i]) ++bits[codesize[i]];
+        longest = codesize[i] > longest ? codesize[i] : longest;
+    }
+    if (prelimit) *prelimit = longest;
+    for (int i = JPGE_OPT_MAX_CLEN; i > 16; --i) {
+        while (bits[i] > 0) {
+            int j = i - 2;
+            while (j > 0 && bits[j] == 0) --j;
+            if (j == 0) return 0;       // cannot happen for a complete code; the walk stays inside the array
+            bits[i] -= 2;
+            bits[i - 1] += 1;
+            bits[j + 1] += 2;
+            bits[j] -= 1;
+        }
+    }
+    int top = 16;
+    while (top > 0 && bits[top] == 0) --top;
+    if (top == 0) return 0;
+    --bits[top];
+    int p = 0;
+    for (int len = 1; len <= JPGE_OPT_MAX_CLEN; ++len)
+        for (int j = 0; j < 256; ++j)
+            if (codesize[j] == len) symbols[p++] = (uint8_t)j;
+    for (int len = 1; len <= 16; ++len) counts16[len - 1] = (uint8_t)bits[len];
+    return p;
+}
+
+// The words the kernels look up, (code << 5) | length by symbol value, from a table's DHT contents (T.81 C.2): `tab`
+// gets `entries` words (16 for DC, 256 for AC), 0 for a symbol the table does not have.  False where the counts and
+// `nsym` do not agree, a code does not fit its length or a symbol has no entry.
+inline bool jpeg_code_words(const uint8_t* counts16, const uint8_t* symbols, int nsym, uint32_t* tab, int entries) {
+    for (int i = 0; i < entries; ++i) tab[i] = 0;
+    uint32_t code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int c = 0; c < counts16[len - 1]; ++c) {
+            if (k >= nsym || symbols[k] >= entries || code >= (1u << len)) return false;
+            tab[symbols[k++]] = (code << 5) | (uint32_t)len;
+            ++code;
+        }
+        code <<= 1;
+    }
+    return k == nsym;
+}
+
+// A frame's tables from its histograms.  hist: u32 [2, JPGE_HUFF_WORDS] in the layout of the code tables; classes: 1
+// for a gray frame (class 1 is left alone: its outputs are zeroed), 2 for colour.  counts u8 [2, 2, 16] and symbols u8
+// [2, 2, 256] by class and kind (0 DC, 1 AC), nsym int [2, 2], ehuff u32 [2, JPGE_HUFF_WORDS].  Returns 0, or 1 + the
+// index 2 * class + kind of the first table that has no symbol.
+inline int jpeg_frame_optimal_tables(const uint32_t* hist, int classes, uint8_t* counts, uint8_t* symbols, int* nsym, uint32_t* ehuff) {
+    for (int i = 0; i < 2 * 2 * 16; ++i) counts[i] = 0;
+    for (int i = 0; i < 2 * 2 * 256; ++i) symbols[i] = 0;
+    for (int i = 0; i < 2 * JPGE_HUFF_WORDS; ++i) ehuff[i] = 0;
+    for (int i = 0; i < 4; ++i) nsym[i] = 0;
+    for (int t = 0; t < classes && t < 2; ++t) {
+        for (int kind = 0; kind < 2; ++kind) {
+            const int at = 2 * t + kind, entries = kind ? 256 : 16;
+            const uint32_t* freq = hist + t * JPGE_HUFF_WORDS + (kind ? 16 : 0);
+            nsym[at] = jpeg_gen_optimal_table(freq, entries, counts + at * 16, symbols + at * 256, nullptr);
+            if (nsym[at] == 0) return 1 + at;
+            if (!jpeg_code_words(counts + at * 16, symbols + at * 256, nsym[at], ehuff + t * JPGE_HUFF_WORDS + (kind ? 16 : 0), entries)) return 1 + at;
+        }
+    }
+    return 0;
 }

@@ -13,6 +13,10 @@
 //                        With a map of ROI levels (elvis_jpeg_fdct_roi) an AC coefficient that the block's coarsened
 //                        step would round to zero is zeroed (jpeg_quantise_roi): one branch, uniform over the launch.
 //   jpeg_bits_kernel     a lane per block: the bit length of its code from the DC difference and the AC symbols.
+//                        In its tally mode (elvis_jpeg_tally) the same walk counts the symbols instead: an LDS histogram
+//                        a workgroup, its non-zero entries added to the frame's with vector atomics.  The host makes
+//                        a frame's own Huffman tables of it (jpeg_gen_optimal_table, csrc/jpeg_encode.h), and the
+//                        _ftab entry points hand bits and pack a table set per frame (a run-time stride).
 //   jpeg_scan_kernel     a workgroup per segment: exclusive prefix sum in place, kScanChunk values a step with a carry;
 //                        the total goes behind the last value.  Used for the block bit offsets and the FF counts.
 //   jpeg_clear_kernel    zeroes the stream words the pack kernel ORs into: no result depends on what the buffer held.
@@ -121,16 +125,42 @@ __device__ __forceinline__ void load_block(const int16_t* __restrict__ src, int1
 }
 
 // coef -> bits u32 [nseg, segb + 1]: element i of a segment is the bit length of its block i (the scan makes offsets of
-// them), 0 past the blocks of a frame's last segment.  grid (segb / 256, segments).
+// them), 0 past the blocks of a frame's last segment.  grid (segb / 256, segments).  Frame f's tables are ehuff + f *
+// table_stride (0: one set for the clip).
+// With `hist` (u32 [n, 2, JPGE_HUFF_WORDS], zeroed by an earlier launch) the launch tallies instead: nothing is looked up
+// and no bit length written; the workgroup - it lies inside one segment, so inside one frame - counts its blocks' symbols
+// in LDS and adds the entries that are not zero to its frame's histogram (vector atomics).  The branch is the same for
+// every lane of the launch.
 __global__ __launch_bounds__(kBlockThreads) void jpeg_bits_kernel(const int16_t* __restrict__ coef, JpegEncGeom g,
-                                                                  const uint32_t* __restrict__ ehuff, uint32_t* __restrict__ bits, int nseg) {
+                                                                  const uint32_t* __restrict__ ehuff, long long table_stride,
+                                                                  uint32_t* __restrict__ bits, int nseg, uint32_t* __restrict__ hist) {
     __shared__ uint32_t tab[2 * JPGE_HUFF_WORDS];
-    stage_tables(tab, ehuff);
     const size_t q = segment_index();
-    const int i = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (q >= (size_t)nseg || i >= g.segb) return;
+    if (q >= (size_t)nseg) return;      // the whole workgroup
     const size_t f = q / (size_t)g.segs;
+    const int i = blockIdx.x * kBlockThreads + threadIdx.x;
     const int b = (int)(q - f * (size_t)g.segs) * g.segb + i;
+    if (hist != nullptr) {
+        for (int k = threadIdx.x; k < 2 * JPGE_HUFF_WORDS; k += kBlockThreads) tab[k] = 0u;
+        __syncthreads();
+        if (i < g.segb && b < g.blocks) {
+            const int16_t* base = coef + f * (size_t)g.blocks * 64;
+            int16_t zz[64];
+            load_block(base + (size_t)b * 64, zz);
+            const int pb = jpeg_enc_pred_block(g, b);
+            const int pred = pb >= 0 ? base[(size_t)pb * 64] : 0;
+            JpegSymbolTally tally{tab + JPGE_HUFF_WORDS * jpeg_enc_table_class(g, b)};
+            jpeg_encode_block(zz, pred, tab, tally);
+        }
+        __syncthreads();
+        for (int k = threadIdx.x; k < 2 * JPGE_HUFF_WORDS; k += kBlockThreads) {
+            const uint32_t v = tab[k];
+            if (v) atomicAdd(hist + f * (size_t)(2 * JPGE_HUFF_WORDS) + k, v);
+        }
+        return;
+    }
+    stage_tables(tab, ehuff + f * (size_t)table_stride);
+    if (i >= g.segb) return;
     if (b >= g.blocks) {
         bits[q * ((size_t)g.segb + 1) + i] = 0u;
         return;
@@ -193,17 +223,19 @@ __device__ __forceinline__ bool span_ok(const long long* __restrict__ off, size_
     return off[f] >= 0 && off[f] <= off[f + 1] && off[f + 1] <= total && off[f + 1] - off[f] < 0x40000000LL;
 }
 
-// coef, bits (offsets) -> segment q's unstuffed stream in words[word_off[q] ..]; grid (segb / 256, segments).
+// coef, bits (offsets) -> segment q's unstuffed stream in words[word_off[q] ..]; grid (segb / 256, segments).  Frame f's
+// tables are ehuff + f * table_stride (0: one set for the clip).
 __global__ __launch_bounds__(kBlockThreads) void jpeg_pack_kernel(const int16_t* __restrict__ coef, JpegEncGeom g,
-                                                                  const uint32_t* __restrict__ ehuff, const uint32_t* __restrict__ bits,
-                                                                  const long long* __restrict__ word_off, uint32_t* __restrict__ words,
-                                                                  long long total_words, int nseg) {
+                                                                  const uint32_t* __restrict__ ehuff, long long table_stride,
+                                                                  const uint32_t* __restrict__ bits, const long long* __restrict__ word_off,
+                                                                  uint32_t* __restrict__ words, long long total_words, int nseg) {
     __shared__ uint32_t tab[2 * JPGE_HUFF_WORDS];
-    stage_tables(tab, ehuff);
     const size_t q = segment_index();
-    const int i = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (q >= (size_t)nseg || i >= g.segb) return;
+    if (q >= (size_t)nseg) return;      // the whole workgroup
     const size_t f = q / (size_t)g.segs;
+    stage_tables(tab, ehuff + f * (size_t)table_stride);
+    const int i = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (i >= g.segb) return;
     const int b = (int)(q - f * (size_t)g.segs) * g.segb + i;
     if (b >= g.blocks || !span_ok(word_off, q, total_words)) return;
     const int16_t* base = coef + f * (size_t)g.blocks * 64;
@@ -327,7 +359,7 @@ dim3 segment_grid(int x, int nseg) {
 
 // The three calls behind the transform; the entry points without an interval are their restart_mcus = 0.
 int bits_call(const char* who, const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
-              int restart_mcus, elvis_stream_t stream) {
+              int restart_mcus, elvis_stream_t stream, long long table_stride = 0) {
     JpegEncGeom g;
     int nseg = 0;
     if (int rc = check_shape(who, n, h, w, channels, sampling, g)) return rc;
@@ -336,8 +368,8 @@ int bits_call(const char* who, const int16_t* coef, const uint32_t* ehuff, uint3
     ELVIS_REQUIRE(coef && ehuff && bits, "%s: null pointer", who);
     ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)bits & 3) == 0 && ((uintptr_t)ehuff & 3) == 0,
                   "%s: coef must be 16-byte aligned, ehuff and bits 4-byte aligned", who);
-    hipLaunchKernelGGL(jpeg_bits_kernel, segment_grid(cdiv(g.segb, kBlockThreads), nseg), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g, ehuff, bits,
-                       nseg);
+    hipLaunchKernelGGL(jpeg_bits_kernel, segment_grid(cdiv(g.segb, kBlockThreads), nseg), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g, ehuff,
+                       table_stride, bits, nseg, (uint32_t*)nullptr);
     ELVIS_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)nseg), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.segb);
     ELVIS_CHECK_LAUNCH(who);
@@ -347,7 +379,7 @@ int bits_call(const char* who, const int16_t* coef, const uint32_t* ehuff, uint3
 
 int pack_call(const char* who, const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,
               int64_t total_words, uint32_t* ffc, int chunks, uint32_t* sizes, int n, int h, int w, int channels, int sampling, int restart_mcus,
-              elvis_stream_t stream) {
+              elvis_stream_t stream, long long table_stride = 0) {
     JpegEncGeom g;
     int nseg = 0;
     if (int rc = check_shape(who, n, h, w, channels, sampling, g)) return rc;
@@ -362,8 +394,8 @@ int pack_call(const char* who, const int16_t* coef, const uint32_t* ehuff, const
     hipLaunchKernelGGL(jpeg_clear_kernel, dim3((unsigned)std::max(1, std::min(4096, cdiv(total_words, 256)))), dim3(256), 0, (hipStream_t)stream, words,
                        (long long)total_words);
     ELVIS_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(jpeg_pack_kernel, segment_grid(cdiv(g.segb, kBlockThreads), nseg), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g, ehuff, bits,
-                       (const long long*)word_off, words, (long long)total_words, nseg);
+    hipLaunchKernelGGL(jpeg_pack_kernel, segment_grid(cdiv(g.segb, kBlockThreads), nseg), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g, ehuff,
+                       table_stride, bits, (const long long*)word_off, words, (long long)total_words, nseg);
     ELVIS_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(jpeg_ff_kernel, segment_grid(chunks, nseg), dim3(kScanChunk), 0, (hipStream_t)stream, bits, g.segb, (const long long*)word_off,
                        (const uint32_t*)words, (long long)total_words, ffc, chunks, nseg);
@@ -374,6 +406,28 @@ int pack_call(const char* who, const int16_t* coef, const uint32_t* ehuff, const
                        sizes, nseg);
     ELVIS_CHECK_LAUNCH(who);
     elvis_note_launch("jpeg_pack_kernel");
+    return ELVIS_OK;
+}
+
+// The tally: the histograms are zeroed by the library, then jpeg_bits_kernel runs in its tally mode over the grid of the
+// bit count.
+int tally_call(const char* who, const int16_t* coef, uint32_t* hist, int n, int h, int w, int channels, int sampling, int restart_mcus,
+               elvis_stream_t stream) {
+    JpegEncGeom g;
+    int nseg = 0;
+    if (int rc = check_shape(who, n, h, w, channels, sampling, g)) return rc;
+    if (int rc = check_restart(who, n, restart_mcus, g, nseg)) return rc;
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(coef && hist, "%s: null pointer", who);
+    ELVIS_REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)hist & 3) == 0, "%s: coef must be 16-byte aligned, hist 4-byte aligned", who);
+    const long long hist_words = (long long)n * 2 * JPGE_HUFF_WORDS;
+    hipLaunchKernelGGL(jpeg_clear_kernel, dim3((unsigned)std::max(1, std::min(4096, cdiv(hist_words, 256)))), dim3(256), 0, (hipStream_t)stream, hist,
+                       hist_words);
+    ELVIS_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(jpeg_bits_kernel, segment_grid(cdiv(g.segb, kBlockThreads), nseg), dim3(kBlockThreads), 0, (hipStream_t)stream, coef, g,
+                       (const uint32_t*)nullptr, 0LL, (uint32_t*)nullptr, nseg, hist);
+    ELVIS_CHECK_LAUNCH(who);
+    elvis_note_launch("jpeg_bits_kernel");
     return ELVIS_OK;
 }
 
@@ -489,4 +543,43 @@ extern "C" int elvis_jpeg_stuff_rst(const uint32_t* bits, const int64_t* word_of
                                     int sampling, int restart_mcus, elvis_stream_t stream) {
     return stuff_call("elvis_jpeg_stuff_rst", bits, word_off, words, total_words, ffc, chunks, out_off, out, out_bytes, n, h, w, channels, sampling,
                       restart_mcus, stream);
+}
+
+// ----------------------------------------------------------------------------- per-frame optimised tables
+extern "C" int elvis_jpeg_tally(const int16_t* coef, uint32_t* hist, int n, int h, int w, int channels, int sampling, int restart_mcus,
+                                elvis_stream_t stream) {
+    return tally_call("elvis_jpeg_tally", coef, hist, n, h, w, channels, sampling, restart_mcus, stream);
+}
+
+extern "C" int elvis_jpeg_bits_ftab(const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
+                                    int restart_mcus, elvis_stream_t stream) {
+    return bits_call("elvis_jpeg_bits_ftab", coef, ehuff, bits, n, h, w, channels, sampling, restart_mcus, stream, 2 * JPGE_HUFF_WORDS);
+}
+
+extern "C" int elvis_jpeg_pack_ftab(const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,
+                                    int64_t total_words, uint32_t* ffc, int chunks, uint32_t* sizes, int n, int h, int w, int channels, int sampling,
+                                    int restart_mcus, elvis_stream_t stream) {
+    return pack_call("elvis_jpeg_pack_ftab", coef, ehuff, bits, word_off, words, total_words, ffc, chunks, sizes, n, h, w, channels, sampling, restart_mcus,
+                     stream, 2 * JPGE_HUFF_WORDS);
+}
+
+// Host only: jpeg_gen_optimal_table of jchuff.c per frame and table (csrc/jpeg_encode.h).  No device is touched.
+extern "C" int elvis_jpeg_optimal_tables(const uint32_t* hist, int n, int channels, uint8_t* counts, uint8_t* symbols, int32_t* nsym, uint32_t* ehuff) {
+    const char* who = "elvis_jpeg_optimal_tables";
+    ELVIS_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 or 3, got %d", who, channels);
+    ELVIS_REQUIRE(n >= 0 && n <= 65535, "%s: n must be in [0, 65535], got %d", who, n);
+    if (n == 0) return ELVIS_OK;
+    ELVIS_REQUIRE(hist && counts && symbols && nsym && ehuff, "%s: null pointer", who);
+    for (int f = 0; f < n; ++f) {
+        const uint32_t* hf = hist + (size_t)f * 2 * JPGE_HUFF_WORDS;
+        for (int k = 0; k < 2 * JPGE_HUFF_WORDS; ++k)
+            ELVIS_REQUIRE(hf[k] <= (uint32_t)JPGE_MAX_BLOCKS * 64u, "%s: frame %d counts %u at entry %d, above 2^26", who, f, hf[k], k);
+        int nsym4[4];
+        const int bad = jpeg_frame_optimal_tables(hf, channels == 3 ? 2 : 1, counts + (size_t)f * 64, symbols + (size_t)f * 1024, nsym4,
+                                                  ehuff + (size_t)f * 2 * JPGE_HUFF_WORDS);
+        for (int k = 0; k < 4; ++k) nsym[(size_t)f * 4 + k] = nsym4[k];
+        ELVIS_REQUIRE(bad == 0, "%s: frame %d has no symbol for its %s table %d (or a code longer than 32 bits before limiting)", who, f,
+                      (bad - 1) & 1 ? "AC" : "DC", (bad - 1) >> 1);
+    }
+    return ELVIS_OK;
 }

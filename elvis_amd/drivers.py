@@ -43,6 +43,9 @@ or `.jpeg` are then written by the GPU from the resident clip (jpeg_write.py: ba
 device writes a restart interval of r MCU rows (jpeg_write.py `restart_rows=`) - any decoder reads the files, and the
 device reader (`png_reader="device"` of the next driver) decodes an interval per lane instead of a frame per lane, so
 turn it on whenever that reader will read the directory.  Non-zero with `jpeg_writer="pil"` is a ValueError.
+And `jpeg_optimize=False` (the default: the Annex K Huffman tables) or True: the device codes every frame with its own
+optimal tables (jpeg_write.py `optimize=True`, libjpeg's `optimize_coding`) - smaller files of the same pixels that any
+decoder reads.  True with `jpeg_writer="pil"`, or a value that is no bool, is a ValueError.
 
 Every driver also takes `png_reader="pil"` (the default: frameio.load_frame per file) or `"device"`: a worker's frame
 range is then decoded by the GPU (jpeg.load_images_device: PNG and JPEG files, told apart by their first bytes; a
@@ -82,7 +85,7 @@ JPEG_WRITERS = ("pil", "device")
 JPEG_QUALITY, JPEG_SUBSAMPLING = 95, "420"      # what cv2.imwrite uses for a .jpg name
 
 
-def _check_png_io(png_writer, png_reader, jpeg_writer="pil", jpeg_restart_rows=0) -> None:
+def _check_png_io(png_writer, png_reader, jpeg_writer="pil", jpeg_restart_rows=0, jpeg_optimize=False) -> None:
     """`png_writer=` of the directory drivers: "pil" (frameio.save_frame / save_mask, the default) or "device" (png.py:
     the files are written by the GPU - any PNG reader decodes them to the same pixels, the bytes are not PIL's) or
     "device-rle" (the same with `deflate="rle"`: runs of equal filtered bytes become matches, for masks and flat frames).
@@ -90,13 +93,19 @@ def _check_png_io(png_writer, png_reader, jpeg_writer="pil", jpeg_restart_rows=0
     decoded by the GPU into a resident clip - the same pixels).  `jpeg_writer=`: "pil" (nothing changes, the default) or
     "device" (jpeg_write.py: names ending in .jpg / .jpeg are written by the GPU at quality 95, 4:2:0).
     `jpeg_restart_rows=`: 0 (no restart interval, the default) or the MCU rows of the interval the device writer
-    writes; PIL's writer here has none, so a non-zero value needs `jpeg_writer="device"`."""
+    writes; PIL's writer here has none, so a non-zero value needs `jpeg_writer="device"`.  `jpeg_optimize=`: False (the
+    Annex K Huffman tables, the default) or True (the device writer's `optimize=True`: every frame's own optimal
+    tables); a bool, and True needs `jpeg_writer="device"` as well."""
     if jpeg_writer not in JPEG_WRITERS:
         raise ValueError(f"jpeg_writer must be one of {JPEG_WRITERS}, got {jpeg_writer!r}")
     if isinstance(jpeg_restart_rows, bool) or not isinstance(jpeg_restart_rows, (int, np.integer)) or jpeg_restart_rows < 0:
         raise ValueError(f"jpeg_restart_rows must be a non-negative integer, got {jpeg_restart_rows!r}")
     if jpeg_restart_rows and jpeg_writer != "device":
         raise ValueError(f"jpeg_restart_rows={jpeg_restart_rows} needs jpeg_writer='device', got jpeg_writer={jpeg_writer!r}")
+    if not isinstance(jpeg_optimize, (bool, np.bool_)):
+        raise ValueError(f"jpeg_optimize must be a bool, got {jpeg_optimize!r}")
+    if jpeg_optimize and jpeg_writer != "device":
+        raise ValueError(f"jpeg_optimize=True needs jpeg_writer='device', got jpeg_writer={jpeg_writer!r}")
     if png_writer not in PNG_WRITERS:
         raise ValueError(f"png_writer must be one of {PNG_WRITERS}, got {png_writer!r}")
     if png_reader not in PNG_READERS:
@@ -107,10 +116,11 @@ def _is_jpeg_name(path) -> bool:
     return os.fspath(path).lower().endswith((".jpg", ".jpeg"))
 
 
-def _write_jpeg_names(frames, paths: Sequence, device, restart_rows: int = 0):
+def _write_jpeg_names(frames, paths: Sequence, device, restart_rows: int = 0, optimize: bool = False):
     """`jpeg_writer="device"`: the frames whose path ends in .jpg / .jpeg are written by jpeg_write.py - a resident clip
     as it is (only finished files come down), host frames through one upload - with a restart interval of
-    `restart_rows` MCU rows where that is not 0.  Returns the frames and paths that are left for the other writer, in
+    `restart_rows` MCU rows where that is not 0, and with every frame's own optimal Huffman tables where `optimize` is
+    set.  Returns the frames and paths that are left for the other writer, in
     their order."""
     mine = [i for i, p in enumerate(paths) if _is_jpeg_name(p)]
     if not mine:
@@ -120,6 +130,8 @@ def _write_jpeg_names(frames, paths: Sequence, device, restart_rows: int = 0):
     kw = dict(quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING)
     if restart_rows:
         kw["restart_rows"] = int(restart_rows)      # the default call is the one it always was
+    if optimize:
+        kw["optimize"] = True
     if isinstance(frames, torch.Tensor):
         clip = frames if not rest else frames[torch.as_tensor(mine, device=frames.device)]
         jpeg_write.save_jpeg_frames_device(clip.contiguous(), [paths[i] for i in mine], **kw)
@@ -166,11 +178,12 @@ class PngDirSink:
     writer: str = "pil"
     jpeg_writer: str = "pil"
     jpeg_restart_rows: int = 0
+    jpeg_optimize: bool = False
 
     def save(self, frames, start: int, device) -> None:
         paths = [os.path.join(self.out_dir, n) for n in self.names[start:start + len(frames)]]
         if self.jpeg_writer == "device":
-            frames, paths = _write_jpeg_names(frames, paths, device, self.jpeg_restart_rows)
+            frames, paths = _write_jpeg_names(frames, paths, device, self.jpeg_restart_rows, self.jpeg_optimize)
             if not paths:
                 return
         if self.writer in _DEVICE_DEFLATE:
@@ -322,7 +335,7 @@ def _run_jobs(jobs: List[ShardJob]) -> None:
 
 def _png_jobs(builtin: Callable, _shard_fn: Optional[ShardFn], in_dir: str, out_dir: str, names: List[str],
               chunks: List[ChunkSpec], maps: np.ndarray, block_size: int, halo: int, kw: dict, png_writer: str,
-              png_reader: str, jpeg_writer: str = "pil", jpeg_restart_rows: int = 0) -> List[ShardJob]:
+              png_reader: str, jpeg_writer: str = "pil", jpeg_restart_rows: int = 0, jpeg_optimize: bool = False) -> List[ShardJob]:
     """The jobs of a directory driver, one per chunk: the resident `builtin` shard function, or the caller's `_shard_fn`
     on host frames.  `png_writer` / `png_reader` / `jpeg_writer` "device" need a GPU on every chunk."""
     for what, value in (("png_writer", png_writer), ("png_reader", png_reader), ("jpeg_writer", jpeg_writer)):
@@ -330,7 +343,7 @@ def _png_jobs(builtin: Callable, _shard_fn: Optional[ShardFn], in_dir: str, out_
             for c in chunks:
                 if c.device.type != "cuda":
                     raise RuntimeError(f"{what}='{value}' needs a GPU (got device '{c.device}'); there is no CPU path")
-    source, sink = PngDirSource(in_dir, names, png_reader), PngDirSink(out_dir, names, png_writer, jpeg_writer, jpeg_restart_rows)
+    source, sink = PngDirSource(in_dir, names, png_reader), PngDirSink(out_dir, names, png_writer, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
     return [ShardJob(_shard_fn or builtin, source, sink, _shard_fn is None, c.start, c.end, halo, maps, block_size,
                      _device_str(c.device), kw) for c in chunks]
 
@@ -361,14 +374,14 @@ _CLIP_SHARDS = {"sinsr": _sinsr_clip_shard, "blur": _blur_clip_shard, "dct": _dc
 
 
 def _write_clip(clip: torch.Tensor, directory: str, names: Sequence[str], png_writer: str, jpeg_writer: str = "pil",
-                jpeg_restart_rows: int = 0) -> None:
+                jpeg_restart_rows: int = 0, jpeg_optimize: bool = False) -> None:
     """A resident clip of frames [n,H,W,3] or of masks [n,H,W] as PNGs `names` of `directory`, with either writer: the
     device writer takes the clip as it is and only finished files come down.  `jpeg_writer` "device": names ending in
     .jpg / .jpeg are written as JPEG by the device, masks as gray, with a restart interval of `jpeg_restart_rows` MCU rows
     where that is not 0."""
     paths = [os.path.join(directory, name) for name in names]
     if jpeg_writer == "device":
-        clip, paths = _write_jpeg_names(clip, paths, clip.device, jpeg_restart_rows)
+        clip, paths = _write_jpeg_names(clip, paths, clip.device, jpeg_restart_rows, jpeg_optimize)
         if not paths:
             return
     if png_writer in _DEVICE_DEFLATE:
@@ -384,7 +397,7 @@ def _write_clip(clip: torch.Tensor, directory: str, names: Sequence[str], png_wr
 
 def _v1_shard(clip, maps, block_size, device, first_frame_index, inpaint=False, stretched_dir=None,
               fullres_masks_dir=None, png_writer="pil", inpainter="telea", inpaint_params=None, own=None, jpeg_writer="pil",
-              jpeg_restart_rows=0, **kw):
+              jpeg_restart_rows=0, jpeg_optimize=False, **kw):
     """Stretch a run of decoded shrunk frames in one launch pair and, with `inpaint`, fill their holes without leaving
     the device: the hole mask goes from the gather to the inpainter as a resident tensor.  The stretched frames and the
     full-resolution masks are written only where a directory asks for them, under the global frame numbers.
@@ -404,6 +417,8 @@ def _v1_shard(clip, maps, block_size, device, first_frame_index, inpaint=False, 
         jpeg_kw = {} if jpeg_writer == "pil" else {"jpeg_writer": jpeg_writer}    # the default call is the one it always was
         if jpeg_restart_rows:
             jpeg_kw["jpeg_restart_rows"] = jpeg_restart_rows
+        if jpeg_optimize:
+            jpeg_kw["jpeg_optimize"] = True
         if stretched_dir is not None:
             _write_clip(out[a:b], stretched_dir, names, png_writer, **jpeg_kw)
         if fullres_masks_dir is not None:
@@ -430,7 +445,7 @@ def _frames_and_maps(frames_dir: str, maps, what: str):
 
 def _restore_downsampled(builtin: Callable, kw: dict, input_frames_dir: str, output_frames_dir: str, downscale_maps,
                          block_size: int, devices, png_writer: str, png_reader: str, _shard_fn: Optional[ShardFn],
-                         jpeg_writer: str = "pil", jpeg_restart_rows: int = 0) -> None:
+                         jpeg_writer: str = "pil", jpeg_restart_rows: int = 0, jpeg_optimize: bool = False) -> None:
     """What the two Downsample drivers share once their own arguments are checked: `output_frames_dir` is cleared and
     every frame of `input_frames_dir` is written to it under the same name."""
     names, maps = _frames_and_maps(input_frames_dir, downscale_maps, "Downscale maps")
@@ -439,7 +454,7 @@ def _restore_downsampled(builtin: Callable, kw: dict, input_frames_dir: str, out
     devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
     _run_jobs(_png_jobs(builtin, _shard_fn, input_frames_dir, output_frames_dir, names, chunk_for_devices(len(names), devs),
                         maps, block_size, 0, kw if _shard_fn is None else {}, png_writer, png_reader, jpeg_writer,
-                        jpeg_restart_rows))
+                        jpeg_restart_rows, jpeg_optimize))
 
 
 def restore_downsampled_with_sinsr(
@@ -458,6 +473,7 @@ def restore_downsampled_with_sinsr(
     png_reader: str = "pil",
     jpeg_writer: str = "pil",
     jpeg_restart_rows: int = 0,
+    jpeg_optimize: bool = False,
     _shard_fn: Optional[ShardFn] = None,
     **model_kwargs,
 ) -> None:
@@ -469,11 +485,11 @@ def restore_downsampled_with_sinsr(
     are accepted and ignored, as are `parallel_chunk_length` / `per_device_workers` (the reference ignores
     them too, elvis.py:2698-2699)."""
     _ = (parallel_chunk_length, per_device_workers)
-    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows)
+    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
     kw = dict(fp32=fp32, seed=seed, schedule=schedule)
     kw.update({k: v for k, v in model_kwargs.items() if k in ("cfg",)})
     _restore_downsampled(_sinsr_clip_shard, kw, input_frames_dir, output_frames_dir, downscale_maps, block_size, devices,
-                         png_writer, png_reader, _shard_fn, jpeg_writer, jpeg_restart_rows)
+                         png_writer, png_reader, _shard_fn, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
 
 
 def restore_downsampled_with_realesrgan(
@@ -497,6 +513,7 @@ def restore_downsampled_with_realesrgan(
     png_reader: str = "pil",
     jpeg_writer: str = "pil",
     jpeg_restart_rows: int = 0,
+    jpeg_optimize: bool = False,
     _shard_fn: Optional[ShardFn] = None,
     enhance: str = "area",
 ) -> None:
@@ -510,20 +527,20 @@ def restore_downsampled_with_realesrgan(
     `enhance="reference"` (default "area"): `tile`, `tile_pad` and `pre_pad` are honoured and every stage resizes with
     Lanczos4, as `restore.restore_frames_realesrgan` describes."""
     _ = (parallel_chunk_length, per_device_workers)
-    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows)
+    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
     if _shard_fn is None:
         from .restore import _check_realesrgan_args
         _check_realesrgan_args(denoise_strength, pre_pad, fp32, model_name, enhance)
     kw = dict(model_name=model_name, denoise_strength=denoise_strength, tile=tile, tile_pad=tile_pad, pre_pad=pre_pad,
               fp32=fp32, model_path=model_path, schedule=schedule, enhance=enhance)
     _restore_downsampled(_realesrgan_clip_shard, kw, input_frames_dir, output_frames_dir, downscale_maps, block_size, devices,
-                         png_writer, png_reader, _shard_fn, jpeg_writer, jpeg_restart_rows)
+                         png_writer, png_reader, _shard_fn, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
 
 
 def _restore_in_place(builtin: Callable, _shard_fn: Optional[ShardFn], frames_dir: str, maps, block_size: int, devices,
                       halo: int, kw: dict, what: str, png_writer: str, png_reader: str, jpeg_writer: str = "pil",
-                      jpeg_restart_rows: int = 0) -> None:
-    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows)
+                      jpeg_restart_rows: int = 0, jpeg_optimize: bool = False) -> None:
+    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
     names, maps = _frames_and_maps(frames_dir, maps, what)
     if maps.size == 0 or int(np.max(maps)) <= 0:
         return   # nothing degraded: the frames stay as decoded (elvis.py:3042-3044)
@@ -538,7 +555,7 @@ def _restore_in_place(builtin: Callable, _shard_fn: Optional[ShardFn], frames_di
         os.makedirs(scratch, exist_ok=True)
         try:
             _run_jobs(_png_jobs(builtin, _shard_fn, frames_dir, scratch, names, chunks, maps, block_size, halo, kw,
-                                png_writer, png_reader, jpeg_writer, jpeg_restart_rows))
+                                png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize))
             for n in names:
                 os.replace(os.path.join(scratch, n), os.path.join(frames_dir, n))
         finally:
@@ -547,7 +564,7 @@ def _restore_in_place(builtin: Callable, _shard_fn: Optional[ShardFn], frames_di
             os.rmdir(scratch)
     else:
         _run_jobs(_png_jobs(builtin, _shard_fn, frames_dir, frames_dir, names, chunks, maps, block_size, halo, kw,
-                            png_writer, png_reader, jpeg_writer, jpeg_restart_rows))
+                            png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize))
 
 
 def restore_blur_adaptive(
@@ -567,6 +584,7 @@ def restore_blur_adaptive(
     png_reader: str = "pil",
     jpeg_writer: str = "pil",
     jpeg_restart_rows: int = 0,
+    jpeg_optimize: bool = False,
     _shard_fn: Optional[ShardFn] = None,
 ) -> None:
     """ELVIS v2 Blur client side over a directory, IN PLACE: drop-in for `restore_with_instantir_adaptive`
@@ -576,12 +594,12 @@ def restore_blur_adaptive(
     (cfg, creative_start, preview_start) and the seed have no meaning for a deterministic forward pass
     and are ignored; `parallel_chunk_length` is ignored like in the reference (elvis.py:3015)."""
     _ = (cfg, creative_start, preview_start, seed, parallel_chunk_length)
-    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows)
+    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
     if batch_size < 1:
         raise ValueError("`batch_size` must be at least 1.")
     kw = {} if _shard_fn is not None else dict(batch_size=batch_size, fp32=fp32)
     _restore_in_place(_blur_clip_shard, _shard_fn, input_frames_dir, blur_maps, block_size, devices, 0, kw, "blur_maps",
-                      png_writer, png_reader, jpeg_writer, jpeg_restart_rows)
+                      png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
 
 
 def restore_dct_adaptive(
@@ -596,6 +614,7 @@ def restore_dct_adaptive(
     png_reader: str = "pil",
     jpeg_writer: str = "pil",
     jpeg_restart_rows: int = 0,
+    jpeg_optimize: bool = False,
     _shard_fn: Optional[ShardFn] = None,
 ) -> None:
     """ELVIS v2 DCT client side over a directory, IN PLACE (the build's definition of the slot; the
@@ -604,7 +623,7 @@ def restore_dct_adaptive(
     overlap, the expand-then-trim pattern of elvis.py:1550-1566, 1650-1657)."""
     kw = {} if _shard_fn is not None else dict(fp32=fp32)
     _restore_in_place(_dct_clip_shard, _shard_fn, input_frames_dir, strength_maps, block_size, devices,
-                      max(0, int(temporal_radius)), kw, "strength_maps", png_writer, png_reader, jpeg_writer, jpeg_restart_rows)
+                      max(0, int(temporal_radius)), kw, "strength_maps", png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
 
 
 def _v1_clip(frames_dir: str, masks_npz: str, block_size: int):
@@ -627,12 +646,13 @@ def _v1_clip(frames_dir: str, masks_npz: str, block_size: int):
     return masks, names
 
 
-def _v1_kw(png_writer: str, jpeg_writer: str = "pil", jpeg_restart_rows: int = 0, **dirs) -> dict:
+def _v1_kw(png_writer: str, jpeg_writer: str = "pil", jpeg_restart_rows: int = 0, jpeg_optimize: bool = False, **dirs) -> dict:
     """The keywords of a v1 shard step: its directories, and each writer where it is not the default (a replaced
     `_shard_fn` of the default path sees the keywords it always saw)."""
     kw = dict(dirs, png_writer=png_writer) if png_writer != "pil" else dirs
     kw = dict(kw, jpeg_writer=jpeg_writer) if jpeg_writer != "pil" else kw
-    return dict(kw, jpeg_restart_rows=jpeg_restart_rows) if jpeg_restart_rows else kw
+    kw = dict(kw, jpeg_restart_rows=jpeg_restart_rows) if jpeg_restart_rows else kw
+    return dict(kw, jpeg_optimize=True) if jpeg_optimize else kw
 
 
 INPAINTERS = ("telea", "temporal")
@@ -657,12 +677,12 @@ def _check_inpainter(inpainter, inpaint_params) -> dict:
 
 def _run_v1(inpaint: bool, frames_dir: str, masks_npz: str, block_size: int, out_dir: str, block_masks_dir: Optional[str],
             devices, png_writer: str, png_reader: str, _shard_fn: Optional[ShardFn], inpainter: str = "telea",
-            inpaint_params: Optional[dict] = None, jpeg_writer: str = "pil", jpeg_restart_rows: int = 0, **dirs) -> np.ndarray:
+            inpaint_params: Optional[dict] = None, jpeg_writer: str = "pil", jpeg_restart_rows: int = 0, jpeg_optimize: bool = False, **dirs) -> np.ndarray:
     """What the two v1 drivers share: the checks, the directories (`dirs`: the ones the shard step writes, by keyword),
     the block-resolution masks, and the stretch (and `inpaint`) of every frame of `frames_dir` into `out_dir`.  With the
     temporal inpainter every worker also reads `radius` frames on either side of its own, and its shard step is told
     which frames are its own (`own`): no two workers write the same file."""
-    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows)
+    _check_png_io(png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
     params = _check_inpainter(inpainter, inpaint_params)
     masks, names = _v1_clip(frames_dir, masks_npz, block_size)
     for d in (out_dir, *dirs.values(), block_masks_dir):
@@ -674,13 +694,13 @@ def _run_v1(inpaint: bool, frames_dir: str, masks_npz: str, block_size: int, out
     devs = resolve_device_list(devices, prefer_cuda=True, allow_cpu_fallback=_shard_fn is not None)
     gpus = [d for d in devs if d.type == "cuda"]
     workers = gpus or (devs if _shard_fn is not None else devs[:1])
-    kw = _v1_kw(png_writer, jpeg_writer, jpeg_restart_rows, **dirs)
+    kw = _v1_kw(png_writer, jpeg_writer, jpeg_restart_rows, jpeg_optimize, **dirs)
     temporal = inpainter == "temporal"
     if temporal:
         kw = dict(kw, inpainter=inpainter, inpaint_params=params)
     jobs = _png_jobs(_v1_shard, _shard_fn, frames_dir, out_dir, names, chunk_for_devices(len(names), workers), masks,
                      block_size, params["radius"] if temporal else 0, kw if _shard_fn is not None else dict(kw, inpaint=inpaint),
-                     png_writer, png_reader, jpeg_writer, jpeg_restart_rows)
+                     png_writer, png_reader, jpeg_writer, jpeg_restart_rows, jpeg_optimize)
     if temporal:
         jobs = [replace(job, kw=dict(job.kw, own=(job.start, job.end))) for job in jobs]
     _run_jobs(jobs)
@@ -700,6 +720,7 @@ def stretch_shrunk_frames(
     png_reader: str = "pil",
     jpeg_writer: str = "pil",
     jpeg_restart_rows: int = 0,
+    jpeg_optimize: bool = False,
     _shard_fn: Optional[ShardFn] = None,
 ) -> np.ndarray:
     """ELVIS v1 client side over a directory (elvis.py:4534-4580): unpack the removal masks of `masks_npz`
@@ -711,7 +732,7 @@ def stretch_shrunk_frames(
     Every frame must hold exactly as many blocks as its mask keeps (`stretch_frame`'s rule): ValueError otherwise,
     before anything is written."""
     return _run_v1(False, frames_dir, masks_npz, block_size, out_dir or frames_dir, block_masks_dir, devices, png_writer,
-                   png_reader, _shard_fn, jpeg_writer=jpeg_writer, jpeg_restart_rows=jpeg_restart_rows,
+                   png_reader, _shard_fn, jpeg_writer=jpeg_writer, jpeg_restart_rows=jpeg_restart_rows, jpeg_optimize=jpeg_optimize,
                    fullres_masks_dir=fullres_masks_dir)
 
 
@@ -729,6 +750,7 @@ def restore_shrunk_frames(
     png_reader: str = "pil",
     jpeg_writer: str = "pil",
     jpeg_restart_rows: int = 0,
+    jpeg_optimize: bool = False,
     inpainter: str = "telea",
     inpaint_params: Optional[dict] = None,
     _shard_fn: Optional[ShardFn] = None,
@@ -752,7 +774,7 @@ def restore_shrunk_frames(
     if out_dir is None:
         raise ValueError("restore_shrunk_frames: out_dir is required")
     return _run_v1(True, frames_dir, masks_npz, block_size, out_dir, block_masks_dir, devices, png_writer, png_reader,
-                   _shard_fn, inpainter, inpaint_params, jpeg_writer=jpeg_writer, jpeg_restart_rows=jpeg_restart_rows,
+                   _shard_fn, inpainter, inpaint_params, jpeg_writer=jpeg_writer, jpeg_restart_rows=jpeg_restart_rows, jpeg_optimize=jpeg_optimize,
                    stretched_dir=stretched_dir,
                    fullres_masks_dir=fullres_masks_dir)
 

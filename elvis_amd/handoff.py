@@ -500,7 +500,8 @@ def roi_levels_from_importance(importance_scores, qp_range: int = 15, base_qp: i
 
 
 def encode_with_roi_device(frames_d: torch.Tensor, importance_scores, block_size: int, *, quality: int = 95, target_bytes: Optional[int] = None,
-                           qp_range: int = 15, base_qp: int = 25, subsampling: str = "420", order: str = "bgr", restart_rows: int = 1):
+                           qp_range: int = 15, base_qp: int = 25, subsampling: str = "420", order: str = "bgr", restart_rows: int = 1,
+                           optimize: bool = False):
     """The reference's ROI approach end to end on a resident clip, with the project's intra codec in the encoder's place
     (`encode_with_roi`, elvis.py:2013-2118; `create_kvazaar_roi_file` + `encode_kvazaar`, utils.py:1026-1053): the
     importance scores become levels (`roi_levels_from_importance`), with `target_bytes` (the clip's budget, bitrate * n /
@@ -508,10 +509,14 @@ def encode_with_roi_device(frames_d: torch.Tensor, importance_scores, block_size
     `jpeg_write.jpeg_roundtrip_device` encodes and decodes at that quality with the map.  `block_size`: the luma pixels
     of a cell of the importance grid, a multiple of 8.  Returns (the decoded resident clip, the bytes of every frame's
     file, int64 [n]; the quality used; the levels, uint8 [n,By,Bx]).  The files are baseline JPEG with a dead zone per
-    block: nothing is claimed about what x265, Kvazaar or SVT-AV1 would make of the same maps."""
+    block: nothing is claimed about what x265, Kvazaar or SVT-AV1 would make of the same maps.  `optimize=True` codes
+    every frame with its own optimal Huffman tables (`jpeg_write.encode_jpeg_device`), in the search and in the round
+    trip: a dead zone moves the symbol statistics towards long runs and EOBs, where the Annex K tables fit worst."""
     from . import jpeg_write
     levels = roi_levels_from_importance(importance_scores, qp_range, base_qp)
     kw = dict(restart_rows=restart_rows, roi_levels=levels, roi_block_size=block_size)
+    if jpeg_write._check_optimize(optimize, "encode_with_roi_device"):
+        kw["optimize"] = True
     if target_bytes is not None:
         quality = jpeg_write.jpeg_quality_for_bytes(frames_d, target_bytes, quality, subsampling, order, **kw)[0]
     decoded, nbytes = jpeg_write.jpeg_roundtrip_device(frames_d, quality, subsampling, order, **kw)

@@ -14,6 +14,7 @@ path for those suffixes, the writer half of jpeg.py:
   jpeg_quality_for_bytes(frames_d, target)     the bisect over the quality for a byte budget of the whole clip
   jpeg_roundtrip_at_bytes_device(frames_d, t)  that search, then the round trip at the quality found
   jpeg_roi_levels(delta_qp), jpeg_roi_scale16  host: delta QPs to the levels of `roi_levels=`, and the table behind a level
+  jpeg_optimal_tables(hist, channels)          host: symbol histograms to the optimal Huffman tables of `optimize=True`
 
 Colour conversion, edge replication, chroma downsampling, the forward DCT, the quantiser, the Huffman coding, the bit
 packing and the byte stuffing run as HIP kernels; the host plans the layout from two small downloads (a frame's bit
@@ -53,6 +54,20 @@ the cells its footprint touches (8 x 8 luma pixels for a luma block, 8 hmax x 8 
 frame; cell indices clamped to the grid, which is the floored h // B x w // B or the full one).  Bytes are not monotone
 in the level: a zeroed coefficient can turn two short symbols into a longer run.  tests/_jpeg_roi_ref.py states the
 rule.  `jpeg_quality_for_bytes` finds the quality for a byte budget from the pack call's sizes alone.
+
+Optimised Huffman tables.  `optimize=True` on every form above (the default, False, changes nothing: the same bytes, the
+same buffers, the same launches) is libjpeg's `optimize_coding`, per frame: the device counts the symbols the frame's
+scan will hold - DC difference categories and AC (run, category) symbols with ZRL and EOB, per table class, over exactly
+the blocks the scan codes, dummy blocks included, predictors reset at every restart interval, coefficients behind the
+ROI dead zone - into a histogram u32 [n, 2, 272] in the layout of the code tables (`jpeg_bits_kernel` in its tally mode,
+an LDS histogram a workgroup); the histograms come down (2 KB a frame, THE THIRD SYNCHRONISATION OF A CLIP, in front of
+the other two); the library's host entry point `elvis_jpeg_optimal_tables` restates `jpeg_gen_optimal_table` of jchuff.c
+(csrc/jpeg_encode.h) and returns every frame's DHT contents and code words; the words go up, [n, 2, 272], and the bit
+count and the pack kernel take frame f's tables at a stride.  Every file gets a header of its own, its tables in the
+four (gray: two) DHT segments where the Annex K ones stand otherwise.  Any baseline decoder reads the files, the device
+reader included.  A frame's bytes depend on that frame alone.  Against a libjpeg-turbo PIL with `optimize=True` the DHT
+segments, their position and everything behind SOS are equal byte for byte, restart intervals included;
+tests/_jpeg_opt_ref.py states the rule.
 """
 from __future__ import annotations
 
@@ -132,6 +147,12 @@ def _check_restart(restart_rows, restart_mcus, who: str) -> Tuple[int, int]:
     if int(restart_mcus) > 65535:
         raise ValueError(f"{who}: restart_mcus must be in 1..65535 (0: no interval), got {restart_mcus}")
     return int(restart_rows), int(restart_mcus)
+
+
+def _check_optimize(optimize, who: str) -> bool:
+    if not isinstance(optimize, (bool, np.bool_)):
+        raise ValueError(f"{who}: optimize must be a bool, got {optimize!r}")
+    return bool(optimize)
 
 
 def jpeg_restart_interval(width: int, height: int, channels: int = 3, subsampling: str = "420", restart_rows: int = 0,
@@ -240,17 +261,90 @@ def encode_tables() -> np.ndarray:
     return tab
 
 
+def jpeg_optimal_tables(hist, channels: int = 3):
+    """Host only (the library's `elvis_jpeg_optimal_tables`, no device): symbol histograms, uint32 [n, 2, 272] or [2, 272]
+    in the layout of `encode_tables` - per table class 16 DC entries by category, 256 AC entries by symbol - to the
+    optimal length-limited tables of libjpeg's `jpeg_gen_optimal_table`.  Returns (tables, ehuff): `tables` is a list
+    with one tuple per frame, ((counts, symbols) for DC 0, AC 0 and, for `channels` 3, DC 1, AC 1) as
+    `jpeg_file_header(huffman=)` takes it, counts a tuple of 16 and symbols the symbol values in code order; `ehuff` is
+    uint32 [n, 2, 272], (code << 5) | length, class 1 all zero for a gray clip.  A [2, 272] histogram gives one frame's
+    tuple and [2, 272].  ValueError for a table without a symbol or a count above 2^26."""
+    who = "jpeg_optimal_tables"
+    if isinstance(channels, bool) or channels not in (1, 3):
+        raise ValueError(f"{who}: channels must be 1 or 3, got {channels!r}")
+    a = np.asarray(hist)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{who}: hist must be an integer array, got {a.dtype}")
+    single = a.ndim == 2
+    if a.ndim not in (2, 3) or a.shape[-2:] != (2, HUFF_WORDS):
+        raise ValueError(f"{who}: hist must be [n, 2, {HUFF_WORDS}] or [2, {HUFF_WORDS}], got {a.shape}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) > MAX_BLOCKS * 64):
+        raise ValueError(f"{who}: counts must be in 0..2^26")
+    a = np.ascontiguousarray(a.reshape(-1, 2, HUFF_WORDS).astype(np.uint32))
+    n = a.shape[0]
+    if n > MAX_FRAMES:
+        raise ValueError(f"{who}: {n} frames (at most {MAX_FRAMES})")
+    counts = np.zeros((n, 2, 2, 16), np.uint8)
+    symbols = np.zeros((n, 2, 2, 256), np.uint8)
+    nsym = np.zeros((n, 2, 2), np.int32)
+    ehuff = np.zeros((n, 2, HUFF_WORDS), np.uint32)
+    if n:
+        check(lib().elvis_jpeg_optimal_tables(a.ctypes.data, n, int(channels), counts.ctypes.data, symbols.ctypes.data, nsym.ctypes.data,
+                                              ehuff.ctypes.data))
+    tables = [tuple((tuple(counts[f, t, k].tolist()), tuple(symbols[f, t, k, :nsym[f, t, k]].tolist()))
+                    for t in range(2 if channels == 3 else 1) for k in range(2)) for f in range(n)]
+    return (tables[0], ehuff[0]) if single else (tables, ehuff)
+
+
+def _check_huffman(huffman, channels: int, who: str):
+    """`huffman=` of `jpeg_file_header`: 2 (gray) or 4 (colour) (counts, symbols) pairs in the order DC 0, AC 0, DC 1, AC 1,
+    each a code a baseline decoder can build: 16 counts, as many distinct symbols as they add up to, 1..12 categories 0..11
+    for DC and 1..256 bytes for AC, no code past its length (T.81 C.2) and none of all ones."""
+    want = 4 if channels == 3 else 2
+    try:
+        pairs = [(tuple(int(v) for v in counts), tuple(int(v) for v in symbols)) for counts, symbols in huffman]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: huffman must be {want} (counts, symbols) pairs of integers") from None
+    if len(pairs) != want:
+        raise ValueError(f"{who}: huffman must hold {want} tables for {channels} channel(s) (DC 0, AC 0" + (", DC 1, AC 1)" if want == 4 else ")")
+                         + f", got {len(pairs)}")
+    for k, (counts, symbols) in enumerate(pairs):
+        name = f"huffman[{k}] ({'AC' if k & 1 else 'DC'} {k >> 1})"
+        if len(counts) != 16 or any(not 0 <= v <= 255 for v in counts):
+            raise ValueError(f"{who}: {name}: 16 counts in 0..255 are needed, got {counts}")
+        if sum(counts) != len(symbols) or not symbols:
+            raise ValueError(f"{who}: {name}: the counts add up to {sum(counts)} and there are {len(symbols)} symbols")
+        top = 255 if k & 1 else 11
+        if len(set(symbols)) != len(symbols) or any(not 0 <= v <= top for v in symbols):
+            raise ValueError(f"{who}: {name}: symbols must be distinct and in 0..{top}")
+        code = 0                                                 # the next code of the current length (T.81 C.2)
+        for length in range(1, 17):
+            code += counts[length - 1]
+            if counts[length - 1] and code > (1 << length) - 1:  # the last one is `length` ones, or past them
+                raise ValueError(f"{who}: {name}: the counts give a code of {length} bits that does not fit or is all ones")
+            code <<= 1
+    return pairs
+
+
 def _segment(marker: int, body: bytes) -> bytes:
     return bytes([0xFF, marker]) + struct.pack(">H", len(body) + 2) + body
 
 
+def _dht_segments(tables) -> bytes:
+    """The DHT segments of (counts, symbols) pairs in the order DC 0, AC 0 (, DC 1, AC 1): table k has class k & 1 and
+    destination k >> 1."""
+    return b"".join(_segment(0xC4, bytes([(k & 1) << 4 | k >> 1]) + bytes(counts) + bytes(symbols)) for k, (counts, symbols) in enumerate(tables))
+
+
 def jpeg_file_header(width: int, height: int, channels: int = 3, quality: int = 95, subsampling: str = "420",
-                     restart_interval: int = 0) -> bytes:
+                     restart_interval: int = 0, huffman=None) -> bytes:
     """Host only: everything of a file in front of its entropy-coded bytes - SOI, the JFIF APP0 segment, one DQT segment per
     table, SOF0, the DHT segments (DC 0, AC 0, and DC 1, AC 1 for colour), for a `restart_interval` (in MCUs) other than
     0 the DRI segment FF DD 00 04 <interval, big-endian>, where libjpeg's `write_scan_header` puts it, and SOS; the
     device's scan, which ends with EOI, follows it.  Components 1 (Y: table 0, Huffman tables 0) and, for colour, 2 and
-    3 (Cb, Cr: table 1, Huffman tables 1)."""
+    3 (Cb, Cr: table 1, Huffman tables 1).  `huffman=`: None for the Annex K tables, or the file's own as (counts,
+    symbols) for DC 0, AC 0 and, for colour, DC 1, AC 1 - what `jpeg_optimal_tables` returns for a frame - written as four
+    (two) DHT segments in the same places; tables that are no code are a ValueError."""
     who = "jpeg_file_header"
     ri = restart_interval
     if isinstance(ri, bool) or not isinstance(ri, (int, np.integer)) or not 0 <= int(ri) <= 65535:
@@ -264,18 +358,29 @@ def jpeg_file_header(width: int, height: int, channels: int = 3, quality: int = 
     hmax, vmax = _FACTORS[subsampling] if channels == 3 else (1, 1)
     comps = [(1, hmax, vmax, 0)] + ([(2, 1, 1, 1), (3, 1, 1, 1)] if channels == 3 else [])
     ntab = 2 if channels == 3 else 1
+    tables = (STD_DC[0], STD_AC[0], STD_DC[1], STD_AC[1])[:2 * ntab] if huffman is None else _check_huffman(huffman, channels, who)
     out = bytearray(b"\xff\xd8") + _segment(0xE0, _JFIF)
     for t, table in enumerate(jpeg_quant_tables(q)[:ntab]):
         out += _segment(0xDB, bytes([t]) + bytes(int(table[z]) for z in ZIGZAG))
     out += _segment(0xC0, bytes([8]) + struct.pack(">HH", int(height), int(width)) + bytes([len(comps)])
                     + b"".join(bytes([cid, h << 4 | v, tq]) for cid, h, v, tq in comps))
-    for t in range(ntab):
-        out += _segment(0xC4, bytes([t]) + bytes(STD_DC[t][0]) + bytes(STD_DC[t][1]))
-        out += _segment(0xC4, bytes([0x10 | t]) + bytes(STD_AC[t][0]) + bytes(STD_AC[t][1]))
+    out += _dht_segments(tables)
     if int(ri):
         out += _segment(0xDD, struct.pack(">H", int(ri)))
     out += _segment(0xDA, bytes([len(comps)]) + b"".join(bytes([cid, tq * 0x11]) for cid, _, _, tq in comps) + bytes([0, 63, 0]))
     return bytes(out)
+
+
+def _frame_headers(width: int, height: int, channels: int, quality: int, subsampling: str, restart_interval: int, huffman) -> List[bytes]:
+    """`jpeg_file_header(..., huffman=tables)` for every frame's tables of `jpeg_optimal_tables`, which the library has
+    checked: the header's other segments are the clip's, so they are made once and a frame's own DHT segments take the
+    place of the Annex K ones."""
+    shared = jpeg_file_header(width, height, channels, quality, subsampling, restart_interval)
+    annex = _dht_segments((STD_DC[0], STD_AC[0], STD_DC[1], STD_AC[1])[:4 if channels == 3 else 2])
+    if shared.count(annex) != 1:
+        raise RuntimeError("jpeg_write: the header does not hold its DHT segments once")
+    front, back = shared.split(annex)
+    return [front + _dht_segments(tables) + back for tables in huffman]
 
 
 # ----------------------------------------------------------------------------- the device forms
@@ -333,7 +438,7 @@ def _guarded(nbytes: int, guard: int, dev, fill: int = 0):
 
 
 def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, guard: int = 0, fill: int = 0, restart=(0, 0), roi_levels=None,
-                 roi_block_size: int = 0, sizes_only: bool = False):
+                 roi_block_size: int = 0, sizes_only: bool = False, optimize: bool = False):
     """The four calls and the two small downloads between them.  Returns None for an empty clip, else a dict: `out_buf`
     (the finished scans on the device with `guard` bytes of 0xA5 on either side), `out_off` (int64 [n + 1], frame f's scan
     is bytes out_off[f] .. out_off[f + 1] of the payload), `header`, and the work buffers with their guards (`coef_buf`,
@@ -351,8 +456,16 @@ def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, 
     `roi_levels` / `roi_block_size`: the map of the module docstring; a host array is uploaded, and the transform runs
     through `elvis_jpeg_fdct_roi`.  `sizes_only=True` stops behind the second download: no stuffing pass, no output
     buffer; the dict has `file_bytes` (int64 [n], header and markers included) instead of `out_buf`, `out` and
-    `out_off`."""
+    `out_off`.
+
+    `optimize=True`: between the transform and the bit count the tally runs (`elvis_jpeg_tally`, which zeroes the
+    histograms itself), the histograms come down - a third synchronisation, the first in order - the tables are built on
+    the host (`jpeg_optimal_tables`) and their code words uploaded, and the bit count and the pack call run through the
+    `_ftab` entry points with a table set per frame.  The dict has `headers` (a list, one per frame) in the place of
+    `header`, and gains `hist_buf` (u32 [n, 2, 272] with its guards), `huffman` (every frame's tables) and `ehuff` (the
+    uploaded words, uint32 [n, 2, 272] on the host); `file_bytes` counts every frame's own header."""
     rows, mcus = _check_restart(*restart, who)
+    optimize = _check_optimize(optimize, who)
     n, h, w, c, ocode, q, scode, roi = _check_clip(frames_d, order, quality, subsampling, who, roi_levels, roi_block_size)
     ri = jpeg_restart_interval(w, h, c, subsampling, rows, mcus)
     segs, mcus_of_frame = _check_segments(n, h, w, c, subsampling, ri, who)
@@ -373,7 +486,11 @@ def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, 
     tail = (ri,) if ri else ()          # the restart entry points take the interval behind `sampling`
     bits_fn, pack_fn, stuff_fn = ((lib().elvis_jpeg_bits_rst, lib().elvis_jpeg_pack_rst, lib().elvis_jpeg_stuff_rst) if ri else
                                   (lib().elvis_jpeg_bits, lib().elvis_jpeg_pack, lib().elvis_jpeg_stuff))
-    header = jpeg_file_header(w, h, c, q, subsampling, ri)
+    stuff_tail = tail
+    if optimize:                        # a table set per frame; these two take the interval always, 0 for none
+        bits_fn, pack_fn, tail = lib().elvis_jpeg_bits_ftab, lib().elvis_jpeg_pack_ftab, (ri,)
+    header = None if optimize else jpeg_file_header(w, h, c, q, subsampling, ri)
+    extra = {}
     s = _s(frames_d)
     with torch.cuda.device(dev):
         ehuff_d = torch.from_numpy(encode_tables().view(np.int32)).to(dev)
@@ -385,6 +502,15 @@ def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, 
             levels, by, bx, b = roi
             levels_d = levels if isinstance(levels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(levels)).to(dev)
             check(lib().elvis_jpeg_fdct_roi(ptr(frames_d), ptr(coef_d), n, h, w, c, ocode, q, scode, ptr(levels_d), by, bx, b, s), dev)
+        if optimize:
+            hist_buf, hist_d = _guarded(n * 2 * HUFF_WORDS * 4, guard, dev, fill)
+            check(lib().elvis_jpeg_tally(ptr(coef_d), ptr(hist_d), n, h, w, c, scode, ri, s), dev)
+            # a synchronisation of its own, in front of the other two: every frame's symbol counts, 2 KB a frame
+            hist = hist_d.cpu().numpy().view(np.uint32).reshape(n, 2, HUFF_WORDS)
+            huffman, ehuff = jpeg_optimal_tables(hist, c)
+            ehuff_d = torch.from_numpy(ehuff.view(np.int32)).to(dev)
+            headers = _frame_headers(w, h, c, q, subsampling, ri, huffman)
+            extra = {"headers": headers, "hist_buf": hist_buf, "huffman": huffman, "ehuff": ehuff}
         check(bits_fn(ptr(coef_d), ptr(ehuff_d), ptr(bits_d), n, h, w, c, scode, *tail, s), dev)
         # the first synchronisation of a clip: every segment's bit count (a frame is one segment without an interval)
         total_bits = bits_d.view(torch.int32).view(nseg, segb + 1)[:, segb].cpu().numpy().view(np.uint32).astype(np.int64)
@@ -402,34 +528,44 @@ def _encode_clip(frames_d: torch.Tensor, order, quality, subsampling, who: str, 
         sizes = sizes_d.cpu().numpy().view(np.uint32).astype(np.int64)
         seg_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         if sizes_only:
-            got = {"file_bytes": len(header) + np.diff(seg_off[::segs]), "header": header, "coef_buf": coef_buf, "bits_buf": bits_buf,
+            head_bytes = np.asarray([len(x) for x in extra["headers"]], np.int64) if optimize else len(header)
+            got = {"file_bytes": head_bytes + np.diff(seg_off[::segs]), "header": header, "coef_buf": coef_buf, "bits_buf": bits_buf,
                    "words_buf": words_buf, "ffc_buf": ffc_buf, "sizes_buf": sizes_buf, "blocks": blocks, "chunks": chunks}
             if ri:
                 got.update(restart_interval=ri, segments=segs, segment_blocks=segb, seg_off=seg_off)
+            if optimize:
+                del got["header"]
+                got.update(extra)
             return got
         total = int(seg_off[-1])
         seg_off_d = torch.from_numpy(seg_off).to(dev)
         out_buf, out_d = _guarded(total, guard, dev, fill)
         check(stuff_fn(ptr(bits_d), ptr(word_off_d), ptr(words_d), total_words, ptr(ffc_d), chunks, ptr(seg_off_d), ptr(out_d), total, n, h, w, c, scode,
-                       *tail, s), dev)
+                       *stuff_tail, s), dev)
     got = {"out_buf": out_buf, "out": out_d, "out_off": np.ascontiguousarray(seg_off[::segs]), "header": header, "coef_buf": coef_buf,
            "bits_buf": bits_buf, "words_buf": words_buf, "ffc_buf": ffc_buf, "sizes_buf": sizes_buf, "blocks": blocks, "chunks": chunks}
     if ri:
         got.update(restart_interval=ri, segments=segs, segment_blocks=segb, seg_off=seg_off)
+    if optimize:
+        del got["header"]
+        got.update(extra)
     return got
 
 
-def _encode_to_host(frames_d, order, quality, subsampling, who: str, restart=(0, 0), roi_levels=None, roi_block_size=0) -> List[bytes]:
-    got = _encode_clip(frames_d, order, quality, subsampling, who, restart=restart, roi_levels=roi_levels, roi_block_size=roi_block_size)
+def _encode_to_host(frames_d, order, quality, subsampling, who: str, restart=(0, 0), roi_levels=None, roi_block_size=0,
+                    optimize: bool = False) -> List[bytes]:
+    got = _encode_clip(frames_d, order, quality, subsampling, who, restart=restart, roi_levels=roi_levels, roi_block_size=roi_block_size,
+                       optimize=optimize)
     if got is None:
         return []
     host = got["out"].cpu().numpy()
     off = got["out_off"]
-    return [got["header"] + host[int(off[f]):int(off[f + 1])].tobytes() for f in range(off.size - 1)]
+    heads = got["headers"] if "headers" in got else [got["header"]] * (off.size - 1)
+    return [heads[f] + host[int(off[f]):int(off[f + 1])].tobytes() for f in range(off.size - 1)]
 
 
 def encode_jpeg_device(frames_d: torch.Tensor, order: str = "bgr", quality: int = 95, subsampling: str = "420", *, restart_rows: int = 0,
-                       restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0) -> List[bytes]:
+                       restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0, optimize: bool = False) -> List[bytes]:
     """One complete baseline JPEG file per frame of a resident contiguous uint8 clip [n,H,W,3], [n,H,W,1] or [n,H,W].
     `order` is the channel order of a 3-channel clip ("bgr", what `save_frame` takes, or "rgb"); `quality` 1..100 and
     `subsampling` "444" | "422" | "420" are libjpeg's; quality 95 and 4:2:0, the defaults, are what `cv2.imwrite` uses.
@@ -440,31 +576,36 @@ def encode_jpeg_device(frames_d: torch.Tensor, order: str = "bgr", quality: int 
     level 0..48 per cell of `roi_block_size` x `roi_block_size` luma pixels, a multiple of 8; By is H // B or ceil(H / B),
     at least 1, Bx likewise) zeroes the AC coefficients a step coarsened by the block's level would round to zero - the
     module docstring has the rule; None writes what the writer always wrote, and so does a map of zeros.
+    `optimize=True` codes every frame with its own optimal Huffman tables, written into its DHT segments (libjpeg's
+    `optimize_coding`; the module docstring has the steps): smaller files, the same pixels, one more synchronisation.
     A frame's bytes depend on that frame and its own map only, not on the frames it is encoded with.  ValueError before
     any launch for a bad argument; an empty clip gives []."""
-    return _encode_to_host(frames_d, order, quality, subsampling, "encode_jpeg_device", (restart_rows, restart_mcus), roi_levels, roi_block_size)
+    return _encode_to_host(frames_d, order, quality, subsampling, "encode_jpeg_device", (restart_rows, restart_mcus), roi_levels, roi_block_size,
+                           optimize)
 
 
 def save_jpeg_frames_device(frames_d: torch.Tensor, paths: Sequence, order: str = "bgr", quality: int = 95, subsampling: str = "420", *,
-                            restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0) -> None:
+                            restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0,
+                            optimize: bool = False) -> None:
     """`encode_jpeg_device`, and frame i written to paths[i]; directories are created as `save_frame` does."""
     paths = list(paths)
     if not isinstance(frames_d, torch.Tensor) or frames_d.dim() < 1 or len(paths) != frames_d.shape[0]:
         raise ValueError(f"save_jpeg_frames_device: {len(paths)} path(s) for the clip {tuple(getattr(frames_d, 'shape', ()))}")
     for path, data in zip(paths, _encode_to_host(frames_d, order, quality, subsampling, "save_jpeg_frames_device", (restart_rows, restart_mcus),
-                                                 roi_levels, roi_block_size)):
+                                                 roi_levels, roi_block_size, optimize)):
         os.makedirs(os.path.dirname(os.fspath(path)) or ".", exist_ok=True)
         with open(path, "wb") as f:
             f.write(data)
 
 
 def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=None, order: str = "bgr", quality: int = 95,
-                     subsampling: str = "420", restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0) -> None:
+                     subsampling: str = "420", restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0,
+                     optimize: bool = False) -> None:
     """Host frames - uint8 (H,W,3), (H,W,1) or (H,W) arrays, a list or one [n,...] array - written as JPEGs to `paths`
     through the device.  Uploaded and encoded `chunk_frames` frames at a time, by default as many as make 32 MB (5 at
     1080p); a run of equal shapes is one clip.  The files do not depend on the chunk size.  `restart_rows` / `restart_mcus`:
     as `encode_jpeg_device` takes them.  `roi_levels` / `roi_block_size`: the same, [len(frames), By, Bx] for frames of
-    one shape; every chunk takes its frames' part of the map."""
+    one shape; every chunk takes its frames' part of the map.  `optimize`: as `encode_jpeg_device` takes it."""
     who = "save_jpeg_frames"
     paths = list(paths)
     if len(frames) != len(paths):
@@ -476,6 +617,7 @@ def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=N
     _check_quality(quality, who)
     _check_subsampling(subsampling, who)
     _check_restart(restart_rows, restart_mcus, who)
+    opt_kw = {"optimize": True} if _check_optimize(optimize, who) else {}
     arrays = [np.asarray(f) for f in frames]
     for a in arrays:
         if a.dtype != np.uint8 or a.ndim not in (2, 3):
@@ -497,19 +639,21 @@ def save_jpeg_frames(frames, paths: Sequence, device="cuda:0", *, chunk_frames=N
                 end += 1
             clip = torch.from_numpy(np.ascontiguousarray(np.stack(arrays[at:end], axis=0))).to(dev)
             roi_kw = {} if roi_levels is None else {"roi_levels": roi_levels[at:end], "roi_block_size": roi_block_size}
-            save_jpeg_frames_device(clip, paths[at:end], order, quality, subsampling, restart_rows=restart_rows, restart_mcus=restart_mcus, **roi_kw)
+            save_jpeg_frames_device(clip, paths[at:end], order, quality, subsampling, restart_rows=restart_rows, restart_mcus=restart_mcus, **roi_kw,
+                                    **opt_kw)
             at = end
 
 
 def jpeg_roundtrip_device(frames_d: torch.Tensor, quality: int = 95, subsampling: str = "420", order: str = "bgr", *, restart_rows: int = 0,
-                          restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0):
+                          restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0, optimize: bool = False):
     """An intra codec in the loop: `encode_jpeg_device` at `quality`, then `jpeg.decode_jpeg_device` of those files.
     Returns (the decoded resident clip, uint8 [n,H,W,C] in the clip's own channel count and `order`; the bytes of every
     frame's file, int64 [n]) - the pixels a client would see and the rate they cost.  `restart_rows=1` gives the reader a
     segment per MCU row to decode side by side: the same pixels, sooner, for a few more bytes.  `roi_levels` /
-    `roi_block_size`: as `encode_jpeg_device` takes them."""
+    `roi_block_size`, `optimize`: as `encode_jpeg_device` takes them (`optimize=True`: the same pixels for fewer bytes)."""
     from .jpeg import decode_jpeg_device
-    files = _encode_to_host(frames_d, order, quality, subsampling, "jpeg_roundtrip_device", (restart_rows, restart_mcus), roi_levels, roi_block_size)
+    files = _encode_to_host(frames_d, order, quality, subsampling, "jpeg_roundtrip_device", (restart_rows, restart_mcus), roi_levels, roi_block_size,
+                            optimize)
     if not files:
         raise ValueError("jpeg_roundtrip_device: no frames")
     c = int(frames_d.shape[3]) if frames_d.dim() == 4 else 1
@@ -518,29 +662,33 @@ def jpeg_roundtrip_device(frames_d: torch.Tensor, quality: int = 95, subsampling
 
 
 def jpeg_encoded_sizes_device(frames_d: torch.Tensor, quality: int = 95, subsampling: str = "420", order: str = "bgr", *, restart_rows: int = 0,
-                              restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0) -> np.ndarray:
+                              restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0, optimize: bool = False) -> np.ndarray:
     """int64 [n]: the length of every file `encode_jpeg_device` would return with the same arguments - header, entropy-coded
     bytes with their stuffed zeros, restart markers and EOI - without producing the files: the transform, the bit lengths
     and the pack call run, and the second small download, the pack call's sizes, ends it.  No stuffing pass, no output
-    buffer, no download of a scan.  An empty clip gives an empty array."""
+    buffer, no download of a scan.  With `optimize=True` the tally and the table builder run as well and every frame's
+    own header, whose DHT segments differ in length, is counted.  An empty clip gives an empty array."""
     got = _encode_clip(frames_d, order, quality, subsampling, "jpeg_encoded_sizes_device", restart=(restart_rows, restart_mcus),
-                       roi_levels=roi_levels, roi_block_size=roi_block_size, sizes_only=True)
+                       roi_levels=roi_levels, roi_block_size=roi_block_size, sizes_only=True, optimize=optimize)
     return np.zeros(0, np.int64) if got is None else got["file_bytes"].astype(np.int64)
 
 
 def jpeg_quality_for_bytes(frames_d: torch.Tensor, target_bytes: int, quality_max: int = 100, subsampling: str = "420", order: str = "bgr", *,
-                           restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0):
+                           restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0, optimize: bool = False):
     """The quality whose files fit `target_bytes`, the budget of the whole clip (bitrate * n / fps / 8): (quality, the
     sizes at that quality as `jpeg_encoded_sizes_device` gives them, int64 [n]; whether they fit).  The search: quality
     1 is probed, and if the clip's bytes exceed the target the answer is (1, sizes, False); else lo = 1, hi =
     `quality_max`, and while lo < hi, mid = (lo + hi + 1) // 2 is probed: lo = mid where it fits, hi = mid - 1 where it
     does not; (lo, sizes(lo), True).  At most 8 probes, each a `jpeg_encoded_sizes_device`.  The quality returned always
-    fits.  Sizes are not strictly monotone in the quality, so it need not be the largest one that does."""
+    fits.  Sizes are not strictly monotone in the quality, so it need not be the largest one that does.  `optimize=True`
+    probes the sizes of the optimised files, headers of their own included."""
     who = "jpeg_quality_for_bytes"
     if isinstance(target_bytes, bool) or not isinstance(target_bytes, (int, np.integer)) or int(target_bytes) < 0:
         raise ValueError(f"{who}: target_bytes must be a non-negative integer, got {target_bytes!r}")
     top = _check_quality(quality_max, who)
     kw = dict(restart_rows=restart_rows, restart_mcus=restart_mcus, roi_levels=roi_levels, roi_block_size=roi_block_size)
+    if _check_optimize(optimize, who):          # the default probe is the call it always was
+        kw["optimize"] = True
     probed = {}
 
     def fits(q: int) -> bool:
@@ -560,11 +708,14 @@ def jpeg_quality_for_bytes(frames_d: torch.Tensor, target_bytes: int, quality_ma
 
 
 def jpeg_roundtrip_at_bytes_device(frames_d: torch.Tensor, target_bytes: int, quality_max: int = 95, subsampling: str = "420", order: str = "bgr", *,
-                                   restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0):
+                                   restart_rows: int = 0, restart_mcus: int = 0, roi_levels=None, roi_block_size: int = 0, optimize: bool = False):
     """An intra codec at a rate: `jpeg_quality_for_bytes` inside 1..`quality_max`, then `jpeg_roundtrip_device` at the
     quality found (quality 1 where even that does not fit).  Returns (the decoded resident clip, the bytes of every
-    frame's file, int64 [n]; the quality; whether the files fit `target_bytes`)."""
+    frame's file, int64 [n]; the quality; whether the files fit `target_bytes`).  `optimize`: on the search and on the
+    round trip alike."""
     kw = dict(restart_rows=restart_rows, restart_mcus=restart_mcus, roi_levels=roi_levels, roi_block_size=roi_block_size)
+    if _check_optimize(optimize, "jpeg_roundtrip_at_bytes_device"):
+        kw["optimize"] = True
     quality, _, fits = jpeg_quality_for_bytes(frames_d, target_bytes, quality_max, subsampling, order, **kw)
     decoded, sizes = jpeg_roundtrip_device(frames_d, quality, subsampling, order, **kw)
     return decoded, sizes, quality, fits

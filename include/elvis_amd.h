@@ -1021,7 +1021,27 @@ int elvis_jpeg_colour(const uint8_t* planes, int64_t stride_blocks, const int32_
  * and full grids.  A dummy block keeps its DC only, as in call 1.  levels = NULL with by = bx = block_size = 0 is call 1
  * itself.  Calls 2 - 4 and their restart forms follow unchanged.  ELVIS_E_INVALID before any launch for what call 1
  * refuses, a block_size that is not a positive multiple of 8, a by or bx that is neither of its two values, and a null
- * map with a non-zero by, bx or block_size. */
+ * map with a non-zero by, bx or block_size.
+ *
+ * Per-frame optimised Huffman tables (libjpeg's optimize_coding: jchuff.c encode_mcu_gather, jpeg_gen_optimal_table; T.81
+ * K.2).  Between call 1 and call 2:
+ *   elvis_jpeg_tally: hist u32 [n, 2, 272] in the layout of ehuff - per frame and table class the DC difference
+ *      categories in entries 0 .. 11 and the AC symbols (run << 4) | category, ZRL F0 and EOB 00 in entries 16 + symbol -
+ *      counted over exactly the blocks the scan codes: dummy blocks included, the DC predictors reset at every restart
+ *      interval (restart_mcus as in the restart forms, 0: none), coefficients as call 1 left them.  The call zeroes hist
+ *      itself; it is the symbol walk of call 2 over another sink, one LDS histogram a workgroup.
+ *   elvis_jpeg_optimal_tables: HOST ONLY, no device is touched: hist, downloaded, to the tables of every frame.  Per
+ *      table class t (0, and 1 for channels = 3; a gray clip builds tables 0 only and the rest is zeroed) and kind k (0 DC
+ *      from entries 0 .. 15, 1 AC from entries 16 .. 271): counts u8 [n, 2, 2, 16], the codes of each length 1 .. 16;
+ *      symbols u8 [n, 2, 2, 256], the symbols in code order; nsym i32 [n, 2, 2], how many; ehuff u32 [n, 2, 272], the
+ *      words calls 2 and 3 look up.  The rule is jpeg_gen_optimal_table's: a reserved symbol 256 of frequency 1, so that
+ *      no real code is all ones; the two entries of smallest non-zero frequency are merged, ties to the largest index,
+ *      until one is left; lengths are counted up to 32 and, from 32 down to 17, shortened by bits[i] -= 2, bits[i - 1] +=
+ *      1, bits[j + 1] += 2, bits[j] -= 1 for the first j <= i - 2 with bits[j] != 0; the reserved symbol leaves the
+ *      longest length; symbols are listed by the length the merge gave them, by value within a length.  ELVIS_E_INVALID
+ *      for a count above 2^26 (blocks a frame times 64), a table without a symbol, a code past 32 bits before limiting.
+ *   elvis_jpeg_bits_ftab, elvis_jpeg_pack_ftab: elvis_jpeg_bits_rst and elvis_jpeg_pack_rst with ehuff u32 [n, 2, 272], a
+ *      table set per frame; call 4 is unchanged.  The DHT segments of every file are the caller's. */
 #define ELVIS_JPEG_SCAN_CHUNK 256
 #define ELVIS_JPEG_STUFF_CHUNK 1024
 #define ELVIS_JPEG_MAX_SEGMENTS 16777216
@@ -1047,6 +1067,14 @@ int elvis_jpeg_pack_rst(const int16_t* coef, const uint32_t* ehuff, const uint32
 int elvis_jpeg_stuff_rst(const uint32_t* bits, const int64_t* word_off, const uint32_t* words, int64_t total_words, const uint32_t* ffc,
                          int chunks, const int64_t* out_off, uint8_t* out, int64_t out_bytes, int n, int h, int w, int channels,
                          int sampling, int restart_mcus, elvis_stream_t stream);
+int elvis_jpeg_tally(const int16_t* coef, uint32_t* hist, int n, int h, int w, int channels, int sampling, int restart_mcus,
+                     elvis_stream_t stream);
+int elvis_jpeg_optimal_tables(const uint32_t* hist, int n, int channels, uint8_t* counts, uint8_t* symbols, int32_t* nsym, uint32_t* ehuff);
+int elvis_jpeg_bits_ftab(const int16_t* coef, const uint32_t* ehuff, uint32_t* bits, int n, int h, int w, int channels, int sampling,
+                         int restart_mcus, elvis_stream_t stream);
+int elvis_jpeg_pack_ftab(const int16_t* coef, const uint32_t* ehuff, const uint32_t* bits, const int64_t* word_off, uint32_t* words,
+                         int64_t total_words, uint32_t* ffc, int chunks, uint32_t* sizes, int n, int h, int w, int channels, int sampling,
+                         int restart_mcus, elvis_stream_t stream);
 
 /* ------------------------------------------------------------------ Real-ESRGAN / RRDBNet (rrdb.hip)
  * The network behind RealESRGANer.enhance (elvis.py:2515): RRDBNet(3, 3, 64, num_block, 32, scale) on f16 NHWC tensors.
