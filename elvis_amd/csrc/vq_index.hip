@@ -191,7 +191,9 @@ extern "C" int elvis_vq_index_build(const float* codebook, int n_embed, int c, v
         q[2] = cb[(size_t)k * 3 + 2];
         memcpy(q + 3, &k, 4);
     }
-    if (hipMemcpy(workspace, img.data(), words * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    // on the caller's stream, and waited for: the host image dies at return
+    if (hipMemcpyAsync(workspace, img.data(), words * 4, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess ||
+        hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
         elvis_set_error("elvis_vq_index_build: writing the index failed");
         return ELVIS_E_RUNTIME;
     }

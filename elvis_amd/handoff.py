@@ -279,6 +279,7 @@ def _planes_to_clip(fill, count: int, height: int, width: int, dev, order: str, 
             return out
         compute = torch.cuda.current_stream(dev)
         h2d = torch.cuda.Stream(dev)
+        h2d.wait_stream(compute)                          # `planes` may be a block that work queued on `compute` still reads
         slots = 1 if step >= count else 2
         host = [torch.empty((step, rows, width), dtype=torch.uint8).pin_memory() for _ in range(slots)]
         planes = [torch.empty((step, rows, width), dtype=torch.uint8, device=dev) for _ in range(slots)]

@@ -402,9 +402,19 @@ def _shrink_inputs():
     return frames, scores, 8, 0.333
 
 
-def _shrink_topk():
+def shrink_topk_statement(frames, scores, b, amount):
+    """The statement's shrink by top-k and the flat stretch back, of any clip and scores."""
     R = importlib.import_module("_shrink_ref")
+    k = R.topk_count(amount, scores.shape[2])
+    sel = [R.topk_select(s, k) for s in scores]
+    out = np.stack([R.gather_blocks(f, so, b) for f, (m, so) in zip(frames, sel)])
+    mask = np.stack([m for m, so in sel])
+    return {"out": out, "mask": mask, "src_of": np.stack([so for m, so in sel]),
+            "back": np.stack([R.stretch_frame(o, m, b) for o, m in zip(out, mask)]),
+            "full": np.stack([np.repeat(np.repeat(m.astype(np.uint8) * 255, b, 0), b, 1) for m in mask])}
 
+
+def _shrink_topk():
     def run(dev):
         from elvis_amd import shrink
         frames, scores, b, amount = _shrink_inputs()
@@ -412,18 +422,8 @@ def _shrink_topk():
         back, full = shrink.stretch_device(out, mask, b, "flat", fullres_mask=True)
         return {"out": out, "mask": mask, "src_of": src_of, "back": back, "full": full}
 
-    def expected():
-        frames, scores, b, amount = _shrink_inputs()
-        k = R.topk_count(amount, scores.shape[2])
-        sel = [R.topk_select(s, k) for s in scores]
-        out = np.stack([R.gather_blocks(f, so, b) for f, (m, so) in zip(frames, sel)])
-        mask = np.stack([m for m, so in sel])
-        return {"out": out, "mask": mask, "src_of": np.stack([so for m, so in sel]),
-                "back": np.stack([R.stretch_frame(o, m, b) for o, m in zip(out, mask)]),
-                "full": np.stack([np.repeat(np.repeat(m.astype(np.uint8) * 255, b, 0), b, 1) for m in mask])}
-
     _add(Case("shrink_topk_stretch_40x104_b8", "shrink", (2, 40, 104), "test_gpu_shrink.py::test_full_size_clips_equal_restatement",
-              run, expected, _exact))
+              run, lambda: shrink_topk_statement(*_shrink_inputs()), _exact))
 
 
 def _shrink_passes(mode):
@@ -710,23 +710,26 @@ for _cid, _clip in BLOCK_CASES.items():
     _blocks(_cid, _clip)
 
 
+def presley_given(kind, b=8):
+    """(frames, maps) of the presley cases: tests/test_gpu_presley_degrade.py's maps on its frames cut to whole blocks."""
+    T = importlib.import_module("test_gpu_presley_degrade")
+    if kind == "scale":
+        values = np.arange(-1, b + 2, dtype=np.int32)
+        bx = (len(values) + 1) // 2
+        grid = np.full(2 * bx, 3, np.int32)
+        grid[:len(values)] = values
+        maps = np.stack([grid.reshape(2, bx), grid[::-1].reshape(2, bx)])
+        return T._frames(100 * b + 3, 2, 2 * b, bx * b, 3), maps
+    maps = np.array([[[-1, 0, 1], [2, 10, 64]], [[64, 10, 2], [1, 0, -1]]], np.int32)
+    return T._frames(200 * b + 3, 2, 2 * b, 3 * b, 3), maps
+
+
 def _presley(kind):
     """tests/test_gpu_presley_degrade.py's maps and block size 8 on its frames cut to whole blocks (the cases there are
     all ragged, and a ragged frame takes the `clone` branch of `_block_out`)."""
     R = importlib.import_module("_presley_degrade_ref")
     b = 8
-
-    def given():
-        T = importlib.import_module("test_gpu_presley_degrade")
-        if kind == "scale":
-            values = np.arange(-1, b + 2, dtype=np.int32)
-            bx = (len(values) + 1) // 2
-            grid = np.full(2 * bx, 3, np.int32)
-            grid[:len(values)] = values
-            maps = np.stack([grid.reshape(2, bx), grid[::-1].reshape(2, bx)])
-            return T._frames(100 * b + 3, 2, 2 * b, bx * b, 3), maps
-        maps = np.array([[[-1, 0, 1], [2, 10, 64]], [[64, 10, 2], [1, 0, -1]]], np.int32)
-        return T._frames(200 * b + 3, 2, 2 * b, 3 * b, 3), maps
+    given = lambda: presley_given(kind, b)
 
     def run(dev):
         from elvis_amd import degrade
@@ -1039,27 +1042,34 @@ def _plane_merge():
     """ops.plane_merge without `out=` (the DCN restorer passes its own): the 9 x 13 frames of the enhance cases, three of
     them, merged from frame 1 on.  The statement is the kernel's written contract (csrc/dcn.hip), in float32 as there:
     out = rint(clip(frame / 255 + residual, 0, 1) * 255), the residual being channel 0 of plane (frame * 3 + colour)."""
-    f0, nsel, h, w, pitch = 1, 2, 9, 13, 8
-
-    def given():
-        rng = np.random.default_rng(33)
-        frames = rng.integers(0, 256, size=(3, h, w, 3), dtype=np.uint8)
-        res = (rng.random((nsel * 3, h, w, pitch), dtype=np.float32) - np.float32(0.5)) * np.float32(0.8)
-        return frames, res
+    f0, nsel, h, w = PLANE_MERGE[:4]
 
     def run(dev):
         from elvis_amd import ops
-        frames, res = given()
+        frames, res = plane_merge_given()
         return {"out": ops.plane_merge(_up(frames, dev), ops.Act(_up(res, dev), 1), f0, nsel)}
 
-    def expected():
-        frames, res = given()
-        centre = frames[f0:f0 + nsel].astype(np.float32) / np.float32(255.0)
-        r = res[..., 0].reshape(nsel, 3, h, w).transpose(0, 2, 3, 1)
-        v = np.clip(centre + r, np.float32(0.0), np.float32(1.0)).astype(np.float32)
-        return {"out": np.rint(v * np.float32(255.0)).astype(np.uint8)}
+    _add(Case("pipeline_plane_merge_9x13", "pipeline", (3, h, w), "csrc/dcn.hip plane_merge_kernel's contract", run,
+              lambda: plane_merge_statement(*plane_merge_given()), _exact))
 
-    _add(Case("pipeline_plane_merge_9x13", "pipeline", (3, h, w), "csrc/dcn.hip plane_merge_kernel's contract", run, expected, _exact))
+
+PLANE_MERGE = (1, 2, 9, 13, 8)          # f0, nsel, h, w, pitch
+
+
+def plane_merge_given(seed=33):
+    f0, nsel, h, w, pitch = PLANE_MERGE
+    rng = np.random.default_rng(seed)
+    frames = rng.integers(0, 256, size=(3, h, w, 3), dtype=np.uint8)
+    res = (rng.random((nsel * 3, h, w, pitch), dtype=np.float32) - np.float32(0.5)) * np.float32(0.8)
+    return frames, res
+
+
+def plane_merge_statement(frames, res):
+    f0, nsel, h, w, pitch = PLANE_MERGE
+    centre = frames[f0:f0 + nsel].astype(np.float32) / np.float32(255.0)
+    r = res[..., 0].reshape(nsel, 3, h, w).transpose(0, 2, 3, 1)
+    v = np.clip(centre + r, np.float32(0.0), np.float32(1.0)).astype(np.float32)
+    return {"out": np.rint(v * np.float32(255.0)).astype(np.uint8)}
 
 
 _plane_merge()
